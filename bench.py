@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- residues/s of the RoseTTAFold forward path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|1|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|1|4|5] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one forward of the full model (config 2 = BASELINE.json configs[1]: B=4 MSAs of N=128 x L=256 per GPU,
@@ -308,6 +308,32 @@ def se3_inputs(cfg, dev, seed):
     return [t.to(dev) for t in (xyz, msa, pair, aa, oh)]
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # 64 MB (decimal: within the limit read either way)
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: write each array of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  When the whole set
+    exceeds DUMP_BUDGET_BYTES, the smallest arrays are kept whole and each larger one keeps an equal share of the rest as a
+    sample of its rows (all dims but the last flattened, the row order kept): the first rows of one permutation drawn from a
+    fixed seed, so the sample is the same from run to run and arrays with the same row count share their sampled rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    left = DUMP_BUDGET_BYTES - 256 * len(arrs)  # .npy headers
+    perms = {}
+    for i, (name, a) in enumerate(sorted(arrs.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrs) - i)
+        if a.nbytes > share:
+            rows = a.reshape(-1, a.shape[-1])
+            k = share // rows[0].nbytes
+            if rows.shape[0] not in perms:
+                perms[rows.shape[0]] = np.random.default_rng(0).permutation(rows.shape[0])
+            a = rows[np.sort(perms[rows.shape[0]][:k])]
+            log(f"dump {name}: {k} of {rows.shape[0]} rows of {tuple(arrs[name].shape)} (seeded sample)")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a CHILD process (never an exec: this process
@@ -340,6 +366,9 @@ def main():
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal on a 1-GPU box)")
     ap.add_argument("--no-graph", action="store_true", help="issue the forward's launches eagerly instead of replaying one hipGraph")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the results of the last one as DIR/<name>.npy (rank 0; with several ranks the "
+                         "gathered batch), float32, at most 64 MB in all (larger outputs as a fixed seeded sample of rows)")
     ap.add_argument("--rehearse-dist", action="store_true",
                     help="one-GPU rehearsal of the multi-GPU code path: with WORLD_SIZE=1 still create the process group and run the "
                          "barrier / gather / all-reduce of every step through it (RCCL one-rank group; collectives forced)")
@@ -350,6 +379,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: nothing has touched the GPU yet, so start the N ranks as a child job (one process
         # per GPU, torch.distributed.run -> RCCL), relay rank 0's JSON line and leave with the child's exit code
@@ -412,11 +443,13 @@ def main():
             except Exception as e:  # noqa: BLE001
                 log(f"hipGraph capture failed ({type(e).__name__}: {e}); eager launches")
 
+    gathered = [None]  # rank 0: the results of every rank from the latest step (--dump-outputs)
+
     def step():
         out = run()
         if dist_on and args.config != 5:  # the one collective of the path: gather the results on rank 0 (RCCL over xGMI)
             from rosettafold_pytorch_amd import shard
-            shard.gather_results(out[0], out[1], out[2], dst=0)
+            gathered[0] = shard.gather_results(out[0], out[1], out[2], dst=0)
         return out
 
     def fence():
@@ -443,6 +476,14 @@ def main():
         tt = torch.tensor([dt], device=dev if args.dist_backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:
+        if args.config == 5:
+            arrays = {"state": out[0], "xyz": out[1]}
+        else:
+            parts = gathered[0] or [out]
+            arrays = {**{f"logits_{k}": torch.cat([p[0][k] for p in parts]) for k in sorted(out[0])},
+                      "xyz": torch.cat([p[1] for p in parts]), "plddt": torch.cat([p[2] for p in parts])}
+        dump_outputs(arrays, args.dump_outputs)
 
     if rank == 0:
         mc = cfg["model"]

@@ -51,14 +51,14 @@ def test_ctypes_table_matches_header():
     assert _lib.lib.rf_h16_dtype() == _lib.RF_BF16
 
 
-def test_gemm_desc_layout_matches_c():
+def test_gemm_desc_layout_matches_c(tmp_path):
     """compile a tiny C program printing sizeof/offsetof of rf_gemm_desc and compare with the ctypes mirror."""
     from rosettafold_pytorch_amd._lib import GemmDesc
     fields = ["M", "kc", "a_bs", "a_ko", "b_bs", "c_bs", "c_co", "conv_n", "bias_mode", "act_eps", "alpha", "tile_cfg",
               "A", "bias", "residual", "ln_out", "ln_eps", "rs", "rs_bstride", "rs_rpb", "rs_alpha"]
     prog = '#include <stdio.h>\n#include <stddef.h>\n#include "rfmi.h"\nint main(){printf("%zu", sizeof(rf_gemm_desc));' + \
            "".join(f'printf(" %zu", offsetof(rf_gemm_desc, {f}));' for f in fields) + "return 0;}"
-    exe = "/tmp/rf_layout_check"
+    exe = str(tmp_path / "rf_layout_check")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=prog.encode(), check=True)
     out = subprocess.run([exe], capture_output=True, check=True).stdout.decode().split()
     assert int(out[0]) == ctypes.sizeof(GemmDesc)
