@@ -13,6 +13,8 @@
  *   - return value: 0 = launched; >0 = hipError_t from the launch; <0 = argument rejected
  *     (RF_EINVAL...) and nothing was launched;
  *   - dtype codes: RF_F32 = 0, RF_BF16 = 1, RF_F16 = 2.  "T" below = activation dtype chosen by the caller.
+ *     RF_F32X3 = 3 is an operand code of rf_gemm_desc.ab_dtype alone (fp32 operands, split-bf16 contraction); every other
+ *     dtype argument of every entry point rejects it with RF_EINVAL.
  *   - the kernel sources are built twice: librfmi.so computes its 16-bit MFMA contractions in bfloat16
  *     (v_mfma_f32_16x16x32_bf16) and accepts {RF_F32, RF_BF16}; librfmi_f16.so computes them in IEEE fp16
  *     (v_mfma_f32_16x16x32_f16: same rate and bytes, 11 significand bits instead of 8, range 65504) and accepts
@@ -31,6 +33,15 @@ extern "C" {
 #define RF_F32 0
 #define RF_BF16 1
 #define RF_F16 2
+/* rf_gemm_desc.ab_dtype only: A and B are fp32 in memory and each element x is split in the kernel into bf16 pieces
+ * hi = bf16(x), lo = bf16(x - hi) (round to nearest even; lo = 0 when hi is not finite, so inf / NaN propagate as on the
+ * exact path).  C = hi_a.hi_b + hi_a.lo_b + lo_a.hi_b with fp32 accumulation (v_mfma_f32_16x16x32_bf16, three per product;
+ * lo.lo is dropped): the "high" float32 matmul precision of PyTorch.  The same bf16 pieces in both libraries, so librfmi.so and
+ * librfmi_f16.so give identical results.  Error bound per element (|x| < 3.39e38, the bf16 range):
+ *   |C - C_exact| <= (3 * 2^-16 + K * 2^-23) * sum_k |a_k| |b_k|   (+ the fp32 rounding of alpha / bias / residual)
+ * (each dropped piece -- lo.lo, and the rounding of lo on either side -- is at most 2^-16 |a b|; random data sits orders of
+ * magnitude below the bound).  Takes and rejects exactly the descriptors of RF_F32. */
+#define RF_F32X3 3
 
 #define RF_EINVAL (-1)   /* inconsistent sizes / unsupported combination */
 #define RF_EALIGN (-2)   /* pointer or stride not aligned as the kernel needs */
@@ -67,7 +78,7 @@ extern "C" {
 typedef struct rf_gemm_desc {
   int32_t M, N, K;
   int32_t nb0, nb1, nb2;
-  int32_t ab_dtype;  /* RF_BF16 (MFMA path) or RF_F32 (exact f32 path) */
+  int32_t ab_dtype;  /* the library's 16-bit code (MFMA path), RF_F32 (exact f32 path) or RF_F32X3 (fp32 operands, split-bf16) */
   int32_t c_dtype;   /* RF_BF16 or RF_F32 */
   int32_t kc;
   int32_t a_mode;
@@ -109,7 +120,8 @@ typedef struct rf_gemm_desc {
 
 int rf_gemm(const rf_gemm_desc* d, void* stream);
 /* Introspection for measurement tools: the kernel family the calling thread's last rf_gemm launched (0 exact fp32, 1 generic
- * bf16 tile kernel, 2 conv3x3 implicit GEMM, 3 persistent tile kernel, 4 register-resident-weights skinny-K kernel, -1 none). */
+ * bf16 tile kernel, 2 conv3x3 implicit GEMM, 3 persistent tile kernel, 4 register-resident-weights skinny-K kernel, 5 split-bf16
+ * fp32 kernel (RF_F32X3), -1 none). */
 int rf_gemm_last_family(void);
 
 /* LayerNorm over the last dim (nn.LayerNorm, rf.py:323,328,416,435,437,442,443,565,573,580,672,

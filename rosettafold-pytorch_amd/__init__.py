@@ -5,6 +5,7 @@ from . import _lib  # noqa: F401  (fails loudly without the HIP library)
 from . import ops  # noqa: F401
 from .model import *  # noqa: F401,F403
 from .model import set_compute_dtype, RT  # noqa: F401
+from .model import set_float32_matmul_precision, get_float32_matmul_precision  # noqa: F401
 from .structure import *  # noqa: F401,F403
 from .structure import flat_state  # noqa: F401
 from .model import invalidate_weight_caches  # noqa: F401

@@ -2,7 +2,7 @@
 //
 // Every dense contraction of the RoseTTAFold forward path goes through here (nn.Linear
 // rf.py:195-281; einsums rf.py:254,257,424,592,916; 3x3 dilated convs rf.py:452-457, resnet.py:19-38
-// as implicit GEMM).  Two code paths share one descriptor:
+// as implicit GEMM).  Three code paths share one descriptor:
 //   * bf16 path: v_mfma_f32_16x16x32_bf16, fp32 accumulate.  256-thread workgroups (4 waves as 2x2),
 //     BMxBN output tile, BK-deep K steps, both operand tiles staged global->LDS with
 //     global_load_lds_dwordx4 (no VGPR round trip), double buffered, one barrier per K step.
@@ -15,6 +15,8 @@
 //     (neighbouring N tiles of one activation row panel share an L2).
 //   * f32 path: exact fp32 FMA tiles (parity mode and the SE(3) module, which the reference
 //     forces to fp32: se3_modules.py:164).
+//   * split-bf16 f32 path (ab_dtype RF_F32X3, the "high" float32 matmul precision): fp32 operands split in-kernel into
+//     bf16 hi + lo pieces, three bf16 MFMAs per product (hi.lo, lo.hi, hi.hi) into fp32 accumulators.
 #include <type_traits>
 
 #include "common.h"
@@ -509,6 +511,47 @@ __device__ __forceinline__ float a_elem_f32(const rf_gemm_desc& d, const float* 
   return Ab[split_off(m, d.a_rc, d.a_ro, d.a_ri) + (int64_t)(k / d.kc) * d.a_ko + (k % d.kc)];
 }
 
+// epilogue of the fp32-operand kernels: the lane's 4 accumulators are C[m][nb .. nb+3] (before alpha / bias / act / residual)
+__device__ __forceinline__ void f32_epilogue4(const GemmP& p, int64_t c_row, int m, int nb, const f32x4 acc) {
+  const rf_gemm_desc& d = p.d;
+  if (p.vec_store && d.c_cc <= 0 && nb + 3 < d.N) {  // 16-byte (fp32) / 8-byte (bf16) store of the lane's 4 columns
+    const int64_t o = c_row + nb;
+    float4 bc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (d.bias_mode == RF_BIAS_COL) bc = *(const float4*)(d.bias + nb);
+    const float bm = d.bias_mode == RF_BIAS_ROW ? d.bias[m] : 0.f;
+    const float bv[4] = {bc.x + bm, bc.y + bm, bc.z + bm, bc.w + bm};
+    float v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      v[r] = apply_act(acc[r] * d.alpha + bv[r], d.act, d.act_eps, (d.act_nvalid < 0 ? m < -d.act_nvalid : nb + r < d.act_nvalid));
+    if (d.residual) {
+      const float4 rr = *(const float4*)(d.residual + o);
+      v[0] += rr.x; v[1] += rr.y; v[2] += rr.z; v[3] += rr.w;
+    }
+    if (d.c_dtype == RF_F32) {
+      *(float4*)((float*)d.C + o) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+      uint2 w;
+      w.x = rf_pack2_h16(v[0], v[1]);
+      w.y = rf_pack2_h16(v[2], v[3]);
+      *(uint2*)((h16_t*)d.C + o) = w;
+    }
+    return;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = nb + r;
+    if (n >= d.N) continue;
+    float x = acc[r] * d.alpha;
+    if (d.bias_mode == RF_BIAS_COL) x += d.bias[n];
+    if (d.bias_mode == RF_BIAS_ROW) x += d.bias[m];
+    x = apply_act(x, d.act, d.act_eps, (d.act_nvalid < 0 ? m < -d.act_nvalid : n < d.act_nvalid));
+    const int64_t o = c_row + split_off(n, d.c_cc, d.c_co, 1);
+    if (d.residual) x += d.residual[o];
+    st(d.C, d.c_dtype, o, x);
+  }
+}
+
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP p) {
   // Exact fp32: v_mfma_f32_16x16x4_f32 is bit-for-bit a k-ordered fmaf chain (no reduced-precision inputs), at the
   // fp32 matrix rate.  64x64 tile, BK=16, 4 waves x (32x32 = 2x2 MFMA tiles); generic (strided / conv) operand loads.
@@ -583,45 +626,191 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmP p) {
     if (m >= d.M) continue;
     const int64_t c_row = c_z + split_off(m, d.c_rc, d.c_ro, d.c_ri);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int nb = n0 + wc * 32 + j * 16 + 4 * fq;
-      if (p.vec_store && d.c_cc <= 0 && nb + 3 < d.N) {  // 16-byte (fp32) / 8-byte (bf16) store of the lane's 4 columns
-        const int64_t o = c_row + nb;
-        float4 bc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (d.bias_mode == RF_BIAS_COL) bc = *(const float4*)(d.bias + nb);
-        const float bm = d.bias_mode == RF_BIAS_ROW ? d.bias[m] : 0.f;
-        const float bv[4] = {bc.x + bm, bc.y + bm, bc.z + bm, bc.w + bm};
-        float v[4];
+    for (int j = 0; j < 2; ++j) f32_epilogue4(p, c_row, m, n0 + wc * 32 + j * 16 + 4 * fq, acc[i][j]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// split-bf16 fp32 kernel (RF_F32X3, "high" float32 matmul precision)
+// ------------------------------------------------------------------------------------------------
+// fp32 operands are read from memory as they are and split while the tile is written to LDS: x = x_0 + x_1 + ... with
+// x_0 = bf16(x), x_1 = bf16(x - x_0), ... (every subtraction is exact in fp32).  The product keeps the pieces (p, q)
+// with p + q < P, smallest first, each one v_mfma_f32_16x16x32_bf16 into the same fp32 accumulator: P = 2 is the 3-product
+// "bf16x3" split.  Always bf16, in both builds: fp16 pieces would bring range limits and subnormal residues.
+typedef __attribute__((ext_vector_type(2))) __bf16 rf_bf16x2;
+
+// two floats -> P packed bf16 pairs (low half = x0).  A non-finite piece ends the split (later pieces 0), so inf / NaN
+// propagate through the x_0 product alone, as through an exact product.
+template <int P>
+__device__ __forceinline__ void split2_bf16(float x0, float x1, unsigned (&out)[P]) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          v[r] = apply_act(acc[i][j][r] * d.alpha + bv[r], d.act, d.act_eps, (d.act_nvalid < 0 ? m < -d.act_nvalid : nb + r < d.act_nvalid));
-        if (d.residual) {
-          const float4 rr = *(const float4*)(d.residual + o);
-          v[0] += rr.x; v[1] += rr.y; v[2] += rr.z; v[3] += rr.w;
-        }
-        if (d.c_dtype == RF_F32) {
-          *(float4*)((float*)d.C + o) = make_float4(v[0], v[1], v[2], v[3]);
+  for (int s = 0; s < P; ++s) {
+    const rf_f32x2 v = {x0, x1};
+    const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(v, rf_bf16x2));
+    out[s] = u;
+    const float h0 = __uint_as_float(u << 16), h1 = __uint_as_float(u & 0xffff0000u);
+    x0 = (__float_as_uint(h0) & 0x7f800000u) == 0x7f800000u ? 0.f : x0 - h0;
+    x1 = (__float_as_uint(h1) & 0x7f800000u) == 0x7f800000u ? 0.f : x1 - h1;
+  }
+}
+
+__device__ __forceinline__ float b_elem_f32(const rf_gemm_desc& d, const float* Bb, int n, int k) {
+  if (n >= d.N || k >= d.K) return 0.f;
+  return Bb[split_off(n, d.b_rc, d.b_ro, d.b_ri) + (int64_t)(k / d.kc) * d.b_ko + (k % d.kc)];
+}
+
+// offset of A element (m, k) for the 16-byte staging path (m < M, k < K); false = zero (conv padding tap)
+__device__ __forceinline__ bool a_off_f32(const rf_gemm_desc& d, int m, int k, int64_t& off) {
+  if (d.a_mode == RF_AMODE_CONV3X3) {
+    const int tap = k / d.conv_c, c = k % d.conv_c;
+    const int hw = d.conv_h * d.conv_w;
+    const int pix = m % hw;
+    const int ii = pix / d.conv_w + (tap / 3 - 1) * d.conv_dil, jj = pix % d.conv_w + (tap % 3 - 1) * d.conv_dil;
+    if (ii < 0 || ii >= d.conv_h || jj < 0 || jj >= d.conv_w) return false;
+    off = ((int64_t)(m / hw) * hw + (int64_t)ii * d.conv_w + jj) * d.conv_c + c;
+    return true;
+  }
+  off = split_off(m, d.a_rc, d.a_ro, d.a_ri) + (int64_t)(k / d.kc) * d.a_ko + (k % d.kc);
+  return true;
+}
+
+// BM x BN x 32 tiles, 4 waves as 2 x 2, P split pieces per operand.  Global fp32 -> registers (one K step ahead) -> split
+// -> LDS images of the P pieces in the bf16 kernel's fragment order (64-byte rows of 8-element chunks, swz<32> swizzle:
+// the ds_read_b128 of a fragment hits distinct bank slots) -> MFMA.  Chunks of 8 consecutive k are loaded as two float4
+// when f32_vec says every such chunk is contiguous and 16-byte aligned (bit 0: A, bit 1: B), element-wise otherwise.
+template <int BM, int BN, int P>
+__global__ __launch_bounds__(256, 2) void gemm_f32split_kernel(const GemmP p) {
+  constexpr int BK = 32, SPR = BK / 8;                   // 16-byte chunks (8 bf16) per LDS row
+  constexpr int TM = BM / 2, TN = BN / 2, WM = TM / 16, WN = TN / 16;
+  constexpr int A_CH = BM * SPR, B_CH = BN * SPR;        // chunks per tile
+  constexpr int A_PT = (A_CH + 255) / 256, B_PT = (B_CH + 255) / 256;
+  constexpr int A_IMG = BM * BK * 2, B_IMG = BN * BK * 2;  // bytes of one bf16 piece image
+  __shared__ __attribute__((aligned(16))) char smem[P * (A_IMG + B_IMG)];
+  char* const a_lds = smem;
+  char* const b_lds = smem + P * A_IMG;
+  const rf_gemm_desc& d = p.d;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int lid = blockIdx.x;
+  const int tn = lid % p.tilesN;
+  const int t2 = lid / p.tilesN;
+  const int tm = t2 % p.tilesM;
+  const int z = t2 / p.tilesM;
+  int z0, z1, z2;
+  batch_decode(d, z, z0, z1, z2);
+  const int m0 = tm * BM, n0 = tn * BN;
+  const float* Ab = (const float*)d.A + (d.a_mode == RF_AMODE_CONV3X3 ? 0 : z0 * d.a_bs[0] + z1 * d.a_bs[1] + z2 * d.a_bs[2]);
+  const float* Bb = (const float*)d.B + z0 * d.b_bs[0] + z1 * d.b_bs[1] + z2 * d.b_bs[2];
+  const bool a_vec = p.f32_vec & 1, b_vec = p.f32_vec & 2;
+
+  float ra[A_PT][8], rb[B_PT][8];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int t = 0; t < A_PT; ++t) {
+      const int c = tid + 256 * t;
+      const int m = m0 + c / SPR, k = k0 + (c % SPR) * 8;
+      if (A_CH % 256 == 0 || c < A_CH) {
+        if (a_vec) {
+          float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+          int64_t off;
+          if (m < d.M && k < d.K && a_off_f32(d, m, k, off)) {  // K % 8 == 0: the whole chunk is in range
+            v0 = *(const float4*)(Ab + off);
+            v1 = *(const float4*)(Ab + off + 4);
+          }
+          ra[t][0] = v0.x; ra[t][1] = v0.y; ra[t][2] = v0.z; ra[t][3] = v0.w;
+          ra[t][4] = v1.x; ra[t][5] = v1.y; ra[t][6] = v1.z; ra[t][7] = v1.w;
         } else {
-          uint2 w;
-          w.x = rf_pack2_h16(v[0], v[1]);
-          w.y = rf_pack2_h16(v[2], v[3]);
-          *(uint2*)((h16_t*)d.C + o) = w;
-        }
-        continue;
-      }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wc * 32 + j * 16 + 4 * fq + r;
-        if (n >= d.N) continue;
-        float x = acc[i][j][r] * d.alpha;
-        if (d.bias_mode == RF_BIAS_COL) x += d.bias[n];
-        if (d.bias_mode == RF_BIAS_ROW) x += d.bias[m];
-        x = apply_act(x, d.act, d.act_eps, (d.act_nvalid < 0 ? m < -d.act_nvalid : n < d.act_nvalid));
-        const int64_t o = c_row + split_off(n, d.c_cc, d.c_co, 1);
-        if (d.residual) x += d.residual[o];
-        st(d.C, d.c_dtype, o, x);
+          for (int e = 0; e < 8; ++e) ra[t][e] = a_elem_f32(d, Ab, m, k + e);
+        }
       }
     }
+#pragma unroll
+    for (int t = 0; t < B_PT; ++t) {
+      const int c = tid + 256 * t;
+      const int n = n0 + c / SPR, k = k0 + (c % SPR) * 8;
+      if (B_CH % 256 == 0 || c < B_CH) {
+        if (b_vec) {
+          float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
+          if (n < d.N && k < d.K) {
+            const float* s = Bb + split_off(n, d.b_rc, d.b_ro, d.b_ri) + (int64_t)(k / d.kc) * d.b_ko + (k % d.kc);
+            v0 = *(const float4*)s;
+            v1 = *(const float4*)(s + 4);
+          }
+          rb[t][0] = v0.x; rb[t][1] = v0.y; rb[t][2] = v0.z; rb[t][3] = v0.w;
+          rb[t][4] = v1.x; rb[t][5] = v1.y; rb[t][6] = v1.z; rb[t][7] = v1.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) rb[t][e] = b_elem_f32(d, Bb, n, k + e);
+        }
+      }
+    }
+  };
+  // split a staged chunk and write its P pieces: chunk c of the tile = row c / SPR, k chunk c % SPR (swizzled slot)
+  auto put = [&](char* img, int img_bytes, int c, const float (&x)[8]) {
+    unsigned w[4][P];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) split2_bf16<P>(x[2 * h], x[2 * h + 1], w[h]);
+    const int row = c / SPR;
+    const int slot = row * SPR + ((c % SPR) ^ swz<BK>(row));
+#pragma unroll
+    for (int s = 0; s < P; ++s) *(uint4*)(img + s * img_bytes + slot * 16) = make_uint4(w[0][s], w[1][s], w[2][s], w[3][s]);
+  };
+
+  f32x4 acc[WM][WN];
+#pragma unroll
+  for (int i = 0; i < WM; ++i)
+#pragma unroll
+    for (int j = 0; j < WN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int nk = (d.K + BK - 1) / BK;
+  load(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt > 0) __syncthreads();  // every wave is done reading the previous step's images
+#pragma unroll
+    for (int t = 0; t < A_PT; ++t)
+      if (A_CH % 256 == 0 || tid + 256 * t < A_CH) put(a_lds, A_IMG, tid + 256 * t, ra[t]);
+#pragma unroll
+    for (int t = 0; t < B_PT; ++t)
+      if (B_CH % 256 == 0 || tid + 256 * t < B_CH) put(b_lds, B_IMG, tid + 256 * t, rb[t]);
+    __syncthreads();
+    if (kt + 1 < nk) load((kt + 1) * BK);  // next step's global loads are in flight under this step's MFMAs
+    h16x8 af[P][WM], bfr[P][WN];
+#pragma unroll
+    for (int s = 0; s < P; ++s) {
+#pragma unroll
+      for (int i = 0; i < WM; ++i) {
+        const int row = wm * TM + i * 16 + fr;
+        af[s][i] = *(const h16x8*)(a_lds + s * A_IMG + (row * SPR + (fq ^ swz<BK>(row))) * 16);
+      }
+#pragma unroll
+      for (int j = 0; j < WN; ++j) {
+        const int row = wn * TN + j * 16 + fr;
+        bfr[s][j] = *(const h16x8*)(b_lds + s * B_IMG + (row * SPR + (fq ^ swz<BK>(row))) * 16);
+      }
+    }
+    // pieces (sa, sb) with sa + sb = o, o from P - 1 down to 0: the small cross terms enter the accumulator before the
+    // leading product
+#pragma unroll
+    for (int o = P - 1; o >= 0; --o)
+#pragma unroll
+      for (int sa = o; sa >= 0; --sa)
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+          for (int j = 0; j < WN; ++j)
+            // weights as MFMA-A, activations as MFMA-B: D[n_local][m_local], as in the other two kernels
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[o - sa][j], af[sa][i], acc[i][j], 0, 0, 0);
+  }
+  const int64_t c_z = z0 * d.c_bs[0] + z1 * d.c_bs[1] + z2 * d.c_bs[2];
+#pragma unroll
+  for (int i = 0; i < WM; ++i) {
+    const int m = m0 + wm * TM + i * 16 + fr;
+    if (m >= d.M) continue;
+    const int64_t c_row = c_z + split_off(m, d.c_rc, d.c_ro, d.c_ri);
+#pragma unroll
+    for (int j = 0; j < WN; ++j) f32_epilogue4(p, c_row, m, n0 + wn * TN + j * 16 + 4 * fq, acc[i][j]);
   }
 }
 
@@ -698,7 +887,8 @@ extern "C" int rf_debug_gemm_fast_stamps(void* buf) {
 
 // Which kernel family the calling thread's last rf_gemm chose (bench.py attributes launch times with it instead of
 // re-deriving the dispatch rules): 0 exact-fp32, 1 generic bf16 tile, 2 conv3x3 implicit GEMM, 3 persistent tile kernel
-// (gemm_fast.hip), 4 register-resident-weights kernel (gemm_wreg.hip); -1 = nothing launched.
+// (gemm_fast.hip), 4 register-resident-weights kernel (gemm_wreg.hip), 5 split-bf16 fp32 kernel (RF_F32X3); -1 = nothing
+// launched.
 static thread_local int g_last_family = -1;
 extern "C" int rf_gemm_last_family(void) { return g_last_family; }
 
@@ -776,6 +966,41 @@ extern "C" int rf_gemm(const rf_gemm_desc* dd, void* stream) {
     if (nblk > 0x7fffffffLL) return RF_EINVAL;
     hipLaunchKernelGGL(gemm_f32_kernel, dim3((unsigned)nblk), dim3(256), 0, s, p);
     g_last_family = 0;
+    return rf_launch_status();
+  }
+  if (d.ab_dtype == RF_F32X3) {
+    // split-bf16 fp32 ("high"): takes and rejects exactly the descriptors of the exact fp32 kernel
+    if (d.act == RF_ACT_BLOCK_LN32 || want_ln) return RF_EINVAL;
+    // 16-byte staging: every 8-element k chunk (k % 8 == 0) lies in one K chunk / conv tap, contiguous and 16-byte aligned
+    auto al4 = [](int64_t v) { return (v % 4) == 0; };
+    p.f32_vec = 0;
+    if (d.K % 8 == 0 && d.kc % 8 == 0) {
+      if (d.a_mode == RF_AMODE_CONV3X3 ? ((uintptr_t)d.A % 16) == 0
+                                       : (((uintptr_t)d.A % 16) == 0 && al4(d.a_ri) && (d.a_rc <= 0 || al4(d.a_ro)) &&
+                                          al4(d.a_ko) && al4(d.a_bs[0]) && al4(d.a_bs[1]) && al4(d.a_bs[2])))
+        p.f32_vec |= 1;
+      if (((uintptr_t)d.B % 16) == 0 && al4(d.b_ri) && (d.b_rc <= 0 || al4(d.b_ro)) && al4(d.b_ko) && al4(d.b_bs[0]) &&
+          al4(d.b_bs[1]) && al4(d.b_bs[2]))
+        p.f32_vec |= 2;
+    }
+    // tile: the bf16 kernel's N rule; 128 rows when that does not pad M and still fills the chip
+    const int bn = pick_bn(d.N);
+    const int64_t tiles128 = (int64_t)((d.M + 127) / 128) * ((d.N + bn - 1) / bn) * batch;
+    const int bm = d.M > 64 && ((d.M + 127) / 128) * 128 <= ((d.M + 63) / 64) * 64 + 32 && tiles128 >= rf_num_cus() ? 128 : 64;
+    p.tilesM = (d.M + bm - 1) / bm;
+    p.tilesN = (d.N + bn - 1) / bn;
+    const int64_t nblk = (int64_t)p.tilesM * p.tilesN * batch;
+    if (nblk > 0x7fffffffLL) return RF_EINVAL;
+#define RF_SPLIT_CASE(BM_, BN_) \
+  if (bm == BM_ && bn == BN_) hipLaunchKernelGGL((gemm_f32split_kernel<BM_, BN_, 2>), dim3((unsigned)nblk), dim3(256), 0, s, p);
+    RF_SPLIT_CASE(128, 128)
+    RF_SPLIT_CASE(128, 96)
+    RF_SPLIT_CASE(128, 64)
+    RF_SPLIT_CASE(64, 128)
+    RF_SPLIT_CASE(64, 96)
+    RF_SPLIT_CASE(64, 64)
+#undef RF_SPLIT_CASE
+    g_last_family = 5;
     return rf_launch_status();
   }
   if (d.ab_dtype != RF_H16) return RF_EINVAL;

@@ -40,12 +40,14 @@ class GraphedForward:
                                    min(m.msa_emb.pos_enc.max_len, m.pair_emb.pos_enc.max_len))
 
     def recapture(self, monotonic=None):
-        """(Re)record the graph: after load_state_dict / set_compute_dtype, or for the other residue-index branch."""
+        """(Re)record the graph: after load_state_dict / set_compute_dtype / set_float32_matmul_precision, or for the other
+        residue-index branch."""
         if self.model.training:
             raise L.RfmiError("GraphedForward records the inference forward: the dropout masks of a training-mode forward are chosen on "
                               "the host per call (model.manual_seed / counters), a replay would repeat one set of masks; call model.eval()")
         with torch.cuda.device(self.device), torch.no_grad():
             self._dtype = M.T()   # the graph holds the kernels of the library active now
+            self._precision = M.get_float32_matmul_precision()   # ... and, in float32 mode, the exact or the split fp32 GEMMs
             # the recorded kernels read the prepared 16-bit weight copies by raw pointer: bring the copies in line with the live
             # parameters first (what the public model(...) call does), and remember which parameters the graph belongs to
             fp = M.weights_fingerprint(self.model)
@@ -80,6 +82,9 @@ class GraphedForward:
             raise L.RfmiError("GraphedForward replays the inference forward; the model is in training mode (model.eval() first)")
         if M.T() != self._dtype:
             raise L.RfmiError(f"GraphedForward was captured in {self._dtype} mode; set_compute_dtype changed it to {M.T()}: call recapture()")
+        if M.get_float32_matmul_precision() != self._precision:
+            raise L.RfmiError(f"GraphedForward was captured under float32 matmul precision {self._precision!r}; "
+                              f"set_float32_matmul_precision changed it to {M.get_float32_matmul_precision()!r}: call recapture()")
         with torch.cuda.device(self.device):
             msa, seq, aa_idx = msa.contiguous(), seq.contiguous(), aa_idx.contiguous()
             mono = self._validate(msa, seq, aa_idx)   # IndexError before anything is overwritten

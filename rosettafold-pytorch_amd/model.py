@@ -33,6 +33,7 @@ VT_ROWS = 80   # 64 value rows + the ones row (k' sums) padded to a multiple of 
 
 class _Runtime:
     dtype = torch.bfloat16
+    f32_precision = "highest"  # set_float32_matmul_precision: "high" = split-bf16 GEMMs in the float32 mode
     # training-mode dropout: masks are Philox4x32-10(train_seed, counter); every dropout call of a forward
     # takes the next ceil(n / 4) counters, so manual_seed(s) in front of a forward reproduces it bit for bit (csrc/ops.hip)
     train_seed = 0
@@ -91,12 +92,33 @@ def set_compute_dtype(dtype):
       torch.bfloat16  v_mfma_f32_16x16x32_bf16, librfmi.so (default: the dtype BASELINE.json quotes the metric on);
       torch.float16   v_mfma_f32_16x16x32_f16, librfmi_f16.so: same rate and bytes, 8x smaller operand rounding
                       (11 significand bits), fp16 range -- the mode that carries the whole-model parity claim at speed;
-      torch.float32   exact fp32 tiles (v_mfma_f32_16x16x4_f32, 1/16 of the rate): the strict oracle-parity mode.
+      torch.float32   fp32 operands.  With set_float32_matmul_precision("highest") (the default) exact fp32 tiles
+                      (v_mfma_f32_16x16x4_f32, 1/16 of the rate): the strict oracle-parity mode.  With "high" the rf_gemm
+                      contractions split each fp32 operand into two bf16 pieces and take three bf16 MFMAs per product
+                      (RF_F32X3, about 2^-16 relative operand error); the structure track stays exact.
     Kernel-ready weight copies are cached per dtype, so switching back and forth costs nothing after the first forward."""
     if dtype not in (torch.bfloat16, torch.float16, torch.float32):
         raise TypeError("compute dtype must be bfloat16, float16 or float32")
     RT.dtype = dtype
     L.select_h16(L.RF_F16 if dtype == torch.float16 else L.RF_BF16)
+    ops.set_split_f32(dtype == torch.float32 and RT.f32_precision == "high")
+
+
+def set_float32_matmul_precision(precision):
+    """Precision of the fp32 GEMMs of the float32 compute mode, named after torch.set_float32_matmul_precision:
+      "highest"  exact fp32 tiles (default);
+      "high"     split bf16: x = hi + lo, hi . hi + hi . lo + lo . hi in fp32 accumulators (RF_F32X3, include/rfmi.h).
+    Stored in every mode, in effect only under set_compute_dtype(torch.float32): the few fp32 GEMMs of the 16-bit modes and
+    the structure track (fp32 end to end by design) stay exact.  A GraphedForward captured under the other precision
+    raises on replay (recapture())."""
+    if precision not in ("highest", "high"):
+        raise ValueError(f'float32 matmul precision must be "highest" or "high", got {precision!r}')
+    RT.f32_precision = precision
+    ops.set_split_f32(RT.dtype == torch.float32 and precision == "high")
+
+
+def get_float32_matmul_precision():
+    return RT.f32_precision
 
 
 def T():

@@ -41,6 +41,22 @@ def dcode(dtype):
     return code
 
 
+# set by model.set_compute_dtype / model.set_float32_matmul_precision: True in float32 mode with the "high" precision
+_SPLIT_F32 = False
+
+
+def set_split_f32(on):
+    global _SPLIT_F32
+    _SPLIT_F32 = bool(on)
+
+
+def gemm_code(dtype, exact=False):
+    """rf_gemm_desc.ab_dtype of an A/B dtype: float32 operands take the split-bf16 kernel (RF_F32X3) while the "high" float32
+    matmul precision is in effect (model.set_float32_matmul_precision), unless the call pins the exact fp32 kernel."""
+    code = dcode(dtype)
+    return L.RF_F32X3 if code == L.RF_F32 and _SPLIT_F32 and not exact else code
+
+
 def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -80,17 +96,18 @@ def gemm(A, B, Cout, M, N, K, *, batch=(1, 1, 1), a_off=0, b_off=0, c_off=0,
          b_bs=(0, 0, 0), b_row=(0, 0, None), b_ko=0, kc=0,
          c_bs=(0, 0, 0), c_row=(0, 0, None), c_col=(0, 0),
          bias=None, bias_mode=None, act=L.ACT_NONE, act_nvalid=0, act_eps=0.0, alpha=1.0,
-         residual=None, res_off=None, conv=None, tile_cfg=0, ln=None, block_ln=None, rs=None):
+         residual=None, res_off=None, conv=None, tile_cfg=0, ln=None, block_ln=None, rs=None, exact=False):
     """C = epilogue(alpha * A @ B^T) with the strided/batched/chunked addressing of rf_gemm_desc.
     *_row = (rc, ro, ri): offset(m) = (m // rc)*ro + (m % rc)*ri, rc=0 -> m*ri.  ri=None -> K (A,B) / N (C).
-    c_col = (cc, co).  Offsets are in elements.  conv = (n, h, w, c, dilation) selects implicit 3x3 im2col."""
+    c_col = (cc, co).  Offsets are in elements.  conv = (n, h, w, c, dilation) selects implicit 3x3 im2col.
+    exact=True keeps fp32 operands on the exact fp32 kernel whatever the float32 matmul precision (gemm_code)."""
     _need_cuda(A, B, Cout, bias, residual)
     if A.dtype != B.dtype:
         raise TypeError("A and B dtypes differ")
     d = GemmDesc()
     d.M, d.N, d.K = int(M), int(N), int(K)
     d.nb0, d.nb1, d.nb2 = [int(x) for x in batch]
-    d.ab_dtype, d.c_dtype = dcode(A.dtype), dcode(Cout.dtype)
+    d.ab_dtype, d.c_dtype = gemm_code(A.dtype, exact), dcode(Cout.dtype)
     d.kc = int(kc)
     d.a_rc, d.a_ro, d.a_ri = int(a_row[0]), int(a_row[1]), int(K if a_row[2] is None else a_row[2])
     d.b_rc, d.b_ro, d.b_ri = int(b_row[0]), int(b_row[1]), int(K if b_row[2] is None else b_row[2])
@@ -144,7 +161,8 @@ def gemm_takes_row_scale(M, N, K):
     return (not _NO_WREG) and K in (288, 384) and M % 64 == 0 and M >= 16384 and N % 128 == 0 and N >= 256  # (+ a split-C output)
 
 
-def linear(x, w, bias=None, *, out=None, out_dtype=None, act=L.ACT_NONE, residual=None, alpha=1.0, tile_cfg=0, ln=None):
+def linear(x, w, bias=None, *, out=None, out_dtype=None, act=L.ACT_NONE, residual=None, alpha=1.0, tile_cfg=0, ln=None,
+           exact=False):
     """out[..., N] = act(x[..., K] @ w[N, K]^T + bias) (+ residual).  x contiguous, w [N, Kw>=K] contiguous."""
     K = x.shape[-1]
     Mrows = x.numel() // K
@@ -153,7 +171,7 @@ def linear(x, w, bias=None, *, out=None, out_dtype=None, act=L.ACT_NONE, residua
         raise ValueError(f"linear: K mismatch {w.shape} vs {x.shape}")
     if out is None:
         out = torch.empty(*x.shape[:-1], N, device=x.device, dtype=out_dtype or x.dtype)
-    gemm(x, w, out, Mrows, N, K, bias=bias, act=act, residual=residual, alpha=alpha, tile_cfg=tile_cfg, ln=ln)
+    gemm(x, w, out, Mrows, N, K, bias=bias, act=act, residual=residual, alpha=alpha, tile_cfg=tile_cfg, ln=ln, exact=exact)
     return out
 
 

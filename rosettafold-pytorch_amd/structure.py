@@ -82,7 +82,7 @@ class G1x1SE3(nn.Module):
             mo = W.shape[0]
             y = torch.empty(V, mo, nc, device=x.device, dtype=F32)
             ops.gemm(x, W, y, V * nc, mo, mi, kc=1, a_row=(nc, mi * nc, 1), a_ko=nc, b_row=(0, 0, mi), b_ko=1,
-                     c_row=(nc, mo * nc, 1), c_col=(1, nc))
+                     c_row=(nc, mo * nc, 1), c_col=(1, nc), exact=True)
             out[d] = y
         return out
 
@@ -118,7 +118,7 @@ class GAttentiveSelfInt(nn.Module):
             mi, mo = self.f_in[d], self.f_out[d]
             s = ops.se3_gram(v, d)
             t = ops.layernorm(s, _f(net[0].weight), _f(net[0].bias), eps=net[0].eps, out_dtype=F32, act=L.ACT_LEAKY)
-            a = ops.linear(t, net[2].weight.detach(), _f(net[2].bias), out_dtype=F32)
+            a = ops.linear(t, net[2].weight.detach(), _f(net[2].bias), out_dtype=F32, exact=True)
             out[d] = ops.se3_attn_apply(a, v, mo, d)
         return out
 
@@ -215,13 +215,13 @@ class GSE3Res(nn.Module):
         if not all(fused.values()):
             # radial MLPs as launches (shapes without a fused instance, or RF_SE3_UNFUSED=1): layer 1 for all G nets in one GEMM,
             # grouped LayerNorm + ReLU, per-net 32x32 layer, grouped LayerNorm + ReLU; the output layer follows per net below
-            h1 = ops.linear(feat, pk["w1"], pk["b1"], out_dtype=F32)  # [cap, G*32]
+            h1 = ops.linear(feat, pk["w1"], pk["b1"], out_dtype=F32, exact=True)  # [cap, G*32]
             h1 = ops.layernorm(h1, pk["g1"], pk["e1"], eps=eps, out_dtype=F32, rows=cap * G, D=32, groups=G, act=L.ACT_RELU)
             h2 = torch.empty_like(h1)
             for gi, n in enumerate(nets):
                 lin = n[3].rp.net[3]
                 ops.gemm(h1, lin.weight.detach(), h2, cap, 32, 32, a_off=gi * 32, a_row=(0, 0, G * 32), c_off=gi * 32,
-                         c_row=(0, 0, G * 32), bias=_f(lin.bias))
+                         c_row=(0, 0, G * 32), bias=_f(lin.bias), exact=True)
             h2 = ops.layernorm(h2, pk["g2"], pk["e2"], eps=eps, out_dtype=F32, rows=cap * G, D=32, groups=G, act=L.ACT_RELU)
         msg = {}
         for which, do, mo in todo:
@@ -241,7 +241,7 @@ class GSE3Res(nn.Module):
                 nout = lin.weight.shape[0]
                 r = torch.empty(cap, nout, device=feat.device, dtype=F32)
                 ops.gemm(h2, lin.weight.detach(), r, cap, nout, 32, a_off=slot[(which, di, do)] * 32, a_row=(0, 0, G * 32),
-                         bias=_f(lin.bias))
+                         bias=_f(lin.bias), exact=True)
                 R[di] = r
             msg[(which, do)] = ops.se3_message(R.get(0), R.get(1), g["basis"], h0, h1f, g["src"], g["count"], mo, do, mi0, mi1, cap)
         q = self.GMAB["q"].run(h)
@@ -336,16 +336,17 @@ class CoordUpdateWithMsaAndPair(RFModule):
 
     def run(self, xyz, msa, pair, aa_idx, seq_onehot, monotonic=True):
         B, Lr = xyz.shape[:2]
-        # the structure track is fp32 end to end (se3_modules.py:164): its input projections use the exact fp32 GEMM
+        # the structure track is fp32 end to end (se3_modules.py:164): its input projections use the exact fp32 GEMM, also
+        # under the "high" float32 matmul precision (exact=True)
         nin, Kp = _node_input(self, msa, seq_onehot, out_dtype=F32)
         wn = self.cached("wn32", lambda: torch.cat([self.node_embed[0].weight.detach().float(),
                                                     torch.zeros(self.node_embed[0].weight.shape[0],
                                                                 Kp - self.node_embed[0].weight.shape[1],
                                                                 device=msa.device)], 1).contiguous())
-        node = ops.linear(nin, wn, _f(self.node_embed[0].bias), out_dtype=F32, act=L.ACT_ELU)
+        node = ops.linear(nin, wn, _f(self.node_embed[0].bias), out_dtype=F32, act=L.ACT_ELU, exact=True)
         node = ln(self.node_embed[2], node, out_dtype=F32)
         e = ops.linear(ln(self.ln_pair, pair, out_dtype=F32), self.edge_embed[0].weight.detach().float(),
-                       _f(self.edge_embed[0].bias), out_dtype=F32, act=L.ACT_ELU)
+                       _f(self.edge_embed[0].bias), out_dtype=F32, act=L.ACT_ELU, exact=True)
         edge = ln(self.edge_embed[2], e, out_dtype=F32)  # [B,L,L,d_edge] fp32
         xyz = xyz.contiguous()
         g = build_graph(xyz, edge, aa_idx.contiguous(), self.n_neighbors, monotonic=monotonic)
@@ -392,20 +393,20 @@ class MsaUpdateWithPairAndCoord(RFModule):
         st = ln(self.ln_state, state.contiguous(), out_dtype=F32)
         m32 = ln(self.ln_msa, msa, out_dtype=F32)
         m_t = ops.cast(m32, T())
-        q = ops.linear(st, self.to_q.weight.detach(), _f(self.to_q.bias), out_dtype=F32)
+        q = ops.linear(st, self.to_q.weight.detach(), _f(self.to_q.bias), out_dtype=F32, exact=True)
         ops.axpby(q, self.scale, None, 0.0, q)
-        k = ops.linear(st, self.to_k.weight.detach(), _f(self.to_k.bias), out_dtype=F32)
+        k = ops.linear(st, self.to_k.weight.detach(), _f(self.to_k.bias), out_dtype=F32, exact=True)
         bins = self.cached("bins", lambda: torch.tensor(self.distance_bins, dtype=F32, device=dev))
         att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
         ops.dist_masked_attention(q, k, xyz.contiguous(), bins, att, B, Lr, H, dq)
         v_t = torch.empty(B, N, D, Lr, device=dev, dtype=T())
         ops.gemm(self.wt("v", self.to_v), m_t, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=_f(self.to_v.bias), bias_mode=L.BIAS_ROW)
+                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=_f(self.to_v.bias), bias_mode=L.BIAS_ROW, exact=False)
         out = torch.empty(B, N, Lr, D, device=dev, dtype=F32)
         ops.gemm(att, v_t, out, Lr, N * dv, Lr, batch=(B, H, 1),
                  a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
                  b_bs=(N * D * Lr, dv * Lr, 0), b_row=(dv, D * Lr, Lr),
-                 c_bs=(N * Lr * D, dv, 0), c_row=(0, 0, D), c_col=(dv, Lr * D))
+                 c_bs=(N * Lr * D, dv, 0), c_row=(0, 0, D), c_col=(dv, Lr * D), exact=False)
         o = ln(self.ln_out, out, out_dtype=F32)
         ops.axpby(m32, 1.0, o, 1.0, m32)
         self.to_out.fn[1].apply_residual(ln(self.to_out.fn[0], m32), m32)
@@ -517,7 +518,7 @@ class FinalBlock(TwoTrackBlock):
     def run3(self, msa, pair, xyz, seq_onehot, aa_idx, monotonic=True, row_group=None):
         pair = self.run(msa, pair, row_group)
         state, xyz = self.coord_update_with_msa_and_pair.run(xyz, msa, _whole_pair(pair, row_group), aa_idx, seq_onehot, monotonic)
-        plddt = ops.linear(state.contiguous(), self.plddt_head.weight.detach(), _f(self.plddt_head.bias), out_dtype=F32)
+        plddt = ops.linear(state.contiguous(), self.plddt_head.weight.detach(), _f(self.plddt_head.bias), out_dtype=F32, exact=True)
         return msa, pair, xyz, plddt[..., 0]
 
     def forward(self, msa, pair, xyz, seq_onehot, aa_idx):

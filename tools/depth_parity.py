@@ -6,6 +6,7 @@
                                                  # against the CPU oracle (oracle/rf_oracle.py), block by block
     python tools/depth_parity.py --oracle --full --modes fp32,bf16,fp16   # the benchmarked 8+5 depth against the oracle
     python tools/depth_parity.py --struct-lowp   # attribution: structure-track node input in the 16-bit type (round-2 policy)
+    python tools/depth_parity.py --modes fp32x3  # float32 mode with the split-bf16 ("high") GEMMs against the exact one
 
 Prints one JSON object (relative L2 of msa / pair / xyz after every block, logits / xyz / plddt at the end, distogram
 argmax agreement over all pairs and over the pairs with a clear top-2 margin in the reference).  tests/test_depth_gpu.py
@@ -25,7 +26,9 @@ import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 from rosettafold_pytorch_amd import model as M  # noqa: E402
 
-MODES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+MODES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16, "fp32x3": torch.float32}
+# fp32x3: float32 mode under set_float32_matmul_precision("high") (split-bf16 GEMMs); every other mode runs under "highest"
+PRECISION = {"fp32x3": "high"}
 
 
 def rel2(a, b):
@@ -121,12 +124,16 @@ def run(args):
     res = {"config": {"B": args.B, "N": args.N, "L": args.L, "blocks": f"{n2}+{n3}", "n_enc": 4, "struct_inputs_fp32": not args.struct_lowp,
                       "reference": "CPU oracle (oracle/rf_oracle.py)" if args.oracle else "exact-fp32 mode of the library"}}
     traces = {}
-    for name in (["fp32"] if "fp32" not in modes else []) + modes:
-        R.set_compute_dtype(MODES[name])
-        hip_trace(model, dmsa, dseq, daa)  # warm-up: weight copies of this mode
-        t0 = time.perf_counter()
-        traces[name] = hip_trace(model, dmsa, dseq, daa)
-        res.setdefault("ms_forward_with_snapshots", {})[name] = 1e3 * (time.perf_counter() - t0)
+    try:
+        for name in (["fp32"] if "fp32" not in modes else []) + modes:
+            R.set_compute_dtype(MODES[name])
+            R.set_float32_matmul_precision(PRECISION.get(name, "highest"))
+            hip_trace(model, dmsa, dseq, daa)  # warm-up: weight copies of this mode
+            t0 = time.perf_counter()
+            traces[name] = hip_trace(model, dmsa, dseq, daa)
+            res.setdefault("ms_forward_with_snapshots", {})[name] = 1e3 * (time.perf_counter() - t0)
+    finally:
+        R.set_float32_matmul_precision("highest")
     R.set_compute_dtype(torch.bfloat16)
     if args.oracle:
         torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
