@@ -462,6 +462,42 @@ int rf_center_ca(const float* xyz, float* y, int64_t nres, void* stream);
 /* Coordinate update (rf.py:816-819): xyz_out from xyz and displacement [B*L,3,3]. */
 int rf_coord_apply(const float* xyz, const float* disp, float* xyz_out, int64_t nres, void* stream);
 
+/* ---- backward pass of PredictionHead and its ResNets (csrc/backward.hip; resnet.py, rf.py:1130-1172) ----------------------
+ * Input gradients of the convolutions and Linears run on rf_gemm (a stride-1 "same" 3x3 convolution's input gradient is the
+ * same convolution with the kernel rotated 180 degrees and its in / out channels swapped); these are the other pieces.
+ * Every reduction goes through per-block partials in the caller's workspace, added in a fixed order: no atomics, bitwise
+ * reproducible run to run.  The float32 matmul precision ("high", RF_F32X3) does not apply here: RF_F32 is exact fp32.
+ *
+ * Weight gradient of a stride-1 "same" convolution on NHWC tensors, fp32 result:
+ *   dw[co][tap][ci] = alpha * sum_{b,p} dy[b,p,co] * x[b, p + delta(tap), ci]     (zero outside the picture)
+ *   dbias[co]       = alpha * sum_{b,p} dy[b,p,co]                                 (dbias may be NULL)
+ * dy [B,H,W,Co], x [B,H,W,Ci], both of `dtype`: the library's 16-bit type (MFMA, fp32 accumulation; Co % 8 == 0, Ci % 8 == 0,
+ * 16-byte aligned, else RF_EALIGN) or RF_F32 (exact fp32).  taps = 9: 3x3 kernel, dilation 1..8, tap = 3*(di+1)+(dj+1) (the
+ * k order of RF_AMODE_CONV3X3, so dw is the forward's [Co][9*Ci] weight layout); taps = 1: 1x1 convolution / Linear over
+ * B*H*W rows (dilation ignored).  Workspace (MANDATORY): rf_conv_wgrad_ws_bytes bytes (0 = unsupported arguments). */
+int64_t rf_conv_wgrad_ws_bytes(int dtype, int B, int H, int W, int Co, int Ci, int taps);
+int rf_conv_wgrad(const void* dy, const void* x, int dtype, float* dw, float* dbias, int B, int H, int W, int Co, int Ci, int taps,
+                  int dilation, float alpha, void* workspace, int64_t ws_bytes, void* stream);
+/* InstanceNorm2d(affine) backward on NHWC [B, HW, C] (statistics pass + apply pass), for y = gamma * xhat + beta with xhat from
+ * x (the saved input the forward normalised, fp32 or 16-bit) and `sums` (the forward's rf_instnorm_stats, eps as there):
+ *   ge = g * (act_out ? (act_out > 0 ? 1 : act_out + 1) : 1)        g fp32: gradient of the output; act_out: the saved output
+ *                                                                  of an ELU that followed the norm (NULL: none)
+ *   dx = gamma / sigma * (ge - mean ge - xhat * mean(ge xhat))      (dx of dx_dtype: fp32 or the 16-bit type)
+ *   dgamma[c] = sum_{b,p} ge xhat, dbeta[c] = sum_{b,p} ge           (either may be NULL)
+ *   ge_out = ge (fp32, may alias g; NULL: not written): the gradient of a residual added before the ELU
+ * Workspace (MANDATORY, 16-byte aligned): rf_instnorm_ws_bytes(B, HW, C) rounded up to 16, plus 16 * B * C bytes. */
+int rf_instnorm_bwd(const float* g, const void* act_out, int act_dtype, const void* x, int x_dtype, const void* sums,
+                    const float* gamma, float eps, void* dx, int dx_dtype, float* ge_out, float* dgamma, float* dbeta, int B,
+                    int64_t HW, int C, void* workspace, int64_t ws_bytes, void* stream);
+/* LayerNorm backward over rows of D <= 1024 (fp32 x, the forward's input; g fp32 gradient of the output; statistics recomputed
+ * in fp32 like rf_layernorm):  dx = rstd * (g gamma - mean(g gamma) - xhat * mean(g gamma xhat))  (dx_dtype fp32 / 16-bit);
+ * dgamma[c] = sum_rows g xhat, dbeta[c] = sum_rows g (either may be NULL).  Workspace: rf_layernorm_bwd_ws_bytes bytes. */
+int64_t rf_layernorm_bwd_ws_bytes(int64_t rows, int D);
+int rf_layernorm_bwd(const float* x, const float* g, const float* gamma, float eps, void* dx, int dx_dtype, float* dgamma,
+                     float* dbeta, int64_t rows, int D, void* workspace, int64_t ws_bytes, void* stream);
+/* out[0] = max_e |x[e]| over n fp32 elements (the power-of-two gradient scale of the fp16 build); workspace >= 4096 bytes. */
+int rf_absmax(const float* x, int64_t n, float* out, void* workspace, int64_t ws_bytes, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

@@ -101,6 +101,12 @@ PROTOTYPES = {
     "rf_onehot": [vp, vp, i32, i64, i32, i32, i64, vp],
     "rf_seqsep_feature": [vp, vp, i32, i64, i32, i32, i32, vp],
     "rf_add_pos_enc": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "rf_conv_wgrad_ws_bytes": [i32, i32, i32, i32, i32, i32, i32],  # returns int64
+    "rf_conv_wgrad": [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp],
+    "rf_instnorm_bwd": [vp, vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, i32, i64, i32, vp, i64, vp],
+    "rf_layernorm_bwd_ws_bytes": [i64, i32],  # returns int64
+    "rf_layernorm_bwd": [vp, vp, vp, f32, vp, i32, vp, vp, i64, i32, vp, i64, vp],
+    "rf_absmax": [vp, i64, vp, vp, i64, vp],
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],
@@ -120,6 +126,8 @@ def _load(path):
         _fn.restype = C.c_int
     handle.rf_instnorm_ws_bytes.restype = C.c_int64
     handle.rf_channel_mean_ws_bytes.restype = C.c_int64
+    handle.rf_conv_wgrad_ws_bytes.restype = C.c_int64
+    handle.rf_layernorm_bwd_ws_bytes.restype = C.c_int64
     handle.rf_build_info.restype = C.c_char_p
     handle.rf_build_info.argtypes = []
     return handle

@@ -1,0 +1,523 @@
+// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172) on gfx950: the weight gradient of a
+// stride-1 "same" convolution (pixel contraction), InstanceNorm2d(affine) backward, LayerNorm backward, and the absolute
+// maximum the fp16 build scales its gradients by.  Input gradients of the convolutions / Linears run on rf_gemm (the forward's
+// implicit-GEMM engine with a repacked weight); these kernels are what the forward does not already have.
+// Every reduction writes per-block partials to a caller-owned workspace and adds them in a fixed order: no atomics, results
+// are bitwise reproducible run to run (like rf_instnorm_stats).
+#include "common.h"
+
+#define RF_CHECK_DT(dt) \
+  if ((dt) != RF_F32 && (dt) != RF_H16) return RF_EINVAL
+
+static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// ================================================================================================
+// rf_conv_wgrad:  dW[co][tap][ci] = alpha * sum_{b,p} dY[b,p,co] * X[b, p + delta(tap), ci]   (zero outside the picture)
+// ================================================================================================
+#define WG_KP 32           // pixels per k-step: the K of one v_mfma_f32_16x16x32
+#define WG_TARGET_WGS 1024 // workgroups to aim for: the pixel axis is split until (tiles x splits) reaches this
+#define WG32_PIX 64        // fp32 kernel: pixels per split unit
+
+// pixel split shared by the host-side size query and the launch: depends on the shape only (never on the device)
+static void wgrad_split(int dtype, int64_t P, int Co, int Ci, int taps, int* tiles, int* splits, int64_t* unit_per_split) {
+  int64_t units, t;
+  if (dtype == RF_F32) {
+    t = (int64_t)cdiv(Ci, 64) * cdiv(Co, 16);
+    units = cdiv(P, WG32_PIX);
+  } else {
+    const bool tall = taps == 9 && Co % 96 == 0;  // 96 x 32 tiles (3 waves) cover C = 288 without padding
+    t = tall ? (int64_t)(Co / 96) * cdiv(Ci, 32) : (int64_t)cdiv(Co, 64) * cdiv(Ci, 64);
+    units = cdiv(P, WG_KP);
+  }
+  int64_t s = (WG_TARGET_WGS + t - 1) / t;
+  if (s > units) s = units;
+  if (s < 1) s = 1;
+  const int64_t ups = (units + s - 1) / s;
+  s = (units + ups - 1) / ups;  // no empty split
+  *tiles = (int)t;
+  *splits = (int)s;
+  *unit_per_split = ups;
+}
+
+// 16-bit operands, fp32 accumulation.  Workgroup = WM x WN waves, each wave a 32(co) x 32(ci) tile for all TAPS taps.  Per
+// 32-pixel k-step the dY tile [32 px][CO_T] and the TAPS shifted X windows [32 px][CI_T] are staged into LDS with 16-byte
+// loads (zero outside the picture, past the split's last pixel and past Co / Ci: the tiles are padded, never masked) and read
+// as MFMA operands with ds_read_b64_tr_b16: both operands contract over the pixel (row) index of a [pixel][channel] image.
+template <int TAPS, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN) void conv_wgrad_h16_kernel(const h16_t* __restrict__ dy, const h16_t* __restrict__ x,
+                                                                   float* __restrict__ ws, float* __restrict__ bws, int H,
+                                                                   int W, int64_t P, int Co, int Ci, int dil, int ci_tiles,
+                                                                   int64_t ups) {
+  constexpr int NT = 64 * WM * WN;
+  constexpr int CO_T = 32 * WM, CI_T = 32 * WN;
+  constexpr int DP = CO_T + 8, XP = CI_T + 8;  // row pitches (elements): +16 bytes, rows stay 8-byte aligned
+  __shared__ __attribute__((aligned(16))) h16_t sdy[WG_KP * DP];
+  __shared__ __attribute__((aligned(16))) h16_t sx[TAPS * WG_KP * XP];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave % WM, wn = wave / WM;
+  const int co0 = (blockIdx.x / ci_tiles) * CO_T, ci0 = (blockIdx.x % ci_tiles) * CI_T;
+  const int split = blockIdx.y;
+  const int64_t p_begin = (int64_t)split * ups * WG_KP;
+  int64_t p_end = p_begin + ups * WG_KP;
+  if (p_end > P) p_end = P;
+  const int64_t HW = (int64_t)H * W;
+  const bool do_bias = bws != nullptr && ci0 == 0;
+
+  f32x4 acc[TAPS][2][2];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[t][a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float bsum = 0.f;  // thread tid < CO_T: bias partial of channel co0 + tid
+
+  // ds_read_b64_tr_b16 addressing (cdna_hip_programming T10): lane 4q+p of a 16-lane group g supplies row 8g + 4h + q,
+  // columns 4p..4p+3 of the 16-column block; it receives column (lane & 15) of those 4 rows, i.e. k = 8g + 4h + 0..3
+  const int g = lane >> 4, q = (lane & 15) >> 2, pcol = (lane & 3) * 4;
+
+  for (int64_t pc = p_begin; pc < p_end; pc += WG_KP) {
+    // ---- stage dY[pc .. pc+31][co0 .. co0+CO_T) ----
+    for (int v = tid; v < WG_KP * (CO_T / 8); v += NT) {
+      const int px = v / (CO_T / 8), cv = (v % (CO_T / 8)) * 8;
+      const int64_t p = pc + px;
+      h16x8 val = (h16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      if (p < p_end && co0 + cv < Co) val = *(const h16x8*)(dy + p * Co + co0 + cv);
+      *(h16x8*)(sdy + px * DP + cv) = val;
+    }
+    // ---- stage the TAPS shifted windows of X ----
+    for (int v = tid; v < TAPS * WG_KP * (CI_T / 8); v += NT) {
+      const int t = v / (WG_KP * (CI_T / 8));
+      const int r = v % (WG_KP * (CI_T / 8));
+      const int px = r / (CI_T / 8), cv = (r % (CI_T / 8)) * 8;
+      const int64_t p = pc + px;
+      h16x8 val = (h16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      if (p < p_end && ci0 + cv < Ci) {
+        const int64_t bb = p / HW, rr = p % HW;
+        const int i = (int)(rr / W) + (TAPS == 9 ? (t / 3 - 1) * dil : 0);
+        const int j = (int)(rr % W) + (TAPS == 9 ? (t % 3 - 1) * dil : 0);
+        if (i >= 0 && i < H && j >= 0 && j < W) val = *(const h16x8*)(x + ((bb * H + i) * W + j) * Ci + ci0 + cv);
+      }
+      *(h16x8*)(sx + (t * WG_KP + px) * XP + cv) = val;
+    }
+    __syncthreads();
+    if (do_bias && tid < CO_T) {
+#pragma unroll 8
+      for (int px = 0; px < WG_KP; ++px) bsum += h2f(sdy[px * DP + tid]);
+    }
+    // ---- MFMA: every lane of every wave takes part (EXEC all ones for the transposed reads) ----
+    h16x8 af[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int col = wm * 32 + a * 16 + pcol;
+      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sdy + (8 * g + q) * DP + col));
+      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(sdy + (8 * g + 4 + q) * DP + col));
+      af[a] = (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t) {
+      h16x8 bf[2];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int col = wn * 32 + b * 16 + pcol;
+        const h16_t* base = sx + t * WG_KP * XP;
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + (8 * g + q) * XP + col));
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(base + (8 * g + 4 + q) * XP + col));
+        bf[b] = (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      }
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[t][a][b] = rf_mfma16(af[a], bf[b], acc[t][a][b], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  // ---- partials: ws[split][co][tap][ci]; D layout of 16x16: col = lane & 15 (ci), row = 4 (lane >> 4) + r (co) ----
+  float* wsp = ws + (int64_t)split * Co * TAPS * Ci;
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int ci = ci0 + wn * 32 + b * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = co0 + wm * 32 + a * 16 + 4 * (lane >> 4) + r;
+          if (co < Co && ci < Ci) wsp[((int64_t)co * TAPS + t) * Ci + ci] = acc[t][a][b][r];
+        }
+      }
+  if (do_bias && tid < CO_T && co0 + tid < Co) bws[(int64_t)split * Co + co0 + tid] = bsum;
+}
+
+// exact fp32: thread (ci = ci0 + tid % 64, co = co0 + 4 (tid / 64) + 0..3) accumulates all taps over its split's pixels
+template <int TAPS>
+__global__ __launch_bounds__(256) void conv_wgrad_f32_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                              float* __restrict__ ws, float* __restrict__ bws, int H, int W,
+                                                              int64_t P, int Co, int Ci, int dil, int64_t ups) {
+  const int ci = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int co_b = blockIdx.y * 16 + (threadIdx.x >> 6) * 4;
+  const int split = blockIdx.z;
+  const int64_t p_begin = (int64_t)split * ups * WG32_PIX;
+  int64_t p_end = p_begin + ups * WG32_PIX;
+  if (p_end > P) p_end = P;
+  const int64_t HW = (int64_t)H * W;
+  float acc[TAPS][4], bs[4];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[t][u] = 0.f;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) bs[u] = 0.f;
+  const bool ci_ok = ci < Ci;
+  for (int64_t p = p_begin; p < p_end; ++p) {
+    float d[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) d[u] = co_b + u < Co ? dy[p * Co + co_b + u] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) bs[u] += d[u];
+    const int64_t bb = p / HW, rr = p % HW;
+    const int i0 = (int)(rr / W), j0 = (int)(rr % W);
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t) {
+      const int i = i0 + (TAPS == 9 ? (t / 3 - 1) * dil : 0), j = j0 + (TAPS == 9 ? (t % 3 - 1) * dil : 0);
+      const float xv = ci_ok && i >= 0 && i < H && j >= 0 && j < W ? x[((bb * H + i) * W + j) * Ci + ci] : 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) acc[t][u] = fmaf(d[u], xv, acc[t][u]);
+    }
+  }
+  float* wsp = ws + (int64_t)split * Co * TAPS * Ci;
+  if (ci_ok)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (co_b + u < Co)
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) wsp[((int64_t)(co_b + u) * TAPS + t) * Ci + ci] = acc[t][u];
+  if (bws && blockIdx.x == 0 && (threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (co_b + u < Co) bws[(int64_t)split * Co + co_b + u] = bs[u];
+}
+
+// out[e] = alpha * sum_{s = 0 .. S-1} part[s][e], in split order
+__global__ __launch_bounds__(256) void ordered_split_sum_kernel(const float* __restrict__ part, float* __restrict__ out, int64_t n,
+                                                                int S, float alpha) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    float s = 0.f;
+    for (int k = 0; k < S; ++k) s += part[(int64_t)k * n + e];
+    out[e] = alpha * s;
+  }
+}
+
+extern "C" int64_t rf_conv_wgrad_ws_bytes(int dtype, int B, int H, int W, int Co, int Ci, int taps) {
+  if (B <= 0 || H <= 0 || W <= 0 || Co <= 0 || Ci <= 0 || (taps != 1 && taps != 9)) return 0;
+  int tiles, S;
+  int64_t ups;
+  wgrad_split(dtype, (int64_t)B * H * W, Co, Ci, taps, &tiles, &S, &ups);
+  return (int64_t)S * ((int64_t)Co * taps * Ci + Co) * (int64_t)sizeof(float);
+}
+
+extern "C" int rf_conv_wgrad(const void* dy, const void* x, int dtype, float* dw, float* dbias, int B, int H, int W, int Co,
+                             int Ci, int taps, int dilation, float alpha, void* workspace, int64_t ws_bytes, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!dy || !x || !dw || B <= 0 || H <= 0 || W <= 0 || Co <= 0 || Ci <= 0) return RF_EINVAL;
+  if (taps != 1 && taps != 9) return RF_EINVAL;
+  if (taps == 9 && (dilation < 1 || dilation > 8)) return RF_EINVAL;
+  if (!workspace || ws_bytes < rf_conv_wgrad_ws_bytes(dtype, B, H, W, Co, Ci, taps)) return RF_EINVAL;
+  const int64_t P = (int64_t)B * H * W;
+  int tiles, S;
+  int64_t ups;
+  wgrad_split(dtype, P, Co, Ci, taps, &tiles, &S, &ups);
+  float* ws = (float*)workspace;
+  float* bws = dbias ? ws + (int64_t)S * Co * taps * Ci : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const int dil = taps == 9 ? dilation : 1;
+  if (dtype == RF_F32) {
+    if (((uintptr_t)dy % 4) || ((uintptr_t)x % 4)) return RF_EALIGN;
+    dim3 grid(cdiv(Ci, 64), cdiv(Co, 16), S);
+    if (taps == 9)
+      hipLaunchKernelGGL(conv_wgrad_f32_kernel<9>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, ws, bws, H, W, P, Co,
+                         Ci, dil, ups);
+    else
+      hipLaunchKernelGGL(conv_wgrad_f32_kernel<1>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, ws, bws, H, W, P, Co,
+                         Ci, dil, ups);
+  } else {
+    // 16-byte channel vectors: rows of 8-channel multiples, 16-byte aligned bases
+    if (Co % 8 || Ci % 8 || ((uintptr_t)dy % 16) || ((uintptr_t)x % 16)) return RF_EALIGN;
+    const h16_t* d16 = (const h16_t*)dy;
+    const h16_t* x16 = (const h16_t*)x;
+    if (taps == 9 && Co % 96 == 0) {
+      const int cit = (int)cdiv(Ci, 32);
+      hipLaunchKernelGGL((conv_wgrad_h16_kernel<9, 3, 1>), dim3((Co / 96) * cit, S), dim3(192), 0, s, d16, x16, ws, bws, H, W,
+                         P, Co, Ci, dil, cit, ups);
+    } else {
+      const int cit = (int)cdiv(Ci, 64);
+      const dim3 grid(cdiv(Co, 64) * cit, S);
+      if (taps == 9)
+        hipLaunchKernelGGL((conv_wgrad_h16_kernel<9, 2, 2>), grid, dim3(256), 0, s, d16, x16, ws, bws, H, W, P, Co, Ci, dil,
+                           cit, ups);
+      else
+        hipLaunchKernelGGL((conv_wgrad_h16_kernel<1, 2, 2>), grid, dim3(256), 0, s, d16, x16, ws, bws, H, W, P, Co, Ci, dil,
+                           cit, ups);
+    }
+  }
+  const int64_t n = (int64_t)Co * taps * Ci;
+  hipLaunchKernelGGL(ordered_split_sum_kernel, dim3(min(cdiv(n, 256), 4096u)), dim3(256), 0, s, ws, dw, n, S, alpha);
+  if (dbias)
+    hipLaunchKernelGGL(ordered_split_sum_kernel, dim3(cdiv(Co, 256)), dim3(256), 0, s, bws, dbias, (int64_t)Co, S, alpha);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_instnorm_bwd
+// ================================================================================================
+#define INB_PIX 128  // pixels per statistics block: the partials have the shape of rf_instnorm_stats' (rf_instnorm_ws_bytes)
+
+__device__ __forceinline__ void in_stats(const double* sums, int64_t i, int64_t HW, float eps, float* mean, float* rstd) {
+  const double s = sums[i * 2], q = sums[i * 2 + 1];
+  const double m = s / (double)HW;
+  double var = q / (double)HW - m * m;
+  var = var > 0.0 ? var : 0.0;
+  *mean = (float)m;
+  *rstd = rsqrtf((float)var + eps);
+}
+
+// incoming gradient times the ELU derivative taken from the ELU output a (y > 0 ? 1 : y + 1)
+__device__ __forceinline__ float in_geff(const float* g, const void* a, int a_dt, int64_t e) {
+  float v = g[e];
+  if (a) {
+    const float y = ld(a, a_dt, e);
+    v *= y > 0.f ? 1.f : y + 1.f;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void instnorm_bwd_stats_kernel(const float* g, const void* a, int a_dt, const void* x, int x_dt,
+                                                                 const double* sums, float eps, float* partials, int64_t HW,
+                                                                 int C) {
+  const int b = blockIdx.y;
+  const int64_t p0 = (int64_t)blockIdx.x * INB_PIX;
+  const int64_t p1 = p0 + INB_PIX < HW ? p0 + INB_PIX : HW;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float mean, rstd;
+    in_stats(sums, (int64_t)b * C + c, HW, eps, &mean, &rstd);
+    float sg = 0.f, sgx = 0.f;
+    for (int64_t p = p0; p < p1; ++p) {
+      const int64_t e = ((int64_t)b * HW + p) * C + c;
+      const float ge = in_geff(g, a, a_dt, e);
+      sg += ge;
+      sgx = fmaf(ge, (ld(x, x_dt, e) - mean) * rstd, sgx);
+    }
+    float* pp = partials + ((int64_t)b * gridDim.x + blockIdx.x) * 2 * C;
+    pp[c] = sg;
+    pp[C + c] = sgx;
+  }
+}
+
+// per (b, c): (sum g, sum g xhat) in block order (fp64) -> coef[b][c] = (mean, rstd, mean g, mean g xhat) for the apply pass;
+// dbeta[c] / dgamma[c] = the sums over b in sample order
+__global__ __launch_bounds__(256) void instnorm_bwd_finalize_kernel(const float* partials, const double* sums, float eps,
+                                                                    float4* coef, float* dgamma, float* dbeta, int B, int nblk,
+                                                                    int64_t HW, int C) {
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
+    double tg = 0.0, tx = 0.0;
+    for (int b = 0; b < B; ++b) {
+      double sg = 0.0, sx = 0.0;
+      for (int k = 0; k < nblk; ++k) {
+        const float* pp = partials + ((int64_t)b * nblk + k) * 2 * C;
+        sg += (double)pp[c];
+        sx += (double)pp[C + c];
+      }
+      float mean, rstd;
+      in_stats(sums, (int64_t)b * C + c, HW, eps, &mean, &rstd);
+      coef[(int64_t)b * C + c] = make_float4(mean, rstd, (float)(sg / (double)HW), (float)(sx / (double)HW));
+      tg += sg;
+      tx += sx;
+    }
+    if (dbeta) dbeta[c] = (float)tg;
+    if (dgamma) dgamma[c] = (float)tx;
+  }
+}
+
+// dx = gamma / sigma * (g - mean g - xhat * mean(g xhat))
+__global__ __launch_bounds__(256) void instnorm_bwd_apply_kernel(const float* g, const void* a, int a_dt, const void* x, int x_dt,
+                                                                 const float4* coef, const float* gamma, void* dx, int dx_dt,
+                                                                 float* ge_out, int64_t HW, int C, int64_t total) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int c = (int)(e % C);
+    const float4 k = coef[(e / (HW * C)) * C + c];
+    const float xh = (ld(x, x_dt, e) - k.x) * k.y;
+    const float ge = in_geff(g, a, a_dt, e);
+    st(dx, dx_dt, e, gamma[c] * k.y * (ge - k.z - xh * k.w));
+    if (ge_out) ge_out[e] = ge;  // (may alias g: each element is read and written by the same thread)
+  }
+}
+
+extern "C" int rf_instnorm_bwd(const float* g, const void* act_out, int act_dtype, const void* x, int x_dtype, const void* sums,
+                               const float* gamma, float eps, void* dx, int dx_dtype, float* ge_out, float* dgamma, float* dbeta,
+                               int B, int64_t HW, int C, void* workspace, int64_t ws_bytes, void* stream) {
+  RF_CHECK_DT(x_dtype);
+  RF_CHECK_DT(dx_dtype);
+  if (act_out) RF_CHECK_DT(act_dtype);
+  if (!g || !x || !sums || !gamma || !dx || B <= 0 || HW <= 0 || C <= 0) return RF_EINVAL;
+  const unsigned nblk = cdiv(HW, INB_PIX);
+  const int64_t part_bytes = (int64_t)B * nblk * 2 * C * (int64_t)sizeof(float);
+  const int64_t coef_off = (part_bytes + 15) / 16 * 16;
+  if (!workspace || ws_bytes < coef_off + (int64_t)B * C * (int64_t)sizeof(float4) || ((uintptr_t)workspace % 16))
+    return RF_EINVAL;
+  float* partials = (float*)workspace;
+  float4* coef = (float4*)((char*)workspace + coef_off);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(instnorm_bwd_stats_kernel, dim3(nblk, B), dim3(256), 0, s, g, act_out, act_dtype, x, x_dtype,
+                     (const double*)sums, eps, partials, HW, C);
+  hipLaunchKernelGGL(instnorm_bwd_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, partials, (const double*)sums, eps, coef, dgamma,
+                     dbeta, B, (int)nblk, HW, C);
+  const int64_t total = (int64_t)B * HW * C;
+  hipLaunchKernelGGL(instnorm_bwd_apply_kernel, dim3(min(cdiv(total, 256), 16384u)), dim3(256), 0, s, g, act_out, act_dtype, x,
+                     x_dtype, (const float4*)coef, gamma, dx, dx_dtype, ge_out, HW, C, total);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_layernorm_bwd: one wave per row (fp32 statistics recomputed from x), per-block column partials for dgamma / dbeta
+// ================================================================================================
+#define LNB_ROWS 64     // rows per block (4 waves x 16 rows)
+#define LNB_MAXC 16     // D <= 64 * LNB_MAXC
+
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* x, const float* g, const float* gamma, float eps,
+                                                            void* dx, int dx_dt, float* partials, int64_t rows, int D) {
+  __shared__ float red[4][2][64 * LNB_MAXC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nper = (D + 63) / 64;
+  float pg[LNB_MAXC], pgx[LNB_MAXC];
+#pragma unroll
+  for (int k = 0; k < LNB_MAXC; ++k) pg[k] = pgx[k] = 0.f;
+  const int64_t r0 = (int64_t)blockIdx.x * LNB_ROWS;
+  for (int rr = wave; rr < LNB_ROWS; rr += 4) {
+    const int64_t r = r0 + rr;
+    if (r >= rows) break;  // (wave-uniform)
+    const float* xr = x + r * D;
+    const float* gr = g + r * D;
+    float xv[LNB_MAXC], gv[LNB_MAXC];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < LNB_MAXC; ++k) {
+      const int c = lane + 64 * k;
+      xv[k] = k < nper && c < D ? xr[c] : 0.f;
+      gv[k] = k < nper && c < D ? gr[c] : 0.f;
+      s += xv[k];
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < LNB_MAXC; ++k) {
+      const int c = lane + 64 * k;
+      const float d = k < nper && c < D ? xv[k] - mean : 0.f;
+      q = fmaf(d, d, q);
+    }
+    const float rstd = rsqrtf(wave_sum(q) / (float)D + eps);
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < LNB_MAXC; ++k) {
+      const int c = lane + 64 * k;
+      if (k < nper && c < D) {
+        const float xh = (xv[k] - mean) * rstd;
+        const float gg = gv[k] * gamma[c];
+        m1 += gg;
+        m2 = fmaf(gg, xh, m2);
+        pg[k] += gv[k];
+        pgx[k] = fmaf(gv[k], xh, pgx[k]);
+      }
+    }
+    m1 = wave_sum(m1) / (float)D;
+    m2 = wave_sum(m2) / (float)D;
+#pragma unroll
+    for (int k = 0; k < LNB_MAXC; ++k) {
+      const int c = lane + 64 * k;
+      if (k < nper && c < D) {
+        const float xh = (xv[k] - mean) * rstd;
+        st(dx, dx_dt, r * D + c, rstd * (gv[k] * gamma[c] - m1 - xh * m2));
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < LNB_MAXC; ++k) {
+    red[wave][0][lane + 64 * k] = pg[k];
+    red[wave][1][lane + 64 * k] = pgx[k];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < D; c += 256) {
+    float tg = 0.f, tx = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      tg += red[w][0][c];
+      tx += red[w][1][c];
+    }
+    partials[(int64_t)blockIdx.x * 2 * D + c] = tg;
+    partials[(int64_t)blockIdx.x * 2 * D + D + c] = tx;
+  }
+}
+
+// dbeta[c] = sum_k partials[k][0][c], dgamma[c] = sum_k partials[k][1][c], block order, fp64
+__global__ __launch_bounds__(256) void layernorm_bwd_finalize_kernel(const float* partials, float* dgamma, float* dbeta, int nblk,
+                                                                     int D) {
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < 2 * D; c += gridDim.x * 256) {
+    double t = 0.0;
+    for (int k = 0; k < nblk; ++k) t += (double)partials[(int64_t)k * 2 * D + c];
+    if (c < D) {
+      if (dbeta) dbeta[c] = (float)t;
+    } else if (dgamma) {
+      dgamma[c - D] = (float)t;
+    }
+  }
+}
+
+extern "C" int64_t rf_layernorm_bwd_ws_bytes(int64_t rows, int D) {
+  return (int64_t)cdiv(rows, LNB_ROWS) * 2 * D * (int64_t)sizeof(float);
+}
+
+extern "C" int rf_layernorm_bwd(const float* x, const float* g, const float* gamma, float eps, void* dx, int dx_dtype,
+                                float* dgamma, float* dbeta, int64_t rows, int D, void* workspace, int64_t ws_bytes,
+                                void* stream) {
+  RF_CHECK_DT(dx_dtype);
+  if (!x || !g || !gamma || !dx || rows <= 0 || D <= 0 || D > 64 * LNB_MAXC) return RF_EINVAL;
+  if (!workspace || ws_bytes < rf_layernorm_bwd_ws_bytes(rows, D)) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nblk = cdiv(rows, LNB_ROWS);
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, s, x, g, gamma, eps, dx, dx_dtype, (float*)workspace, rows,
+                     D);
+  hipLaunchKernelGGL(layernorm_bwd_finalize_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, s, (const float*)workspace, dgamma,
+                     dbeta, (int)nblk, D);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_absmax: out[0] = max |x[e]| (fp32; NaN propagates); max is order independent, the two passes keep it atomics-free
+// ================================================================================================
+#define AMAX_BLOCKS 1024
+
+__global__ __launch_bounds__(256) void absmax_kernel(const float* x, int64_t n, float* part) {
+  __shared__ float red[4];
+  float m = 0.f;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const float v = fabsf(x[e]);
+    m = v > m || v != v ? v : m;
+  }
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+extern "C" int rf_absmax(const float* x, int64_t n, float* out, void* workspace, int64_t ws_bytes, void* stream) {
+  if (!x || !out || n <= 0) return RF_EINVAL;
+  if (!workspace || ws_bytes < AMAX_BLOCKS * (int64_t)sizeof(float)) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nb = min(cdiv(n, 256), (unsigned)AMAX_BLOCKS);
+  hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, x, n, (float*)workspace);
+  hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, (int64_t)nb, out);
+  return rf_launch_status();
+}

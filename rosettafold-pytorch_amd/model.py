@@ -266,6 +266,15 @@ class RFModule(nn.Module):
             return w.to(T()).contiguous()
         return self.cached(("wt", key), make)
 
+    def wt_input_grad(self, key, lin, npad=None):
+        """W^T [K, N (zero-padded to npad)] of a Linear / 1x1 convolution in T: the B operand of its input gradient (backward)."""
+        def make():
+            w = lin.weight.detach().reshape(lin.weight.shape[0], -1)
+            if npad is not None and npad != w.shape[0]:
+                w = torch.cat([w, w.new_zeros(npad - w.shape[0], w.shape[1])], 0)
+            return w.t().to(T()).contiguous()
+        return self.cached(("wt_input_grad", key, npad), make)
+
     def wcat(self, key, lins):
         return self.cached(("wcat", key), lambda: torch.cat([l.weight.detach() for l in lins], 0).to(T()).contiguous())
 
@@ -1327,6 +1336,168 @@ def conv3x3(mod, key, conv, x, dilation, out_dtype=None):
     return out
 
 
+def conv_input_grad_weight(w):
+    """[Co, Ci, k, k] kernel of a stride-1 "same" convolution -> [Ci, Co, k, k]: its input gradient (any dilation) is the same
+    convolution of the output gradient with the kernel rotated 180 degrees and its in / out channels swapped."""
+    return w.flip(-1, -2).transpose(0, 1)
+
+
+def conv3x3_input_grad(mod, key, conv, dy, dilation, residual=None):
+    """Input gradient of conv3x3 on the forward's implicit-GEMM engine (rf_gemm conv mode, conv288 at C = 288) with the repacked
+    kernel: fp32 NHWC (+ residual, in place when given).  The 16-bit modes write the 16-bit type (what the 288-channel engine
+    writes) and widen it; the fp32 mode writes fp32 with the exact fp32 kernel."""
+    B, Hh, Ww, Co = dy.shape
+    Ci = conv.weight.shape[1]
+    wk = mod.cached(("conv_input_grad", key), lambda: conv_input_grad_weight(conv.weight.detach()).permute(0, 2, 3, 1)
+                    .reshape(Ci, 9 * Co).to(T()).contiguous())
+    if T() == F32:
+        out = residual if residual is not None else torch.empty(B, Hh, Ww, Ci, device=dy.device, dtype=F32)
+        return ops.gemm(dy, wk, out, B * Hh * Ww, Ci, 9 * Co, conv=(B, Hh, Ww, Co, dilation), residual=residual, exact=True)
+    o16 = torch.empty(B, Hh, Ww, Ci, device=dy.device, dtype=T())
+    ops.gemm(dy, wk, o16, B * Hh * Ww, Ci, 9 * Co, conv=(B, Hh, Ww, Co, dilation))
+    if residual is not None:
+        return ops.axpby(residual, 1.0, o16, 1.0, residual)
+    return ops.axpby(o16, 1.0, None, 0.0, torch.empty(o16.shape, device=dy.device, dtype=F32))
+
+
+# ================================================================================================
+# backward of PredictionHead / ResNet / ResBlock2D (opt-in per module: enable_backward)
+# ================================================================================================
+def _recording(mod):
+    """record an autograd graph only when the module opted in AND grad mode is on (requires_grad alone never switches it on)"""
+    return getattr(mod, "_rf_backward", False) and torch.is_grad_enabled()
+
+
+def _check_backward_call(mod, row_group, *channels):
+    if row_group is not None:
+        raise NotImplementedError(f"{type(mod).__name__}: the backward pass does not support row-sharded calls (row_group)")
+    for c in channels:
+        if c % 8:
+            raise ValueError(f"{type(mod).__name__}: the backward pass needs channel counts that are multiples of 8, got {c}")
+
+
+def _copy(t):
+    return ops.axpby(t, 1.0, None, 0.0, torch.empty(t.shape, device=t.device, dtype=t.dtype))
+
+
+def _dropout_rec(t, p):
+    """dropout_(t, p) returning what the backward replays: (p, seed, offset), or None when nothing was dropped."""
+    if p is None or p <= 0.0 or t.numel() == 0:
+        return None
+    rec = (p, RT.train_seed, RT.train_offset)
+    dropout_(t, p)
+    return rec
+
+
+def _replay_dropout(g, rec):
+    """multiply g by the forward's mask / (1 - p) (rf_dropout with the recorded seed and offset), in place"""
+    if rec is None:
+        return g
+    p, seed, off = rec
+    return ops.fill(g, 0.0) if p >= 1.0 else ops.dropout(g, p, seed, off)
+
+
+def _grad_scale(gs):
+    """Power of two that brings max |g| into [1, 2) in the fp16 mode, whose 16-bit gradient operands would underflow for small
+    losses; 1 in the other modes.  Exact: every backward step is linear in the gradient, the scale is undone in fp32."""
+    if RT.dtype != torch.float16:
+        return 1.0
+    m = ops.absmax(gs)
+    if not math.isfinite(m) or m == 0.0:
+        return 1.0
+    return 2.0 ** max(-100, min(100, -math.floor(math.log2(m))))
+
+
+def _scaled_copy(g, s):
+    """fresh contiguous fp32 s * g (autograd may hand in expanded or non-contiguous gradients)"""
+    g = g.float().contiguous()
+    return ops.axpby(g, s, None, 0.0, torch.empty(g.shape, device=g.device, dtype=F32))
+
+
+def _unscale(ts, s):
+    if s != 1.0:
+        for t in ts:
+            if t is not None:
+                ops.axpby(t, 1.0 / s, None, 0.0, t)
+
+
+def _conv_weight_grad(dw, w):
+    """fp32 [Co, 9 * Ci] gradient in the forward's [co][tap][ci] layout -> a contiguous [Co, Ci, 3, 3] like the weight"""
+    Co, Ci = w.shape[0], w.shape[1]
+    out = torch.empty(Co, Ci, 3, 3, device=dw.device, dtype=F32)
+    return ops.copy4d(dw, (9 * Ci, 1, Ci, 1), out, (9 * Ci, 9, 1, 1), (Co, Ci, 9, 1))
+
+
+def _param_grads(mod, grads, s):
+    ps = list(mod.parameters())
+    out = [grads.get(p) for p in ps]
+    _unscale(out, s)
+    return tuple(out)
+
+
+class _BlockFn(torch.autograd.Function):
+    """ResBlock2D.forward with enable_backward (NCHW in / out)."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        xf = x.float().permute(0, 2, 3, 1).contiguous()
+        tape = {}
+        _, o_f = mod.run(ops.cast(xf, T()), xf, tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return o_f.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        s = _grad_scale([g.float().contiguous()])
+        dx, grads = mod._backward(ctx.tape, _scaled_copy(g.permute(0, 2, 3, 1), s))
+        ctx.tape = None
+        _unscale([dx], s)
+        return (None, dx.permute(0, 3, 1, 2) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
+
+
+class _ResNetFn(torch.autograd.Function):
+    """ResNet.forward with enable_backward (NCHW in / out)."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        xf = x.float().permute(0, 2, 3, 1).contiguous()
+        tape = {}
+        out = mod.run(ops.cast(xf, T()), tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        s = _grad_scale([g.float().contiguous()])
+        dx, grads = mod._backward(ctx.tape, _scaled_copy(g.permute(0, 2, 3, 1), s), want_dx=ctx.needs_input_grad[1])
+        ctx.tape = None
+        _unscale([dx], s)
+        return (None, dx.permute(0, 3, 1, 2) if dx is not None else None) + _param_grads(mod, grads, s)
+
+
+_HEADS = ("theta", "phi", "dist", "omega")
+
+
+class _HeadFn(torch.autograd.Function):
+    """PredictionHead.forward with enable_backward: pair fp32 NHWC -> the four logit maps (fp32 NHWC)."""
+
+    @staticmethod
+    def forward(ctx, mod, pair, *params):
+        tape = {}
+        out = mod.run(pair, tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return tuple(out[k] for k in _HEADS)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        mod = ctx.mod
+        dpair, grads, s = mod._backward(ctx.tape, dict(zip(_HEADS, gs)), want_dpair=ctx.needs_input_grad[1])
+        ctx.tape = None
+        return (None, dpair) + _param_grads(mod, grads, s)
+
+
 # ================================================================================================
 # pair axial attention
 # ================================================================================================
@@ -1686,6 +1857,7 @@ class InitialCoordGenerationWithMsaAndPair(RFModule):
 # ================================================================================================
 class ResBlock2D(RFModule):
     """resnet.py:15-44."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, channel, kernel_size, dilation, p_dropout=0.15):
         super().__init__()
@@ -1718,12 +1890,16 @@ class ResBlock2D(RFModule):
                                 out_dtype=F32, out2=shard.interior(nxt, next_halo), **kw)
         return o_t, o_f
 
-    def run(self, x_t, x_f, row_group=None, rows_global=None, next_halo=0):
+    def run(self, x_t, x_f, row_group=None, rows_global=None, next_halo=0, tape=None):
         """x_t: T NHWC (conv input), x_f: fp32 copy (residual).  Returns (T, fp32) of elu(block(x)+x).
         row_group / rows_global: x holds a block of the picture's rows (shard.resblock_row_sharded): every convolution first
-        fetches `dilation` rows from each neighbouring rank, the InstanceNorm sums are all-reduced."""
+        fetches `dilation` rows from each neighbouring rank, the InstanceNorm sums are all-reduced.
+        tape: a dict that receives what _backward needs (the recording forward of enable_backward; same kernels, same numbers)."""
         f = self.layer.fn
         kw = {} if row_group is None else {"row_group": row_group, "rows_global": rows_global}
+        if tape is not None:
+            _check_backward_call(self, row_group, x_t.shape[-1])
+            return self._run_recording(x_t, x_f, tape)
         if row_group is not None and x_t.shape[0] == 1:
             return self._run_rows_b1(x_t, x_f, row_group, rows_global, next_halo)
 
@@ -1743,13 +1919,56 @@ class ResBlock2D(RFModule):
                                 out_dtype=F32, out2_dtype=T(), **kw)
         return o_t, o_f
 
+    def _run_recording(self, x_t, x_f, tape):
+        """run() without row blocks, keeping the tensors of the backward: the convolutions' outputs (the norms' inputs), the
+        InstanceNorm statistics, the ELU output before the dropout overwrites it, the dropout's (p, seed, offset), the output."""
+        f = self.layer.fn
+        s1, s2 = [], []
+        y1 = conv3x3(self, "c1", f[0], x_t, self.dilation)
+        a, _ = ops.instnorm(y1, _f(f[1].weight), _f(f[1].bias), eps=f[1].eps, act=L.ACT_ELU, out_dtype=T(), stats_out=s1)
+        a_elu, drop = a, None
+        if self.training:
+            if _p(f[3]) > 0:
+                a_elu = _copy(a)
+            drop = _dropout_rec(a, _p(f[3]))   # resnet.py:30
+        y2 = conv3x3(self, "c2", f[4], a, self.dilation)
+        o_f, o_t = ops.instnorm(y2, _f(f[5].weight), _f(f[5].bias), eps=f[5].eps, residual=x_f, act=L.ACT_ELU,
+                                out_dtype=F32, out2_dtype=T(), stats_out=s2)
+        tape.update(x_t=x_t, y1=y1, s1=s1[0], a1=a_elu, a1d=a, drop=drop, y2=y2, s2=s2[0], o_f=o_f)
+        return o_t, o_f
+
+    def _backward(self, tape, g):
+        """g: fp32 NHWC gradient of the block output (overwritten).  Returns (fp32 gradient of the block input, {param: grad})."""
+        f, d = self.layer.fn, self.dilation
+        # elu(IN2(conv2(.)) + x): g * elu' is both the residual branch's gradient (written back into g) and IN2's input
+        dy2, dg5, db5 = ops.instnorm_bwd(g, tape["y2"], tape["s2"], _f(f[5].weight), eps=f[5].eps, act_out=tape["o_f"],
+                                         dx_dtype=T(), ge_out=g)
+        dw2, _ = ops.conv_wgrad(dy2, tape["a1d"], 9, d)
+        da = conv3x3_input_grad(self, "c2", f[4], dy2, d)
+        _replay_dropout(da, tape["drop"])
+        dy1, dg1, db1 = ops.instnorm_bwd(da, tape["y1"], tape["s1"], _f(f[1].weight), eps=f[1].eps, act_out=tape["a1"],
+                                         dx_dtype=T())
+        dw1, _ = ops.conv_wgrad(dy1, tape["x_t"], 9, d)
+        dx = conv3x3_input_grad(self, "c1", f[0], dy1, d, residual=g)
+        return dx, {f[0].weight: _conv_weight_grad(dw1, f[0].weight), f[1].weight: dg1, f[1].bias: db1,
+                    f[4].weight: _conv_weight_grad(dw2, f[4].weight), f[5].weight: dg5, f[5].bias: db5}
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd: with grad mode on, forward() records and loss.backward() fills every parameter's .grad (and the
+        input's, if it requires grad) through the HIP backward kernels.  Stored on this module; returns self."""
+        self._rf_backward = bool(mode)
+        return self
+
     def forward(self, x):  # NCHW like the reference
+        if _recording(self):
+            return _BlockFn.apply(self, x, *self.parameters())
         xf = x.float().permute(0, 2, 3, 1).contiguous()
         return self.run(ops.cast(xf, T()), xf)[1].permute(0, 3, 1, 2)
 
 
 class ResNet(RFModule):
     """resnet.py:47-83."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, n_res_blocks, in_channels, intermediate_channels, out_channels, dilations=[1, 2, 4, 8],
                  p_dropout=0.15):
@@ -1763,10 +1982,14 @@ class ResNet(RFModule):
         self.layer = nn.Sequential(*layers)
         self.n_res_blocks = n_res_blocks
 
-    def run(self, x_t, row_group=None, rows_global=None):
-        """x_t: T NHWC -> fp32 NHWC logits.  row_group / rows_global: x_t is a block of the picture's rows (see ResBlock2D.run)."""
+    def run(self, x_t, row_group=None, rows_global=None, tape=None):
+        """x_t: T NHWC -> fp32 NHWC logits.  row_group / rows_global: x_t is a block of the picture's rows (see ResBlock2D.run).
+        tape: a dict that receives what _backward needs (the recording forward of enable_backward; same kernels, same numbers)."""
         l0, l1 = self.layer[0], self.layer[1]
         kw = {} if row_group is None else {"row_group": row_group, "rows_global": rows_global}
+        if tape is not None:
+            _check_backward_call(self, row_group, x_t.shape[-1], l0.weight.shape[0])
+            return self._run_recording(x_t, tape)
         h = ops.linear(x_t, self.wt("in", l0), None)
         dil = [self.layer[3 + b].dilation for b in range(self.n_res_blocks)] + [0]
         if row_group is not None and h.shape[0] == 1:
@@ -1781,13 +2004,60 @@ class ResNet(RFModule):
         lo = self.layer[3 + self.n_res_blocks]
         return ops.linear(h_t, self.wt("out", lo), _f(lo.bias), out_dtype=F32)
 
+    def _run_recording(self, x_t, tape):
+        l0, l1 = self.layer[0], self.layer[1]
+        s0 = []
+        h = ops.linear(x_t, self.wt("in", l0), None)
+        h_f, h_t = ops.instnorm(h, _f(l1.weight), _f(l1.bias), eps=l1.eps, act=L.ACT_ELU, out_dtype=F32, out2_dtype=T(),
+                                stats_out=s0)
+        tape.update(x_t=x_t, h0=h, s0=s0[0], h_f=h_f, blocks=[])
+        for b in range(self.n_res_blocks):
+            bt = {}
+            h_t, h_f = self.layer[3 + b].run(h_t, h_f, tape=bt)
+            tape["blocks"].append(bt)
+        lo = self.layer[3 + self.n_res_blocks]
+        tape["h_last"] = h_t
+        return ops.linear(h_t, self.wt("out", lo), _f(lo.bias), out_dtype=F32)
+
+    def _backward(self, tape, g, want_dx=True):
+        """g: fp32 NHWC gradient of the logits (overwritten).  Returns (fp32 NHWC gradient of x_t or None, {param: grad})."""
+        l0, l1 = self.layer[0], self.layer[1]
+        lo = self.layer[3 + self.n_res_blocks]
+        B, H, W, Co = g.shape
+        C, Cin = lo.weight.shape[1], l0.weight.shape[1]
+        co8 = pad8(Co)   # the 37 / 19 logit channels, zero-padded to 16-byte rows
+        gp = ops.zeros(B, H, W, co8, device=g.device, dtype=T())
+        ops.copy4d(g, (0, 0, Co, 1), gp, (0, 0, co8, 1), (1, 1, B * H * W, Co))
+        dwo, dbo = ops.conv_wgrad(gp, tape["h_last"], 1, bias=True)
+        grads = {lo.weight: dwo[:Co].view(Co, C, 1, 1), lo.bias: dbo[:Co]}
+        dh = ops.linear(gp, self.wt_input_grad("out", lo, co8), None, out_dtype=F32, exact=True)
+        for b in reversed(range(self.n_res_blocks)):
+            dh, gb = self.layer[3 + b]._backward(tape["blocks"][b], dh)
+            grads.update(gb)
+        dh0, dg, db = ops.instnorm_bwd(dh, tape["h0"], tape["s0"], _f(l1.weight), eps=l1.eps, act_out=tape["h_f"], dx_dtype=T())
+        dwi, _ = ops.conv_wgrad(dh0, tape["x_t"], 1)
+        grads.update({l0.weight: dwi.view(C, Cin, 1, 1), l1.weight: dg, l1.bias: db})
+        dx = ops.linear(dh0, self.wt_input_grad("in", l0), None, out_dtype=F32, exact=True) if want_dx else None
+        return dx, grads
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd for this ResNet and its ResBlock2Ds (see ResBlock2D.enable_backward).  Returns self."""
+        self._rf_backward = bool(mode)
+        for m in self.layer:
+            if isinstance(m, ResBlock2D):
+                m.enable_backward(mode)
+        return self
+
     def forward(self, x):  # NCHW in / NCHW out like the reference
+        if _recording(self):
+            return _ResNetFn.apply(self, x, *self.parameters())
         xf = x.float().permute(0, 2, 3, 1).contiguous()
         return self.run(ops.cast(xf, T())).permute(0, 3, 1, 2)
 
 
 class PredictionHead(RFModule):
     """rf.py:1130-1172."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, in_channels, n_res_blocks, p_dropout):
         super().__init__()
@@ -1799,15 +2069,67 @@ class PredictionHead(RFModule):
         self.phi_head = nn.Sequential(ResNet(n_res_blocks, c, c, 19, p_dropout=p_dropout), nn.Identity())
 
     def forward(self, pair):
+        if _recording(self):
+            return dict(zip(_HEADS, _HeadFn.apply(self, pair.float().contiguous(), *self.parameters())))
         return self.run(pair.float().contiguous())
 
-    def run(self, pair, row_group=None):
+    def enable_backward(self, mode=True):
+        """Opt in to autograd for the head, its four ResNets and their ResBlock2Ds: with grad mode on, forward() returns logits
+        that take part in autograd and loss.backward() fills the .grad of every head parameter (and of the pair input when it
+        requires grad) through the HIP backward kernels.  In train() mode the backward replays the forward's dropout masks.
+        Stored on the modules (no global state); returns self."""
+        self._rf_backward = bool(mode)
+        for name in _HEADS:
+            getattr(self, name + "_head")[0].enable_backward(mode)
+        return self
+
+    def _backward(self, tape, gs, want_dpair=True):
+        """gs: {name: gradient of that logit map}.  Returns (fp32 gradient of pair or None, {param: grad}, 1.0): the unscaled
+        gradients (each ResNet and the projection scale their own operands in the fp16 mode)."""
+        grads, d = {}, {}
+        for name in _HEADS:
+            res = getattr(self, name + "_head")[0]
+            s = _grad_scale([gs[name].float().contiguous()])
+            d[name], gr = res._backward(tape[name], _scaled_copy(gs[name], s))
+            _unscale([d[name]] + list(gr.values()), s)
+            grads.update(gr)
+        B, Lr, _, Cc = d["theta"].shape
+        # x feeds theta / phi, xs = (x + x^T) / 2 feeds dist / omega (rf.py:1160)
+        da = ops.axpby(d["dist"], 1.0, d["omega"], 1.0, d["dist"])
+        dat = torch.empty_like(da)
+        ops.copy4d(da, (Lr * Lr * Cc, Cc, Lr * Cc, 1), dat, (Lr * Lr * Cc, Lr * Cc, Cc, 1), (B, Lr, Lr, Cc))
+        dx = ops.axpby(d["theta"], 1.0, d["phi"], 1.0, d["theta"])
+        ops.axpby(dx, 1.0, da, 0.5, dx)
+        ops.axpby(dx, 1.0, dat, 0.5, dx)
+        # the 16-bit modes' centring of x (and of the projection's operand) is invariant for every consumer: no gradient term
+        _replay_dropout(dx, tape["drop"])
+        s = _grad_scale([dx])
+        if s != 1.0:
+            ops.axpby(dx, s, None, 0.0, dx)
+        lin, lnm = self.proj[1], self.proj[0]
+        dx_t = ops.cast(dx, T())
+        dw, db = ops.conv_wgrad(dx_t, tape["op"], 1, bias=True)
+        grads.update({lin.weight: dw, lin.bias: db})
+        dpair = None
+        if want_dpair or lnm.weight.requires_grad or lnm.bias.requires_grad:
+            dt = ops.linear(dx_t, self.wt_input_grad("p", lin), None, out_dtype=F32, exact=True)
+            dpair, dg, dbeta = ops.layernorm_bwd(tape["pair"], dt, _f(lnm.weight), eps=lnm.eps)
+            grads.update({lnm.weight: dg, lnm.bias: dbeta})
+        _unscale([dw, db, dpair, grads.get(lnm.weight), grads.get(lnm.bias)], s)
+        return (dpair if want_dpair else None), grads, 1.0
+
+    def run(self, pair, row_group=None, tape=None):
         """pair fp32 [B, L, L, C] -> the four logit maps (fp32 NHWC).  row_group: `pair` is this rank's block of rows
         [B, h, L, C] (contiguous split shard.shard_range(L, world, rank)); the symmetrisation (rf.py:1160) fetches the
         transposed sub-blocks from the other ranks, the ResNets exchange halo rows and InstanceNorm sums; returns the same rows
         of the logit maps."""
         B, h, Lr, Cc = pair.shape
+        if tape is not None:
+            _check_backward_call(self, row_group, Cc, self.proj[1].weight.shape[0])
+        elif row_group is not None and getattr(self, "_rf_backward", False) and torch.is_grad_enabled():
+            raise NotImplementedError("PredictionHead: the backward pass does not support row-sharded calls (row_group)")
         kwc = {} if row_group is None else {"row_group": row_group, "rows_global": Lr}
+        drop = None
         # Operand conditioning for the 16-bit modes (exact in exact arithmetic): every ResNet starts conv1x1 (no bias) ->
         # InstanceNorm (resnet.py:57-60), which is invariant to a per-channel constant of the conv's input, and the mean over
         # the picture of 0.5 (x + x^T) is the mean of x.  At random init that constant is ~19x the part that varies over the
@@ -1817,11 +2139,16 @@ class PredictionHead(RFModule):
         cond = RT.head_center and ops.is_h16(T()) and Cc % 4 == 0 and self.proj[1].weight.shape[0] % 4 == 0
         if cond and not self.training:
             t = ln(self.proj[0], pair, out_dtype=F32)
-            x = ops.linear(ops.center_apply(t, ops.channel_mean(t, **kwc), out_dtype=T()), self.wt("p", self.proj[1]), None, out_dtype=F32)
+            op = ops.center_apply(t, ops.channel_mean(t, **kwc), out_dtype=T())
+            x = ops.linear(op, self.wt("p", self.proj[1]), None, out_dtype=F32)
         else:
-            x = ops.linear(ln(self.proj[0], pair), self.wt("p", self.proj[1]), _f(self.proj[1].bias), out_dtype=F32)
+            op = ln(self.proj[0], pair)
+            x = ops.linear(op, self.wt("p", self.proj[1]), _f(self.proj[1].bias), out_dtype=F32)
             if self.training:
-                dropout_(x, _p(self.proj[2]))   # rf.py:1138
+                if tape is not None:
+                    drop = _dropout_rec(x, _p(self.proj[2]))
+                else:
+                    dropout_(x, _p(self.proj[2]))   # rf.py:1138
             if cond:
                 ops.center_apply(x, ops.channel_mean(x, **kwc))
         if row_group is None:
@@ -1834,5 +2161,11 @@ class PredictionHead(RFModule):
             kw = {"row_group": row_group, "rows_global": Lr}
         xs = ops.axpby(x, 0.5, xt, 0.5, torch.empty(x.shape, device=x.device, dtype=T()))
         x_t = ops.cast(x, T())
+        if tape is not None:
+            tape.update(pair=pair, op=op, drop=drop)
+            for name in _HEADS:
+                tape[name] = {}
+            return {"theta": self.theta_head[0].run(x_t, tape=tape["theta"]), "phi": self.phi_head[0].run(x_t, tape=tape["phi"]),
+                    "dist": self.dist_head[0].run(xs, tape=tape["dist"]), "omega": self.omega_head[0].run(xs, tape=tape["omega"])}
         return {"theta": self.theta_head[0].run(x_t, **kw), "phi": self.phi_head[0].run(x_t, **kw),
                 "dist": self.dist_head[0].run(xs, **kw), "omega": self.omega_head[0].run(xs, **kw)}

@@ -374,10 +374,11 @@ def weighted_msa_sum(x, w, y, y_ld):
 
 
 def instnorm(x, gamma, beta, *, eps=1e-6, residual=None, act=L.ACT_NONE, out_dtype=None, out2_dtype=None, row_group=None,
-             rows_global=None, out=None, out2=None):
+             rows_global=None, out=None, out2=None, stats_out=None):
     """InstanceNorm2d(affine) over NHWC x [B,H,W,C]; returns (y, y2) where y2 is an optional second copy.
     row_group / rows_global: x is a block of H of the picture's rows_global rows, the other blocks live on the other ranks of
-    the torch.distributed group: the per-(b, c) sums are all-reduced (2*B*C doubles) before they are applied."""
+    the torch.distributed group: the per-(b, c) sums are all-reduced (2*B*C doubles) before they are applied.
+    stats_out: a list the fp64 sums of rf_instnorm_stats are appended to (what instnorm_bwd takes)."""
     B, H, W, Cc = x.shape
     _need_cuda(x, gamma, beta, residual)
     sums = torch.empty(B * Cc * 2, device=x.device, dtype=torch.float64)  # fully written by the ordered finalize step
@@ -390,6 +391,8 @@ def instnorm(x, gamma, beta, *, eps=1e-6, residual=None, act=L.ACT_NONE, out_dty
         shard.all_reduce_sum(sums, row_group)
         # rf_instnorm_apply divides by ITS pixel count: hand it global sums scaled to the local block (exact up to one rounding)
         sums.mul_(float(H) / float(rows_global))
+    if stats_out is not None:
+        stats_out.append(sums)
     # out / out2: caller-owned contiguous destinations (e.g. the interior of a pre-haloed picture, shard.haloed_buffer)
     y = out if out is not None else torch.empty(x.shape, device=x.device, dtype=out_dtype or x.dtype)
     y2 = out2 if out2 is not None else (torch.empty(x.shape, device=x.device, dtype=out2_dtype) if out2_dtype is not None else None)
@@ -401,6 +404,84 @@ def instnorm(x, gamma, beta, *, eps=1e-6, residual=None, act=L.ACT_NONE, out_dty
                                 ptr(y), dcode(y.dtype), ptr(y2), dcode(y2.dtype) if y2 is not None else 0, B, H * W,
                                 Cc, stream()), "rf_instnorm_apply")
     return y, y2
+
+
+# --------------------------------------------------------------------------------------------- backward (csrc/backward.hip)
+def conv_wgrad(dy, x, taps, dilation=1, *, bias=False, alpha=1.0):
+    """Weight gradient of a stride-1 "same" convolution (rf_conv_wgrad): dy [..., Co], x [..., Ci] contiguous of one dtype
+    (fp32: exact; the 16-bit type: MFMA with fp32 accumulation).  taps = 9: NHWC [B, H, W, C] tensors, 3x3 kernel of `dilation`;
+    taps = 1: any leading shape (1x1 convolution / Linear over the rows).  Returns (fp32 dW [Co, taps * Ci] in the forward's
+    [co][tap][ci] weight layout, fp32 dbias [Co] or None), both times alpha."""
+    _need_cuda(dy, x)
+    if dy.dtype != x.dtype or not (dy.is_contiguous() and x.is_contiguous()) or dy.shape[:-1] != x.shape[:-1]:
+        raise ValueError("conv_wgrad: contiguous dy / x of one dtype and the same pixels")
+    Co, Ci = dy.shape[-1], x.shape[-1]
+    if taps == 9:
+        B, H, W = dy.shape[0], dy.shape[1], dy.shape[2]
+    else:
+        B, H, W = 1, 1, dy.numel() // Co
+    code = dcode(dy.dtype)
+    ws_bytes = int(lib.rf_conv_wgrad_ws_bytes(code, B, H, W, Co, Ci, taps))
+    if ws_bytes <= 0:
+        raise ValueError(f"conv_wgrad: unsupported shape / taps ({tuple(dy.shape)}, {Ci}, taps={taps})")
+    ws = torch.empty(ws_bytes, device=dy.device, dtype=torch.uint8)
+    dw = torch.empty(Co, taps * Ci, device=dy.device, dtype=F32)
+    db = torch.empty(Co, device=dy.device, dtype=F32) if bias else None
+    check(lib.rf_conv_wgrad(ptr(dy), ptr(x), code, ptr(dw), ptr(db), B, H, W, Co, Ci, taps, int(dilation), float(alpha), ptr(ws),
+                            ws_bytes, stream()), "rf_conv_wgrad")
+    return dw, db
+
+
+def instnorm_bwd(g, x, sums, gamma, *, eps=1e-6, act_out=None, dx_dtype=F32, ge_out=None):
+    """InstanceNorm2d(affine) backward over NHWC (rf_instnorm_bwd): g fp32 gradient of the (ELU'd, when act_out = the saved ELU
+    output is given) norm output, x the saved norm input, sums the forward's statistics (instnorm(stats_out=...)).
+    Returns (dx of dx_dtype, fp32 dgamma [C], fp32 dbeta [C]); ge_out: fp32 destination of g times the ELU derivative (may be g)."""
+    B, H, W, Cc = x.shape
+    _need_cuda(g, x, sums, gamma, act_out, ge_out)
+    for t in (g, x, act_out, ge_out):
+        if t is not None and (tuple(t.shape) != tuple(x.shape) or not t.is_contiguous()):
+            raise ValueError("instnorm_bwd: contiguous tensors of one shape")
+    if g.dtype != F32 or (ge_out is not None and ge_out.dtype != F32):
+        raise TypeError("instnorm_bwd: g / ge_out must be fp32")
+    ws_bytes = (int(lib.rf_instnorm_ws_bytes(B, H * W, Cc)) + 15) // 16 * 16 + 16 * B * Cc
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    dx = torch.empty(x.shape, device=x.device, dtype=dx_dtype)
+    dgamma = torch.empty(Cc, device=x.device, dtype=F32)
+    dbeta = torch.empty(Cc, device=x.device, dtype=F32)
+    check(lib.rf_instnorm_bwd(ptr(g), ptr(act_out), dcode(act_out.dtype) if act_out is not None else 0, ptr(x), dcode(x.dtype),
+                              ptr(sums), ptr(gamma), float(eps), ptr(dx), dcode(dx_dtype), ptr(ge_out), ptr(dgamma), ptr(dbeta),
+                              B, H * W, Cc, ptr(ws), ws_bytes, stream()), "rf_instnorm_bwd")
+    return dx, dgamma, dbeta
+
+
+def layernorm_bwd(x, g, gamma, *, eps=1e-5, dx_dtype=F32):
+    """LayerNorm backward over the last dim (rf_layernorm_bwd): x fp32 (the forward's input), g fp32 gradient of the output.
+    Returns (dx of dx_dtype, fp32 dgamma [D], fp32 dbeta [D])."""
+    D = x.shape[-1]
+    rows = x.numel() // D
+    _need_cuda(x, g, gamma)
+    if x.dtype != F32 or g.dtype != F32 or tuple(g.shape) != tuple(x.shape) or not (x.is_contiguous() and g.is_contiguous()):
+        raise ValueError("layernorm_bwd: contiguous fp32 x and g of one shape")
+    ws_bytes = int(lib.rf_layernorm_bwd_ws_bytes(rows, D))
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    dx = torch.empty(x.shape, device=x.device, dtype=dx_dtype)
+    dgamma = torch.empty(D, device=x.device, dtype=F32)
+    dbeta = torch.empty(D, device=x.device, dtype=F32)
+    check(lib.rf_layernorm_bwd(ptr(x), ptr(g), ptr(gamma), float(eps), ptr(dx), dcode(dx_dtype), ptr(dgamma), ptr(dbeta), rows, D,
+                               ptr(ws), ws_bytes, stream()), "rf_layernorm_bwd")
+    return dx, dgamma, dbeta
+
+
+def absmax(xs):
+    """max |x| over fp32 tensors (rf_absmax; one host read for the whole list)."""
+    _need_cuda(*xs)
+    out = torch.empty(len(xs), device=xs[0].device, dtype=F32)
+    ws = torch.empty(4096, device=xs[0].device, dtype=torch.uint8)
+    for i, x in enumerate(xs):
+        if x.dtype != F32 or not x.is_contiguous():
+            raise ValueError("absmax: contiguous fp32 tensors")
+        check(lib.rf_absmax(ptr(x), x.numel(), ptr(out, i), ptr(ws), 4096, stream()), "rf_absmax")
+    return max(out.tolist())
 
 
 def center_channels(x, out=None):

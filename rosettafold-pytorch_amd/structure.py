@@ -553,19 +553,28 @@ class RoseTTAFold(RFModule):
                                       n_neighbors=32, p_dropout=p_dropout)
         self.prediction_head = PredictionHead(in_channels=d_pair, n_res_blocks=4, p_dropout=p_dropout)
 
-    @torch.no_grad()
     def forward(self, msa, seq, aa_idx):
-        if not msa.is_cuda:
-            raise L.RfmiError("RoseTTAFold (MI355X build) needs device tensors; there is no CPU fallback")
-        with torch.cuda.device(msa.device):  # device guard: kernels go to the inputs' GPU, whatever the caller's current one
-            msa, seq, aa_idx = msa.contiguous(), seq.contiguous(), aa_idx.contiguous()
-            # the reference raises IndexError for out-of-range tokens / residue indices (nn.Embedding, rf.py:73,98)
-            mono = check_index_range(msa, seq, aa_idx, self.msa_emb.to_embedding.num_embeddings,
-                                     min(self.msa_emb.pos_enc.max_len, self.pair_emb.pos_enc.max_len))
-            _PENDING_EDGE_COUNTS.clear()
-            out = self.forward_validated(msa, seq, aa_idx, mono)
-            check_edge_capacity()
-            return out
+        """The inference forward, under no_grad.  With prediction_head.enable_backward() and the caller's grad mode on, the trunk
+        still runs under no_grad and only the head records: the logits take part in autograd (xyz and plddt do not)."""
+        head_grad = torch.is_grad_enabled() and getattr(self.prediction_head, "_rf_backward", False)
+        with torch.no_grad():
+            if not msa.is_cuda:
+                raise L.RfmiError("RoseTTAFold (MI355X build) needs device tensors; there is no CPU fallback")
+            with torch.cuda.device(msa.device):  # device guard: kernels go to the inputs' GPU, whatever the caller's current one
+                msa, seq, aa_idx = msa.contiguous(), seq.contiguous(), aa_idx.contiguous()
+                # the reference raises IndexError for out-of-range tokens / residue indices (nn.Embedding, rf.py:73,98)
+                mono = check_index_range(msa, seq, aa_idx, self.msa_emb.to_embedding.num_embeddings,
+                                         min(self.msa_emb.pos_enc.max_len, self.pair_emb.pos_enc.max_len))
+                _PENDING_EDGE_COUNTS.clear()
+                if not head_grad:
+                    out = self.forward_validated(msa, seq, aa_idx, mono)
+                    check_edge_capacity()
+                    return out
+                p, xyz, plddt = self._trunk(msa, seq, aa_idx, mono)
+                check_edge_capacity()
+        with torch.cuda.device(msa.device), torch.enable_grad():
+            logits = self.prediction_head(p)
+        return logits, xyz, plddt
 
     @torch.no_grad()
     def forward_validated(self, msa, seq, aa_idx, mono=True, row_group=None):
@@ -574,6 +583,14 @@ class RoseTTAFold(RFModule):
         row_group: ONE sample spread over the ranks of a torch.distributed group (shard.forward_row_sharded): every rank gets the
         same inputs, the pair track runs on row blocks shard_range(L, world, rank), the MSA and structure tracks are replicated;
         returns this rank's rows of the logit maps and the whole xyz / plddt."""
+        with torch.cuda.device(msa.device):
+            p, xyz, plddt = self._trunk(msa, seq, aa_idx, mono, row_group)
+            logits = self.prediction_head.run(p, row_group)
+        return logits, xyz, plddt
+
+    @torch.no_grad()
+    def _trunk(self, msa, seq, aa_idx, mono, row_group=None):
+        """forward_validated up to the prediction head: returns (pair or this rank's rows of it, xyz, plddt)."""
         with torch.cuda.device(msa.device):
             m = self.msa_emb.run(msa, aa_idx)
             p = self.pair_emb.run(seq, aa_idx)
@@ -587,8 +604,7 @@ class RoseTTAFold(RFModule):
             for blk in self.three_track_blocks:
                 m, p, xyz = blk.run3(m, p, xyz, onehot, aa_idx, mono, row_group)
             m, p, xyz, plddt = self.final_block.run3(m, p, xyz, onehot, aa_idx, mono, row_group)
-            logits = self.prediction_head.run(p, row_group)
-        return logits, xyz, plddt
+        return p, xyz, plddt
 
 
 def flat_state(model):
