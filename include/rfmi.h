@@ -498,6 +498,24 @@ int rf_layernorm_bwd(const float* x, const float* g, const float* gamma, float e
 /* out[0] = max_e |x[e]| over n fp32 elements (the power-of-two gradient scale of the fp16 build); workspace >= 4096 bytes. */
 int rf_absmax(const float* x, int64_t n, float* out, void* workspace, int64_t ws_bytes, void* stream);
 
+/* ---- backward pass of the pair axial attention (csrc/backward.hip; model.py PerformerSelfAttention / FeedForward,
+ * rf.py:501-528) -------------------------------------------------------------------------------------------------------------
+ * The products of the FAVOR+ and feed-forward backward run on rf_gemm and rf_conv_wgrad; these are the elementwise pieces.
+ *
+ * Linear-attention normalisation backward, for out = num[r, :dh] / num[r, dh] (rf_linattn_normalize), g fp32 = d out:
+ *   dnum[r, c] = g[r, c] / num[r, dh]  (c < dh),  dnum[r, dh] = -sum_c g[r, c] out[r, c] / num[r, dh],  dnum[r, dh+1 .. dnum_ld) = 0
+ * num fp32 (row stride num_ld > dh), g fp32 (row stride g_ld >= dh), dnum of dtype (row stride dnum_ld > dh); dh <= 64. */
+int rf_linattn_normalize_bwd(const float* num, int64_t num_ld, const float* g, int64_t g_ld, void* dnum, int dtype,
+                             int64_t dnum_ld, int64_t rows, int dh, void* stream);
+/* ReLU feature-map backward of the generalized FAVOR+ kernel (phi = relu(z) + eps for columns < nvalid, 0 beyond):
+ *   dz[r, c] = (c < nvalid && z[r, c] > 0) ? dphi[r, c] : 0      dphi, z fp32 [rows, ld]; dz of dtype [rows, ld]
+ * z is the fp32 pre-activation (the mask is never taken from a rounded phi). */
+int rf_relu_feature_bwd(const float* dphi, const float* z, void* dz, int dtype, int64_t rows, int ld, int nvalid, void* stream);
+/* Feed-forward hidden backward, for h = dropout(relu(hpre)) of the training-mode forward (rf_dropout mask (p, seed, offset)):
+ *   dh[e] = hpre[e] > 0 ? g[e] * keep(e) / (1 - p) : 0     (p = 0: no mask)   g, hpre fp32 [n]; dh of dtype [n]; 0 <= p < 1 */
+int rf_relu_dropout_bwd(const float* g, const float* hpre, void* dh, int dtype, float p, uint64_t seed, uint64_t offset, int64_t n,
+                        void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

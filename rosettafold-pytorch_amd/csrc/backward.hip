@@ -1,4 +1,5 @@
-// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172) on gfx950: the weight gradient of a
+// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172) and of the pair axial attention (end of
+// file) on gfx950: the weight gradient of a
 // stride-1 "same" convolution (pixel contraction), InstanceNorm2d(affine) backward, LayerNorm backward, and the absolute
 // maximum the fp16 build scales its gradients by.  Input gradients of the convolutions / Linears run on rf_gemm (the forward's
 // implicit-GEMM engine with a repacked weight); these kernels are what the forward does not already have.
@@ -519,5 +520,77 @@ extern "C" int rf_absmax(const float* x, int64_t n, float* out, void* workspace,
   const unsigned nb = min(cdiv(n, 256), (unsigned)AMAX_BLOCKS);
   hipLaunchKernelGGL(absmax_kernel, dim3(nb), dim3(256), 0, s, x, n, (float*)workspace);
   hipLaunchKernelGGL(absmax_kernel, dim3(1), dim3(256), 0, s, (const float*)workspace, (int64_t)nb, out);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// pair axial attention backward (model.py PerformerSelfAttention / FeedForward, rf.py:501-528): the elementwise pieces the
+// unfused forward chain does not have.  Every product of the FAVOR+ / feed-forward backward runs on rf_gemm / rf_conv_wgrad.
+// ================================================================================================
+
+// rf_linattn_normalize_bwd: one wave per row.  out = N[:, :dh] / den, den = N[:, dh]:
+//   dN[:, :dh] = g / den,  dN[:, dh] = -sum_c g out / den,  dN[:, dh + 1 .. dn_ld) = 0
+__global__ __launch_bounds__(256) void linattn_normalize_bwd_kernel(const float* __restrict__ num, int64_t num_ld,
+                                                                    const float* __restrict__ g, int64_t g_ld, void* dn, int dn_dt,
+                                                                    int64_t dn_ld, int64_t rows, int dh) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;  // (wave-uniform)
+  const float den = num[r * num_ld + dh];
+  const float gv = lane < dh ? g[r * g_ld + lane] : 0.f;
+  const float ov = lane < dh ? num[r * num_ld + lane] / den : 0.f;
+  const float s = wave_sum(gv * ov);
+  for (int c = lane; c < dn_ld; c += 64) {
+    const float v = c < dh ? gv / den : (c == dh ? -s / den : 0.f);
+    st(dn, dn_dt, r * dn_ld + c, v);
+  }
+}
+
+extern "C" int rf_linattn_normalize_bwd(const float* num, int64_t num_ld, const float* g, int64_t g_ld, void* dnum, int dtype,
+                                        int64_t dnum_ld, int64_t rows, int dh, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!num || !g || !dnum || rows <= 0 || dh <= 0 || dh > 64 || num_ld <= dh || g_ld < dh || dnum_ld <= dh) return RF_EINVAL;
+  hipLaunchKernelGGL(linattn_normalize_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, num, num_ld, g, g_ld,
+                     dnum, dtype, dnum_ld, rows, dh);
+  return rf_launch_status();
+}
+
+// rf_relu_feature_bwd: dz[r][c] = c < nvalid && z[r][c] > 0 ? dphi[r][c] : 0   (rows x ld, fp32 in, dz of dtype)
+__global__ __launch_bounds__(256) void relu_feature_bwd_kernel(const float* __restrict__ dphi, const float* __restrict__ z, void* dz,
+                                                               int dz_dt, int ld_, int nvalid, int64_t total) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int c = (int)(e % ld_);
+    st(dz, dz_dt, e, c < nvalid && z[e] > 0.f ? dphi[e] : 0.f);
+  }
+}
+
+extern "C" int rf_relu_feature_bwd(const float* dphi, const float* z, void* dz, int dtype, int64_t rows, int ld, int nvalid,
+                                   void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!dphi || !z || !dz || rows <= 0 || ld <= 0 || nvalid < 0 || nvalid > ld) return RF_EINVAL;
+  const int64_t total = rows * ld;
+  hipLaunchKernelGGL(relu_feature_bwd_kernel, dim3(min(cdiv(total, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, dphi, z, dz,
+                     dtype, ld, nvalid, total);
+  return rf_launch_status();
+}
+
+// rf_relu_dropout_bwd: dh[e] = h[e] > 0 ? g[e] * (keep(seed, offset, e) ? 1 / (1 - p) : 0) : 0   (p = 0: no mask)
+__global__ __launch_bounds__(256) void relu_dropout_bwd_kernel(const float* __restrict__ g, const float* __restrict__ h, void* dh,
+                                                               int dh_dt, int drop, unsigned thresh, float inv_keep, uint64_t seed,
+                                                               uint64_t offset, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    float v = h[e] > 0.f ? g[e] : 0.f;
+    if (drop) v = dropout_keep(seed, offset, e, thresh) ? v * inv_keep : 0.f;
+    st(dh, dh_dt, e, v);
+  }
+}
+
+extern "C" int rf_relu_dropout_bwd(const float* g, const float* h, void* dh, int dtype, float p, uint64_t seed, uint64_t offset,
+                                   int64_t n, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!g || !h || !dh || n < 0 || !(p >= 0.f) || !(p < 1.f)) return RF_EINVAL;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(min(cdiv(n, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, g, h, dh, dtype,
+                     p > 0.f ? 1 : 0, dropout_threshold(p), 1.f / (1.f - p), seed, offset, n);
   return rf_launch_status();
 }

@@ -94,6 +94,31 @@ __device__ __forceinline__ float wave_max(float v) {
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
+// Training-mode dropout mask (rf_dropout, csrc/ops.hip; replayed by the backward kernels): Philox4x32-10 keyed by the 64-bit
+// seed, counter = offset + element / 4, word element % 4.
+__device__ __forceinline__ void philox4x32_10(uint64_t ctr, uint64_t key, unsigned (&r)[4]) {
+  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
+  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+// keep[e] of the mask (seed, offset): uniform 32-bit word >= p * 2^32
+__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t offset, int64_t e, unsigned thresh) {
+  unsigned r[4];
+  philox4x32_10(offset + (uint64_t)(e >> 2), seed, r);
+  return r[e & 3] >= thresh;
+}
+static inline unsigned dropout_threshold(float p) {
+  const double t = (double)p * 4294967296.0;
+  return t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
+}
+
 static inline int rf_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

@@ -1155,28 +1155,7 @@ extern "C" int rf_tile_1d_feats(const float* msa1d, void* feat, int dtype, int64
 // word element % 4 -- a mask depends on (seed, offset, element index) only, so a fixed seed reproduces a forward bit for bit on
 // any grid, and the host hands every dropout call of a forward its own offset range (no state on the device).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint64_t ctr, uint64_t key, unsigned (&r)[4]) {
-  unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0u, c3 = 0u;
-  unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-// keep[e] of the mask (seed, offset): uniform 32-bit word >= p * 2^32
-__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t offset, int64_t e, unsigned thresh) {
-  unsigned r[4];
-  philox4x32_10(offset + (uint64_t)(e >> 2), seed, r);
-  return r[e & 3] >= thresh;
-}
-static inline unsigned dropout_threshold(float p) {
-  const double t = (double)p * 4294967296.0;
-  return t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
-}
+// (philox4x32_10 / dropout_keep / dropout_threshold: common.h, shared with the backward's mask replay)
 
 __global__ __launch_bounds__(256) void dropout_kernel(const void* x, void* y, int dt, unsigned thresh, float inv_keep, uint64_t seed,
                                                       uint64_t offset, int64_t n) {
@@ -1463,7 +1442,7 @@ extern "C" int rf_add_pos_enc(const float* x, const int64_t* aa_idx, const float
   return rf_launch_status();
 }
 
-extern "C" int rf_version(void) { return 6; }
+extern "C" int rf_version(void) { return 7; }
 #ifdef RF_H16_IS_F16
 extern "C" const char* rf_build_info(void) { return "librfmi_f16 gfx950 (MI355X) round-3: 16-bit operand type = IEEE fp16"; }
 #else

@@ -150,13 +150,17 @@ def _p(drop_module):
     return float(drop_module.p) if isinstance(drop_module, nn.Dropout) else 0.0
 
 
-def add_dropped(x_res, compute, drops):
+def add_dropped(x_res, compute, drops, recs=None):
     """x_res += dropout_{p_k}(... dropout_{p_1}(f)) for the training-mode forward: `compute(tmp)` ADDS f to the zeroed fp32 tmp
-    (every producer of the forward path accumulates into a residual stream: handing it zeros yields f itself)."""
+    (every producer of the forward path accumulates into a residual stream: handing it zeros yields f itself).
+    recs: a list that receives each dropout's (p, seed, offset) record (the recording forward of enable_backward)."""
     tmp = ops.zeros(*x_res.shape, device=x_res.device, dtype=F32)
     compute(tmp)
     for pk in drops:
-        dropout_(tmp, pk)
+        if recs is None:
+            dropout_(tmp, pk)
+        else:
+            recs.append(_dropout_rec(tmp, pk))
     return ops.axpby(x_res, 1.0, tmp, 1.0, x_res)
 
 
@@ -307,12 +311,13 @@ class Linear(nn.Linear):
         return ops.linear(xt, ops.cast(self.weight.detach().contiguous(), T()), _f(self.bias), out_dtype=F32)
 
 
-def project_into_residual(x, w, bias, x_res, next_ln, drops=(), xn_out=None):
+def project_into_residual(x, w, bias, x_res, next_ln, drops=(), xn_out=None, recs=None):
     """x_res += x @ w^T + bias, with the next LayerNorm when the fused epilogue applies (ops.linear_residual_ln); training mode:
-    `drops` = the dropouts the reference applies to the projected tensor before the residual add (then returns None)."""
+    `drops` = the dropouts the reference applies to the projected tensor before the residual add (then returns None); recs: see
+    add_dropped."""
     drops = tuple(d for d in drops if d and d > 0)
     if drops:
-        add_dropped(x_res, lambda tmp: ops.linear(x, w, bias, out=tmp, residual=tmp), drops)
+        add_dropped(x_res, lambda tmp: ops.linear(x, w, bias, out=tmp, residual=tmp), drops, recs)
         return None
     return ops.linear_residual_ln(x, w, bias, x_res, next_ln, xn_out)
 
@@ -384,22 +389,33 @@ class RowWise(nn.Module):
 
 class FeedForward(RFModule):
     """rf.py:270-281."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, d_emb, d_ff, p_dropout=0.1):
         super().__init__()
         self.net = nn.Sequential(Linear(d_emb, d_ff), nn.ReLU(), nn.Dropout(p_dropout), Linear(d_ff, d_emb))
 
-    def apply_residual(self, xn, x_res, next_ln=None, drops=()):
+    def apply_residual(self, xn, x_res, next_ln=None, drops=(), tape=None):
         """x_res += W2 relu(W1 xn + b1) + b2   (x_res fp32, in place).  With `next_ln` the second GEMM's epilogue also
         emits next_ln(x_res) (returned, or None when the fused form does not apply).
         Training mode (self.training): dropout on the hidden activations (rf.py:276) and, from the wrapping module, `drops` on
-        the block's output before the residual add (rf.py:25-26, 330) -- two GEMMs with the hidden tensor in memory."""
+        the block's output before the residual add (rf.py:25-26, 330) -- two GEMMs with the hidden tensor in memory.
+        tape: a dict that receives what _backward needs (the normalised input and the dropout records; same kernels, same
+        numbers)."""
         ph = _p(self.net[2]) if self.training else 0.0
         drops = tuple(d for d in drops if d and d > 0)
+        if tape is not None:
+            _check_backward_call(self, None, xn.shape[-1], self.net[0].out_features)
+            tape.update(xn=xn, hdrop=None, drops=[])
         if ph > 0 or drops:
             w1, b1, w2, b2 = self.wt("w1", self.net[0]), _f(self.net[0].bias), self.wt("w2", self.net[3]), _f(self.net[3].bias)
-            h = dropout_(ops.linear(xn, w1, b1, act=L.ACT_RELU), ph)
-            add_dropped(x_res, lambda tmp: ops.linear(h, w2, b2, out=tmp, residual=tmp), drops)
+            h = ops.linear(xn, w1, b1, act=L.ACT_RELU)
+            if tape is not None:
+                tape["hdrop"] = _dropout_rec(h, ph)
+            else:
+                dropout_(h, ph)
+            add_dropped(x_res, lambda tmp: ops.linear(h, w2, b2, out=tmp, residual=tmp), drops,
+                        tape["drops"] if tape is not None else None)
             return None
         if ops.ffn_fused_applies(xn, x_res, self.net[0].in_features, self.net[0].out_features):
             # one launch, hidden activations on chip (csrc/ffn.hip); the weights are packed once per module
@@ -419,7 +435,36 @@ class FeedForward(RFModule):
         h = ops.linear(xn, w1, b1, act=L.ACT_RELU)
         return ops.linear_residual_ln(h, w2, b2, x_res, next_ln)
 
+    def _backward(self, tape, g):
+        """g: fp32 gradient of the block's output (overwritten).  The hidden pre-activation is recomputed from the saved input
+        (the fused forward never writes it).  Returns (fp32 gradient of xn, {param: grad})."""
+        xn = tape["xn"]
+        D = xn.shape[-1]
+        R = xn.numel() // D
+        l1, l2 = self.net[0], self.net[3]
+        for rec in tape["drops"]:
+            _replay_dropout(g, rec)
+        x2 = xn.reshape(R, D)
+        g_t = ops.cast(g.reshape(R, D), T())
+        hpre = ops.linear(x2, self.wt("w1", l1), _f(l1.bias), out_dtype=F32)
+        h = ops.linear(x2, self.wt("w1", l1), _f(l1.bias), act=L.ACT_RELU)
+        _replay_dropout(h, tape["hdrop"])
+        dw2, db2 = ops.conv_wgrad(g_t, h, 1, bias=True)
+        gh = ops.linear(g_t, self.wt_input_grad("w2", l2), None, out_dtype=F32, exact=True)
+        dh = ops.relu_dropout_bwd(gh, hpre, T(), tape["hdrop"])
+        dw1, db1 = ops.conv_wgrad(dh, x2, 1, bias=True)
+        dxn = ops.linear(dh, self.wt_input_grad("w1", l1), None, out_dtype=F32, exact=True)
+        return dxn.view(xn.shape), {l1.weight: dw1, l1.bias: db1, l2.weight: dw2, l2.bias: db2}
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd: with grad mode on, forward() records and loss.backward() fills the .grad of both Linears (and of
+        the input, if it requires grad) through the HIP backward kernels.  Stored on this module; returns self."""
+        self._rf_backward = bool(mode)
+        return self
+
     def forward(self, x):
+        if _recording(self):
+            return _FeedForwardFn.apply(self, x, *self.parameters())
         xn = ops.cast(x.contiguous(), T())
         out = ops.zeros(*x.shape, device=x.device, dtype=F32)
         self.apply_residual(xn, out)
@@ -807,6 +852,7 @@ def gaussian_orthogonal_random_matrix(nb_rows, nb_cols, generator=None):
 class PerformerSelfAttention(RFModule):
     """performer_pytorch.SelfAttention as the reference instantiates it (rf.py:313-318, 505-518):
     dim_head=64, nb_features=266, no qkv bias, output bias; softmax-kernel or generalized ReLU features."""
+    _rf_backward = False   # enable_backward (generalized ReLU features only)
 
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.0, generalized_attention=False, **kw):
         super().__init__()
@@ -831,14 +877,21 @@ class PerformerSelfAttention(RFModule):
             return pp.to(T()).contiguous()
         return self.cached(("proj", log2e), make)
 
-    def attend(self, xn, x_res, axis, next_ln=None, seq_group=None, drops=()):
+    def attend(self, xn, x_res, axis, next_ln=None, seq_group=None, drops=(), tape=None):
         """xn: T [B,L1,L2,D] layer-normed input; sequences run along `axis` (1 or 2); x_res (fp32, same shape)
         += to_out(linear attention).  All intermediates are addressed by strides: no transposes.
         Returns next_ln(x_res) when the fused residual+LayerNorm epilogue applies, else None.
         seq_group: a torch.distributed group over which the SEQUENCE axis is sharded (every rank holds a slice of every
         sequence: pair-track row blocks).  Linear attention communicates contexts, not maps: the local
-        k'^T [v | 1] sums are all-reduced (fp32) before the queries are applied (rf.py:505-518 semantics unchanged)."""
+        k'^T [v | 1] sums are all-reduced (fp32) before the queries are applied (rf.py:505-518 semantics unchanged).
+        tape: a dict that receives what _backward needs (xn, the axis, the output dropout's records); the kernels are the same."""
         B, L1, L2, D = xn.shape
+        if tape is not None:
+            _check_backward_call(self, seq_group, D)
+            if not self.generalized:
+                raise NotImplementedError("PerformerSelfAttention: the backward pass covers the generalized (ReLU) feature map only")
+            tape.update(xn=xn, axis=axis, drops=[])
+        recs = tape["drops"] if tape is not None else None
         H, dh, inner = self.heads, self.dim_head, self.inner
         dev = xn.device
         Ls, Lo = (L1, L2) if axis == 1 else (L2, L1)
@@ -901,7 +954,7 @@ class PerformerSelfAttention(RFModule):
                 qkv = ops.linear(xn, wqkv, bqkv)
                 ops.favor_attention(qkv, pcf, o, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
                                     0, inner, 2 * inner, B, Lo, H, Ls, dh, m, not gen, eps)
-            return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+            return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
         qk = ops.linear(xn, self.wcat("qk", [self.to_q, self.to_k]), None)  # [R, 2*inner]
         # q' [B,Lo,H,Ls,M_PAD]
         dq = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=T())
@@ -953,10 +1006,138 @@ class PerformerSelfAttention(RFModule):
                  c_bs=(RB * H * VT_ROWS, so * H * VT_ROWS, VT_ROWS), c_row=(0, 0, ss * H * VT_ROWS))
         o = torch.empty(R, inner, device=dev, dtype=T())
         ops.linattn_normalize(num, VT_ROWS, o, dh, R * H, dh)
-        return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+        return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
+
+    def _backward(self, tape, g):
+        """g: fp32 [B, L1, L2, D] gradient of what attend() added to x_res (overwritten).  q|k|v, the features, the context and
+        the numerator are rebuilt from the saved xn on the unfused chain (whichever forward path ran).  Per sequence, with
+        phi = relu(z) + eps, C = phi_k^T [v | 1], N = phi_q C, out = N[:, :64] / N[:, 64]:
+            dN = normalize_bwd(N, d out);  dphi_q = dN C^T;  dC = phi_q^T dN;  dphi_k = [v | 1] dC^T;  dv = phi_k dC[:, :64]
+            dq = (dphi_q * 1[z_q > 0]) P,  dk = (dphi_k * 1[z_k > 0]) P
+        The fp16 mode's context scale s = 2^-ceil(log2 Ls) is carried as in the forward: N and C hold s N, s C, so dN comes out
+        as dN / s and dC = s phi_q^T (dN / s).  Returns (fp32 gradient of xn, {param: grad})."""
+        xn, axis = tape["xn"], tape["axis"]
+        B, L1, L2, D = xn.shape
+        H, dh, inner = self.heads, self.dim_head, self.inner
+        dev = xn.device
+        Ls, Lo = (L1, L2) if axis == 1 else (L2, L1)
+        ss, so = (L2, 1) if axis == 1 else (1, L2)
+        RB = L1 * L2
+        R = B * RB
+        W2, W3 = 2 * inner, 3 * inner
+        S = B * Lo * H
+        V = VT_ROWS
+        m = self.fast_attention.projection_matrix.shape[0]
+        pc = self.proj_scaled()
+        pct = self.cached(("proj_t",), lambda: self.proj_scaled().t().contiguous())   # P^T [dh, M_PAD]
+        cs = 2.0 ** -math.ceil(math.log2(max(Ls, 1))) if T() == torch.float16 else 1.0
+        for rec in tape["drops"]:
+            _replay_dropout(g, rec)
+        g_t = ops.cast(g.reshape(R, D), T())
+        x2 = xn.reshape(R, D)
+
+        # ---- the forward's unfused chain, with the extra layouts the products below contract over
+        qk = ops.linear(x2, self.wcat("qk", [self.to_q, self.to_k]), None)   # [R, 2 inner]
+        seq_rows = dict(batch=(B, Lo, 1), a_bs=(RB * W2, so * W2, 0), a_row=(H, ss * W2, dh),
+                        c_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, 0), c_row=(H, M_PAD, Ls * M_PAD))
+
+        def feats(off, act, dtype):   # [B, Lo, H, Ls, M_PAD]: phi (act RELU_EPS) or the fp32 pre-activation z (act NONE)
+            out = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=dtype)
+            ops.gemm(qk, pc, out, Ls * H, M_PAD, dh, a_off=off, act=act, act_nvalid=m, act_eps=1e-3, **seq_rows)
+            return out
+
+        def feats_t(off):             # phi^T [B, Lo, H, M_PAD, Ls]
+            out = torch.empty(B, Lo, H, M_PAD, Ls, device=dev, dtype=T())
+            ops.gemm(pc, qk, out, M_PAD, Ls, dh, batch=(B, Lo, H), b_off=off, b_bs=(RB * W2, so * W2, dh), b_row=(0, 0, ss * W2),
+                     c_bs=(Lo * H * M_PAD * Ls, H * M_PAD * Ls, M_PAD * Ls), c_row=(0, 0, Ls),
+                     act=L.ACT_RELU_EPS, act_nvalid=-m, act_eps=1e-3)
+            return out
+
+        zq, zk = feats(0, L.ACT_NONE, F32), feats(inner, L.ACT_NONE, F32)
+        phq, phk = feats(0, L.ACT_RELU_EPS, T()), feats(inner, L.ACT_RELU_EPS, T())
+        phq_t, kt = feats_t(0), feats_t(inner)
+        vt = ops.zeros(B, Lo, H, V, Ls, device=dev, dtype=T())
+        ones_row = ops.fill(torch.empty(B * Lo * H, Ls, device=dev, dtype=T()), 1.0)
+        ops.copy4d(ones_row, (0, 0, Ls, 1), vt, (0, 0, V * Ls, 1), (1, 1, B * Lo * H, Ls), y_off=dh * Ls)
+        ops.gemm(self.wt("v", self.to_v), xn, vt, inner, Ls, D, batch=(B, Lo, 1), b_bs=(RB * D, so * D, 0), b_row=(0, 0, ss * D),
+                 c_bs=(Lo * H * V * Ls, H * V * Ls, 0), c_row=(dh, V * Ls, Ls))
+        v1 = torch.empty(R * H, V, device=dev, dtype=T())   # [v | 1 | 0] rows in the numerator's row layout
+        self._seq_transpose(vt, v1, B, Lo, H, Ls, so, ss, to_rows=True)
+        per_seq = lambda r, c: dict(batch=(S, 1, 1), a_bs=(r, 0, 0), b_bs=(c, 0, 0))   # noqa: E731
+        ctx = torch.empty(S, V, M_PAD, device=dev, dtype=T())   # C^T (e-major), as the forward
+        ops.gemm(vt, kt, ctx, V, M_PAD, Ls, c_bs=(V * M_PAD, 0, 0), alpha=cs, **per_seq(V * Ls, M_PAD * Ls))
+        cj = torch.empty(S, M_PAD, V, device=dev, dtype=T())    # C (feature-major)
+        ops.gemm(kt, vt, cj, M_PAD, V, Ls, c_bs=(M_PAD * V, 0, 0), alpha=cs, **per_seq(M_PAD * Ls, V * Ls))
+        num_rows = dict(batch=(B, Lo, H), a_bs=(RB * H * V, so * H * V, V), a_row=(0, 0, ss * H * V))
+        num = torch.empty(R * H, V, device=dev, dtype=F32)
+        ops.gemm(phq, ctx, num, Ls, V, M_PAD, batch=(B, Lo, H),
+                 a_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, Ls * M_PAD), a_row=(0, 0, M_PAD),
+                 b_bs=(Lo * H * V * M_PAD, H * V * M_PAD, V * M_PAD),
+                 c_bs=(RB * H * V, so * H * V, V), c_row=(0, 0, ss * H * V))
+        o = torch.empty(R, inner, device=dev, dtype=T())
+        ops.linattn_normalize(num, V, o, dh, R * H, dh)
+
+        # ---- output projection
+        dwo, dbo = ops.conv_wgrad(g_t, o, 1, bias=True)
+        do = ops.linear(g_t, self.wt_input_grad("o", self.to_out), None, out_dtype=F32, exact=True)   # [R, inner]
+        # ---- linear attention
+        dn = torch.empty(R * H, V, device=dev, dtype=T())
+        ops.linattn_normalize_bwd(num, V, do, dh, dn, V, R * H, dh)
+        dn_t = torch.empty(B, Lo, H, V, Ls, device=dev, dtype=T())
+        self._seq_transpose(dn_t, dn, B, Lo, H, Ls, so, ss, to_rows=False)
+        dc = torch.empty(S, M_PAD, V, device=dev, dtype=T())     # dC (feature-major)
+        ops.gemm(phq_t, dn_t, dc, M_PAD, V, Ls, c_bs=(M_PAD * V, 0, 0), alpha=cs, **per_seq(M_PAD * Ls, V * Ls))
+        dc_t = torch.empty(S, V, M_PAD, device=dev, dtype=T())   # dC^T (e-major)
+        ops.gemm(dn_t, phq_t, dc_t, V, M_PAD, Ls, c_bs=(V * M_PAD, 0, 0), alpha=cs, **per_seq(V * Ls, M_PAD * Ls))
+        feat_c = dict(c_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, Ls * M_PAD))
+        dphq = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=F32)
+        ops.gemm(dn, cj, dphq, Ls, M_PAD, V, b_bs=(Lo * H * M_PAD * V, H * M_PAD * V, M_PAD * V), **num_rows, **feat_c)
+        dphk = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=F32)
+        ops.gemm(v1, dc, dphk, Ls, M_PAD, V, b_bs=(Lo * H * M_PAD * V, H * M_PAD * V, M_PAD * V), **num_rows, **feat_c)
+        dzq = ops.relu_feature_bwd(dphq, zq, m, T())
+        dzk = ops.relu_feature_bwd(dphk, zk, m, T())
+        del dphq, dphk, zq, zk
+        # ---- dq | dk | dv straight into the q|k|v projection's layout [R, 3 inner]
+        dqkv = torch.empty(R, W3, device=dev, dtype=T())
+        qkv_c = dict(batch=(B, Lo, H), c_bs=(RB * W3, so * W3, dh), c_row=(0, 0, ss * W3))
+        feat_a = dict(a_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, Ls * M_PAD))
+        ops.gemm(dzq, pct, dqkv, Ls, dh, M_PAD, **feat_a, **qkv_c)
+        ops.gemm(dzk, pct, dqkv, Ls, dh, M_PAD, c_off=inner, **feat_a, **qkv_c)
+        ops.gemm(phk, dc_t, dqkv, Ls, dh, M_PAD, c_off=2 * inner, b_bs=(Lo * H * V * M_PAD, H * V * M_PAD, V * M_PAD),
+                 **feat_a, **qkv_c)
+        dw, _ = ops.conv_wgrad(dqkv, x2, 1)   # [3 inner, D]: to_q | to_k | to_v
+        wqkv_t = self.cached(("wqkv_input_grad",), lambda: torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(),
+                                                                      self.to_v.weight.detach()], 0).t().to(T()).contiguous())
+        dxn = ops.linear(dqkv, wqkv_t, None, out_dtype=F32, exact=True)
+        return dxn.view(xn.shape), {self.to_q.weight: dw[:inner], self.to_k.weight: dw[inner:W2], self.to_v.weight: dw[W2:],
+                                    self.to_out.weight: dwo, self.to_out.bias: dbo}
+
+    @staticmethod
+    def _seq_transpose(seq_major, rows, B, Lo, H, Ls, so, ss, to_rows):
+        """[B, Lo, H, 80, Ls] (sequence index innermost) <-> [B, L1, L2, H, 80] (the numerator's rows), one copy per sample."""
+        V = VT_ROWS
+        rs = (so * H * V, ss * H * V, V, 1)          # (o, n, h, e) in the row layout, past the sample offset
+        ts = (H * V * Ls, 1, V * Ls, Ls)              # (o, n, h, e) in the sequence-major layout
+        for b in range(B):
+            ro, to = b * Lo * Ls * H * V, b * Lo * H * V * Ls
+            if to_rows:
+                ops.copy4d(seq_major, ts, rows, rs, (Lo, Ls, H, V), x_off=to, y_off=ro)
+            else:
+                ops.copy4d(rows, rs, seq_major, ts, (Lo, Ls, H, V), x_off=ro, y_off=to)
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd (generalized ReLU feature map only: the softmax-kernel Performer of the MSA track raises
+        NotImplementedError): with grad mode on, forward() records and loss.backward() fills the .grad of to_q / to_k / to_v,
+        to_out (and of the input, if it requires grad); projection_matrix is a buffer.  Stored on this module; returns self."""
+        if mode and not self.generalized:
+            raise NotImplementedError("PerformerSelfAttention: the backward pass covers the generalized (ReLU) feature map only")
+        self._rf_backward = bool(mode)
+        return self
 
     def forward(self, x):
         """x [S, n, dim] -> [S, n, dim] (library call surface)."""
+        if _recording(self):
+            return _PerformerFn.apply(self, x, *self.parameters())
         S_, n, D = x.shape
         xn = ops.cast(x.contiguous(), T()).view(1, S_, n, D)
         out = ops.zeros(1, S_, n, D, device=x.device, dtype=F32)
@@ -1498,11 +1679,88 @@ class _HeadFn(torch.autograd.Function):
         return (None, dpair) + _param_grads(mod, grads, s)
 
 
+class _PerformerFn(torch.autograd.Function):
+    """PerformerSelfAttention.forward with enable_backward ([S, n, dim] in / out)."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        S_, n, D = x.shape
+        xn = ops.cast(x.contiguous(), T()).view(1, S_, n, D)
+        out = ops.zeros(1, S_, n, D, device=x.device, dtype=F32)
+        tape = {}
+        mod.attend(xn, out, axis=2, drops=(mod.p_dropout,) if mod.training else (), tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return out.view(S_, n, D)
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        s = _grad_scale([g.float().contiguous()])
+        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, s).view(ctx.tape["xn"].shape))
+        ctx.tape = None
+        _unscale([dx], s)
+        return (None, dx.view(g.shape) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
+
+
+class _FeedForwardFn(torch.autograd.Function):
+    """FeedForward.forward with enable_backward."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        xn = ops.cast(x.contiguous(), T())
+        out = ops.zeros(*x.shape, device=x.device, dtype=F32)
+        tape = {}
+        mod.apply_residual(xn, out, tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        s = _grad_scale([g.float().contiguous()])
+        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, s))
+        ctx.tape = None
+        _unscale([dx], s)
+        return (None, dx.view(g.shape) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
+
+
+class _AxialFn(torch.autograd.Function):
+    """PairUpdateWithAxialAttentionLayer / PairUpdateWithAxialAttention .forward with enable_backward (fp32 [B, L, L, d_pair])."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        x = fresh_f32(x)
+        tape = {}
+        mod.run(x, tape=tape)
+        ctx.mod, ctx.tape = mod, tape
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        mod = ctx.mod
+        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, 1.0))
+        ctx.tape = None
+        return (None, dx if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, 1.0)
+
+
+def _pre_norm_residual_bwd(g, sub_backward, sub_tape, x_in, lnm, grads):
+    """Backward of x += f(LayerNorm(x)) for the gradient g of the updated x (fp32, accumulated in place): f's backward runs on
+    a copy of g brought to the fp16 mode's power-of-two scale, the LayerNorm's on the saved fp32 input."""
+    s = _grad_scale([g])
+    dxn, gr = sub_backward(sub_tape, _scaled_copy(g, s))
+    dx, dgamma, dbeta = ops.layernorm_bwd(x_in, dxn, _f(lnm.weight), eps=lnm.eps)
+    gr.update({lnm.weight: dgamma, lnm.bias: dbeta})
+    _unscale([dx] + list(gr.values()), s)
+    ops.axpby(g, 1.0, dx, 1.0, g)
+    grads.update(gr)
+
+
 # ================================================================================================
 # pair axial attention
 # ================================================================================================
 class PairUpdateWithAxialAttentionLayer(RFModule):
     """rf.py:501-528.  RowWise: sequences along dim 1 (i) for fixed j; ColWise: along dim 2 (rf.py:31-54)."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, d_pair, d_ff, n_heads, p_dropout, performer_kws):
         super().__init__()
@@ -1518,12 +1776,20 @@ class PairUpdateWithAxialAttentionLayer(RFModule):
             Residual(nn.Sequential(LayerNorm(d_pair), self.ff)),
         )
 
-    def run(self, x, xn=None, next_ln=None, row_group=None):
+    def run(self, x, xn=None, next_ln=None, row_group=None, tape=None):
         """x fp32 in place; xn = layer[0] pre-norm of x if already produced; returns next_ln(x) or None.
         row_group: x holds a block of ROWS (dim 1) of the pair tensor, the other row blocks live on the other ranks of this
         torch.distributed group (shard.pair_axial_layer_row_sharded): the RowWise attention all-reduces its contexts, the
-        ColWise attention and the feed-forward are local."""
+        ColWise attention and the feed-forward are local.
+        tape: a dict that receives what _backward needs (an fp32 copy of x in front of each sub-layer -- x is updated in place
+        -- and the sub-layers' tapes); the kernels and numbers are those of the plain call."""
         l0, l1, l2 = self.layer[0].fn[0], self.layer[1].fn[0], self.layer[2].fn[0]
+        if tape is not None:
+            _check_backward_call(self, row_group, x.shape[-1])
+            tape.update(row={}, col={}, ff={})
+        elif row_group is not None and _recording(self):
+            raise NotImplementedError("PairUpdateWithAxialAttentionLayer: the backward pass does not support row-sharded calls")
+        snap = (lambda k: tape.__setitem__(k, _copy(x))) if tape is not None else (lambda k: None)
         if row_group is not None and RT.rowshard_attention == "transpose":
             # the direction that crosses the row blocks, on the TRANSPOSED blocks: two transposing exchanges of the fp32 stream
             # (1/world of the tensor per rank each) instead of the all-reduce of the contexts (0.57 GB per rank at L = 1024 whatever
@@ -1536,16 +1802,42 @@ class PairUpdateWithAxialAttentionLayer(RFModule):
         else:
             if xn is None:
                 xn = ln(l0, x)
+            snap("x0")
             xn = self.row_attn.attend(xn, x, axis=1, next_ln=l1, seq_group=row_group,
-                                      drops=(self.row_attn.p_dropout,) if self.training else ())
+                                      drops=(self.row_attn.p_dropout,) if self.training else (),
+                                      tape=tape["row"] if tape is not None else None)
         if xn is None:
             xn = ln(l1, x)
-        xn = self.col_attn.attend(xn, x, axis=2, next_ln=l2, drops=(self.col_attn.p_dropout,) if self.training else ())
+        snap("x1")
+        xn = self.col_attn.attend(xn, x, axis=2, next_ln=l2, drops=(self.col_attn.p_dropout,) if self.training else (),
+                                  tape=tape["col"] if tape is not None else None)
         if xn is None:
             xn = ln(l2, x)
-        return self.ff.apply_residual(xn, x, next_ln)   # (its hidden dropout, rf.py:519, is the FeedForward's own)
+        snap("x2")
+        # (its hidden dropout, rf.py:519, is the FeedForward's own)
+        return self.ff.apply_residual(xn, x, next_ln, tape=tape["ff"] if tape is not None else None)
+
+    def _backward(self, tape, g):
+        """g: fp32 gradient of the layer's output (overwritten).  Returns (fp32 gradient of its input, {param: grad})."""
+        grads = {}
+        _pre_norm_residual_bwd(g, self.ff._backward, tape["ff"], tape["x2"], self.layer[2].fn[0], grads)
+        _pre_norm_residual_bwd(g, self.col_attn._backward, tape["col"], tape["x1"], self.layer[1].fn[0], grads)
+        _pre_norm_residual_bwd(g, self.row_attn._backward, tape["row"], tape["x0"], self.layer[0].fn[0], grads)
+        return g, grads
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd for the layer, its two Performers and its FeedForward: with grad mode on, forward() records and
+        loss.backward() fills the .grad of every parameter (and of the input, if it requires grad) through the HIP backward
+        kernels; in train() mode the backward replays the forward's dropout masks.  Stored on the modules; returns self."""
+        self._rf_backward = bool(mode)
+        self.row_attn.enable_backward(mode)
+        self.col_attn.enable_backward(mode)
+        self.ff.enable_backward(mode)
+        return self
 
     def forward(self, x):
+        if _recording(self):
+            return _AxialFn.apply(self, x, *self.parameters())
         x = fresh_f32(x)
         self.run(x)
         return x
@@ -1553,19 +1845,44 @@ class PairUpdateWithAxialAttentionLayer(RFModule):
 
 class PairUpdateWithAxialAttention(RFModule):
     """rf.py:531-547."""
+    _rf_backward = False   # enable_backward
 
     def __init__(self, d_pair, d_ff, n_heads, p_dropout, n_encoder_layers, performer_kws={}):
         super().__init__()
         self.layers = nn.ModuleList([PairUpdateWithAxialAttentionLayer(d_pair, d_ff, n_heads, p_dropout, performer_kws)
                                      for _ in range(n_encoder_layers)])
 
-    def run(self, x, row_group=None):
+    def run(self, x, row_group=None, tape=None):
+        """x fp32 in place.  tape: a dict that receives the layers' tapes (see PairUpdateWithAxialAttentionLayer.run)."""
+        if tape is not None:
+            _check_backward_call(self, row_group, x.shape[-1])
+            tape["layers"] = [{} for _ in self.layers]
+        elif row_group is not None and _recording(self):
+            raise NotImplementedError("PairUpdateWithAxialAttention: the backward pass does not support row-sharded calls")
         xn = None
         for i, layer in enumerate(self.layers):
             nxt = self.layers[i + 1].layer[0].fn[0] if i + 1 < len(self.layers) else None
-            xn = layer.run(x, xn=xn, next_ln=nxt, row_group=row_group)
+            xn = layer.run(x, xn=xn, next_ln=nxt, row_group=row_group, tape=tape["layers"][i] if tape is not None else None)
+
+    def _backward(self, tape, g):
+        grads = {}
+        for i in reversed(range(len(self.layers))):
+            g, gr = self.layers[i]._backward(tape["layers"][i], g)
+            grads.update(gr)
+        return g, grads
+
+    def enable_backward(self, mode=True):
+        """Opt in to autograd for the stack and every layer below it (see PairUpdateWithAxialAttentionLayer.enable_backward).
+        Inside RoseTTAFold.forward only the final block's stack records, and only together with the prediction head.
+        Returns self."""
+        self._rf_backward = bool(mode)
+        for layer in self.layers:
+            layer.enable_backward(mode)
+        return self
 
     def forward(self, x):
+        if _recording(self):
+            return _AxialFn.apply(self, x, *self.parameters())
         x = fresh_f32(x)
         self.run(x)
         return x

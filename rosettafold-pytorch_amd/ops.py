@@ -484,6 +484,46 @@ def absmax(xs):
     return max(out.tolist())
 
 
+def linattn_normalize_bwd(num, num_ld, g, g_ld, dnum, dnum_ld, rows, dh):
+    """Backward of linattn_normalize (rf_linattn_normalize_bwd): num fp32 rows (column dh = the denominator), g fp32 gradient of
+    the normalised rows; writes dnum (fp32 / the 16-bit type): g / den in columns < dh, -sum g out / den in column dh, zeros up
+    to dnum_ld."""
+    _need_cuda(num, g, dnum)
+    if num.dtype != F32 or g.dtype != F32:
+        raise TypeError("linattn_normalize_bwd: num and g must be fp32")
+    check(lib.rf_linattn_normalize_bwd(ptr(num), int(num_ld), ptr(g), int(g_ld), ptr(dnum), dcode(dnum.dtype), int(dnum_ld), int(rows),
+                                       int(dh), stream()), "rf_linattn_normalize_bwd")
+    return dnum
+
+
+def relu_feature_bwd(dphi, z, nvalid, out_dtype):
+    """Backward of the ReLU feature map relu(z) + eps (rf_relu_feature_bwd): dphi, z contiguous fp32 [..., ld] (z the fp32
+    pre-activation); returns dphi * 1[z > 0] in columns < nvalid, 0 beyond, as out_dtype."""
+    _need_cuda(dphi, z)
+    if dphi.dtype != F32 or z.dtype != F32 or dphi.shape != z.shape or not (dphi.is_contiguous() and z.is_contiguous()):
+        raise ValueError("relu_feature_bwd: contiguous fp32 dphi and z of one shape")
+    ld = dphi.shape[-1]
+    dz = torch.empty(dphi.shape, device=dphi.device, dtype=out_dtype)
+    check(lib.rf_relu_feature_bwd(ptr(dphi), ptr(z), ptr(dz), dcode(out_dtype), dphi.numel() // ld, ld, int(nvalid), stream()),
+          "rf_relu_feature_bwd")
+    return dz
+
+
+def relu_dropout_bwd(g, hpre, out_dtype, drop=None):
+    """Backward of dropout(relu(hpre)) (rf_relu_dropout_bwd): g, hpre contiguous fp32 of one shape; drop = (p, seed, offset) of
+    the forward's rf_dropout mask or None.  Returns g * 1[hpre > 0] (* mask / (1 - p)) as out_dtype."""
+    _need_cuda(g, hpre)
+    if g.dtype != F32 or hpre.dtype != F32 or g.shape != hpre.shape or not (g.is_contiguous() and hpre.is_contiguous()):
+        raise ValueError("relu_dropout_bwd: contiguous fp32 g and hpre of one shape")
+    p, seed, off = drop if drop is not None else (0.0, 0, 0)
+    dh = torch.empty(g.shape, device=g.device, dtype=out_dtype)
+    if p >= 1.0:
+        return fill(dh, 0.0)
+    check(lib.rf_relu_dropout_bwd(ptr(g), ptr(hpre), ptr(dh), dcode(out_dtype), float(p), int(seed), int(off), g.numel(), stream()),
+          "rf_relu_dropout_bwd")
+    return dh
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through

@@ -515,11 +515,21 @@ class FinalBlock(TwoTrackBlock):
                                                                         n_neighbors=n_neighbors, p_dropout=p_dropout)
         self.plddt_head = Linear(d_state, 1)
 
-    def run3(self, msa, pair, xyz, seq_onehot, aa_idx, monotonic=True, row_group=None):
-        pair = self.run(msa, pair, row_group)
+    def run3(self, msa, pair, xyz, seq_onehot, aa_idx, monotonic=True, row_group=None, axial_grad=False):
+        """axial_grad: the pair axial update records (its forward() under grad mode, enable_backward): the returned pair takes
+        part in autograd; the MSA update and the structure track read a detached copy (the same numbers as the plain run)."""
+        if axial_grad:
+            att = self.msa_update_using_self_att.run(msa)
+            pair = self.pair_update_with_msa.run(msa, pair, att)
+            with torch.enable_grad():
+                pair_rec = self.pair_update_with_axial_attention(pair)
+            pair = pair_rec.detach()
+            self.msa_update_with_pair.run(msa, pair)
+        else:
+            pair = self.run(msa, pair, row_group)
         state, xyz = self.coord_update_with_msa_and_pair.run(xyz, msa, _whole_pair(pair, row_group), aa_idx, seq_onehot, monotonic)
         plddt = ops.linear(state.contiguous(), self.plddt_head.weight.detach(), _f(self.plddt_head.bias), out_dtype=F32, exact=True)
-        return msa, pair, xyz, plddt[..., 0]
+        return msa, (pair_rec if axial_grad else pair), xyz, plddt[..., 0]
 
     def forward(self, msa, pair, xyz, seq_onehot, aa_idx):
         msa = fresh_f32(msa)
@@ -555,8 +565,16 @@ class RoseTTAFold(RFModule):
 
     def forward(self, msa, seq, aa_idx):
         """The inference forward, under no_grad.  With prediction_head.enable_backward() and the caller's grad mode on, the trunk
-        still runs under no_grad and only the head records: the logits take part in autograd (xyz and plddt do not)."""
+        still runs under no_grad and only the head records: the logits take part in autograd (xyz and plddt do not).
+        With final_block.pair_update_with_axial_attention.enable_backward() as well, that update records too (the trunk runs
+        under no_grad up to its input; its output feeds the recording head, a detached copy the MSA update and the structure
+        track), so the gradient reaches its parameters.  It needs the head: enabling it alone raises ValueError.  The axial
+        updates of the two-track and three-track blocks record only when called directly, never inside this forward."""
         head_grad = torch.is_grad_enabled() and getattr(self.prediction_head, "_rf_backward", False)
+        axial_grad = torch.is_grad_enabled() and getattr(self.final_block.pair_update_with_axial_attention, "_rf_backward", False)
+        if axial_grad and not head_grad:
+            raise ValueError("final_block.pair_update_with_axial_attention has backward enabled but prediction_head does not: no "
+                             "gradient could reach it (enable_backward() on the head too)")
         with torch.no_grad():
             if not msa.is_cuda:
                 raise L.RfmiError("RoseTTAFold (MI355X build) needs device tensors; there is no CPU fallback")
@@ -570,7 +588,7 @@ class RoseTTAFold(RFModule):
                     out = self.forward_validated(msa, seq, aa_idx, mono)
                     check_edge_capacity()
                     return out
-                p, xyz, plddt = self._trunk(msa, seq, aa_idx, mono)
+                p, xyz, plddt = self._trunk(msa, seq, aa_idx, mono, axial_grad=axial_grad)
                 check_edge_capacity()
         with torch.cuda.device(msa.device), torch.enable_grad():
             logits = self.prediction_head(p)
@@ -589,8 +607,9 @@ class RoseTTAFold(RFModule):
         return logits, xyz, plddt
 
     @torch.no_grad()
-    def _trunk(self, msa, seq, aa_idx, mono, row_group=None):
-        """forward_validated up to the prediction head: returns (pair or this rank's rows of it, xyz, plddt)."""
+    def _trunk(self, msa, seq, aa_idx, mono, row_group=None, axial_grad=False):
+        """forward_validated up to the prediction head: returns (pair or this rank's rows of it, xyz, plddt).  axial_grad: the
+        final block's pair axial update records (FinalBlock.run3)."""
         with torch.cuda.device(msa.device):
             m = self.msa_emb.run(msa, aa_idx)
             p = self.pair_emb.run(seq, aa_idx)
@@ -603,7 +622,7 @@ class RoseTTAFold(RFModule):
             xyz = self.initial_coord_generation_with_msa_and_pair.run(m, _whole_pair(p, row_group), onehot, aa_idx)
             for blk in self.three_track_blocks:
                 m, p, xyz = blk.run3(m, p, xyz, onehot, aa_idx, mono, row_group)
-            m, p, xyz, plddt = self.final_block.run3(m, p, xyz, onehot, aa_idx, mono, row_group)
+            m, p, xyz, plddt = self.final_block.run3(m, p, xyz, onehot, aa_idx, mono, row_group, axial_grad=axial_grad)
         return p, xyz, plddt
 
 
