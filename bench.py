@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- residues/s of the RoseTTAFold forward path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|1|4|5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|1|4|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one forward of the full model (config 2 = BASELINE.json configs[1]: B=4 MSAs of N=128 x L=256 per GPU,
 d_msa=384, d_pair=288, 8 two-track + 4 three-track + final block, 4 encoder layers) on synthetic token inputs already
 resident in HBM, random-init weights.  Independent MSAs shard across ranks (one process per GPU); the only collective is
-the gather of the results to rank 0 (RCCL), inside the timed region.  Rank 0 prints ONE JSON line.  Extra legs on rank 0
-at N=1:
+the gather of the results to rank 0 (RCCL), inside the timed region.  Rank 0 prints ONE JSON line.  A plain run does only
+what that line's headline needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.  With --full, rank 0
+adds legs at N=1 after the timed steps (each can be left out with its --no-* option):
   * roofline: the dominant kernel family timed live with HIP events around every rf_gemm launch of one extra profiled
     step (the library reports which kernel family each launch took: rf_gemm_last_family); achieved = algorithmic FLOPs of
     those launches / their time.  `traffic` comes from the PMC file of THIS tree (profiles/r04_traffic_pmc.json carries a
@@ -20,8 +21,8 @@ at N=1:
   * cpu_baseline: the CPU oracle (oracle/rf_oracle.py, pinned to the reference's golden vectors) on the host cores: one
     layer of each kind at the bench shapes (B=1), warm-up + best of 3, scaled by the layer counts.
 Other workloads: --config 4 (BASELINE.json configs[3]: B=1, N=64, L=1024) and --config 5 (configs[4]: the SE(3) structure
-module alone, B=8, L=256, k=128) print a JSON line of the same form with their own `roofline` (dominant rf_gemm family of
-that workload, PMC files profiles/r04_config{4,5}_*); no parity / cpu legs.
+module alone, B=8, L=256, k=128) print a JSON line of the same form; with --full it carries their own `roofline` (dominant
+rf_gemm family of that workload, PMC files profiles/r04_config{4,5}_*); no parity / cpu legs.
 """
 import argparse
 import hashlib
@@ -361,9 +362,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline, parity and cpu_baseline legs (rank 0, one GPU) and add them "
+                         "to the JSON line; a plain run measures the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out the roofline leg")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: leave out the parity leg")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) | gloo (rehearsal on a 1-GPU box)")
     ap.add_argument("--no-graph", action="store_true", help="issue the forward's launches eagerly instead of replaying one hipGraph")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -504,9 +508,9 @@ def main():
                        "launch": "one hipGraph replay per step (validation + input copy outside the graph)" if used_graph
                        else "eager launches through the C ABI"},
         }
-        full = args.config == 2 and args.dtype == "bf16"
+        headline = args.config == 2 and args.dtype == "bf16"
         pmc_tag = "r04_" if args.config == 2 else f"r04_config{args.config}_"
-        if world == 1 and args.dtype == "bf16" and args.config in (2, 4, 5) and not args.no_roofline:
+        if args.full and world == 1 and args.dtype == "bf16" and args.config in (2, 4, 5) and not args.no_roofline:
             fams, shapes = profile_gemms(eager if args.config != 5 else run)
             name, (secs, flops, n, nbytes) = max(fams.items(), key=lambda kv: kv[1][0])
             traffic, tnote = None, "no PMC collection for this tree (tools/pmc_traffic.py)"
@@ -544,9 +548,9 @@ def main():
                                "families": {k: {"s": v[0], "tflops": v[1] / max(v[0], 1e-12) / 1e12, "n": v[2],
                                                 "algorithmic_GBps": v[3] / max(v[0], 1e-12) / 1e9}
                                             for k, v in fams.items()}}
-        if world == 1 and full and not args.no_parity:
+        if args.full and world == 1 and headline and not args.no_parity:
             res["parity"] = parity_block(model, inputs, out, R, 1e3 * dt / args.steps, graph=used_graph)
-        if world == 1 and full and not args.no_cpu_baseline:
+        if args.full and world == 1 and headline and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(res), flush=True)
     if dist_on:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-shape launch times of one bench line (roofline.shapes): python tools/shape_probe.py <bench.json> [kernel prefix]"""
+"""Per-shape launch times of one `bench.py --full` line (roofline.shapes): python tools/shape_probe.py <bench.json> [kernel prefix]"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 pre = sys.argv[2] if len(sys.argv) > 2 else ""
