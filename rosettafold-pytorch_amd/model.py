@@ -24,50 +24,15 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .ops import F32
+from .runtime import RT, T, manual_seed, dropout_, _f, fresh_f32  # noqa: F401  (re-exported: model.RT is the one runtime)
+from .backward import (_RecordedFn, _recording, _check_backward_call, _copy, _dropout_rec, _replay_dropout,  # noqa: F401
+                       _grad_scale, _scaled_copy, _unscale, _conv_weight_grad, _param_grads, _pre_norm_residual_bwd,
+                       conv_input_grad_weight, conv3x3_input_grad)
 
 N_IDX, CA_IDX, C_IDX = 0, 1, 2  # rf.py:15
 M_FEAT = 266   # performer nb_features = int(64 * ln 64)
 M_PAD = 288    # padded to a multiple of 32 for the MFMA K loop
 VT_ROWS = 80   # 64 value rows + the ones row (k' sums) padded to a multiple of 16
-
-
-class _Runtime:
-    dtype = torch.bfloat16
-    f32_precision = "highest"  # set_float32_matmul_precision: "high" = split-bf16 GEMMs in the float32 mode
-    # training-mode dropout: masks are Philox4x32-10(train_seed, counter); every dropout call of a forward
-    # takes the next ceil(n / 4) counters, so manual_seed(s) in front of a forward reproduces it bit for bit (csrc/ops.hip)
-    train_seed = 0
-    train_offset = 0
-    cache_epoch = 0  # bumped whenever kernel-ready weight copies are dropped (graph.GraphedForward re-records on a change)
-    # structure-track node input (LayerNorm(msa) -> position-weighted sum, rf.py:789-798) in fp32 also in the 16-bit modes:
-    # the SE(3) stack is discontinuous (GNormBias, kNN, distance bins), so its inputs are not the place to round
-    # (tools/depth_parity.py --struct-lowp measures the difference)
-    struct_inputs_fp32 = True
-    # PredictionHead: remove the per-(sample, channel) mean over the picture from the projected pair tensor before it is rounded
-    # to the 16-bit operand type (PredictionHead.run; RF_HEAD_CENTER=0 restores the plain cast)
-    head_center = bool(int(__import__("os").environ.get("RF_HEAD_CENTER", "1")))
-    # Operand conditioning of the 16-bit modes (csrc/condition.hip; exact algebra): PairUpdateWithMsa's tiled 1-D features and its
-    # first convolution see operands with the per-sample constant removed.  RF_CONDITION=0: the plain form (ablation / probes).
-    condition = bool(int(__import__("os").environ.get("RF_CONDITION", "1")))
-    condition_values = bool(int(__import__("os").environ.get("RF_CONDITION_V", "1")))   # the attention layers' value path (value_conditioning)
-    # SE(3) radial MLPs: last Linear inside the message kernel (csrc/se3.hip: rf_se3_radial_message); RF_SE3_UNFUSED=1 writes the
-    # radial outputs with a K = 32 GEMM and reads them back (round-3 path, kept for A/B timing and as the form for unusual shapes)
-    se3_fused_radial = not bool(int(__import__("os").environ.get("RF_SE3_UNFUSED", "0")))
-    fused_favor = True  # use the fused FAVOR+ kernel when the shape allows (bf16, dim_head 64, seq 128/256)
-    fused_outer_ln = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER_LN", "0")))  # LayerNorm(1024) in the outer-product GEMM epilogue
-    fused_tied = not bool(int(__import__("os").environ.get("RF_NO_FUSED_TIED", "0")))  # tied-attention logits + softmax in one launch
-    fused_outer = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER", "0")))  # outer product -> LN -> Linear in one kernel
-    tied_v2 = not bool(int(__import__("os").environ.get("RF_TIED_V1", "0")))  # head-major q|k|v + collapsed weights + A.V kernel
-    tied_fold_w = not bool(int(__import__("os").environ.get("RF_TIED_NO_FOLD", "0")))  # position weights folded into q by the projection's epilogue
-    # pair-track row blocks (shard.forward_row_sharded): how the attention direction that crosses the blocks is computed --
-    # "transpose" (two transposing exchanges, fused kernel) or "contexts" (all-reduce of the Performer contexts, GEMM chain)
-    rowshard_attention = __import__("os").environ.get("RF_ROWSHARD_ATTENTION", "transpose")
-    head_major_qkv = int(__import__("os").environ.get("RF_HEAD_MAJOR_QKV", "0"))  # 1: every FAVOR+ layer, 2: only where the sequence is the inner row index
-    # Producer -> consumer chains whose intermediate (q|k|v, feed-forward hidden) is larger than this many bytes are run
-    # panel by panel, so the intermediate panel is still in the 256 MB Infinity Cache when its consumer reads it
-    # (tools/mall_chunk_bench.py: projection + FAVOR alone 958 -> 842 us at 200 MB panels; inside the full forward the
-    # step time did not move, 432 vs 437 ms, so it is opt-in: RF_MALL_PANEL_MB=208).  0 disables.
-    mall_panel_bytes = int(__import__("os").environ.get("RF_MALL_PANEL_MB", "0")) << 20
 
 
 def row_panels(rows, bytes_per_row, unit):
@@ -81,9 +46,6 @@ def row_panels(rows, bytes_per_row, unit):
         if units % n == 0 and (rows // n) * bytes_per_row <= cap and (rows // n) >= 16384:
             return rows // n
     return rows
-
-
-RT = _Runtime()
 
 
 def set_compute_dtype(dtype):
@@ -119,30 +81,6 @@ def set_float32_matmul_precision(precision):
 
 def get_float32_matmul_precision():
     return RT.f32_precision
-
-
-def T():
-    return RT.dtype
-
-
-def manual_seed(seed):
-    """Seed of the training-mode dropout masks (model.train(); the inference forward draws nothing).  Like torch.manual_seed:
-    the same seed in front of the same forward gives the same masks; consecutive forwards continue the counter stream."""
-    RT.train_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    RT.train_offset = 0
-
-
-def dropout_(t, p):
-    """In-place nn.Dropout(p) of a training-mode forward on a contiguous fp32 / 16-bit tensor (rf_dropout); identity for p <= 0."""
-    if p is None or p <= 0.0 or t.numel() == 0:
-        return t
-    if p >= 1.0:
-        return ops.fill(t, 0.0)
-    if not t.is_contiguous():
-        raise ValueError("dropout_: contiguous tensors only")
-    off = RT.train_offset
-    RT.train_offset += (t.numel() + 3) // 4
-    return ops.dropout(t, p, RT.train_seed, off)
 
 
 def _p(drop_module):
@@ -286,14 +224,37 @@ class RFModule(nn.Module):
         return self.cached(("bcat", key), lambda: torch.cat([l.bias.detach() for l in lins], 0).float().contiguous())
 
 
-def _f(p):
-    return None if p is None else p.detach()
+class RecordingModule(RFModule):
+    """An RFModule of one input with an opt-in HIP backward pass (the protocol: backward.py).  forward() is `_record(x, None)`;
+    once the module opted in and grad mode is on, it is `_record(x, tape)` inside the one autograd Function."""
+    _rf_backward = False            # enable_backward
+    _rf_scales_own_grads = False    # True: _backward brings its own operands to the fp16 mode's scale (_RecordedFn leaves it at 1)
 
+    def _backward_children(self):
+        """the sub-modules whose backward this module's composes (enable_backward switches them along)"""
+        return ()
 
-def fresh_f32(x):
-    """A new contiguous fp32 copy of x (the public forwards never mutate their inputs)."""
-    y = torch.empty(x.shape, device=x.device, dtype=F32)
-    return ops.axpby(x.detach().contiguous(), 1.0, None, 0.0, y)
+    def enable_backward(self, mode=True):
+        """Opt in to autograd: with grad mode on, forward() records and loss.backward() fills the .grad of every parameter (and
+        of the input, if it requires grad) through the HIP backward kernels; in train() mode the backward replays the forward's
+        dropout masks.  Stored on this module and the sub-modules its class docstring names (no global state); returns self."""
+        self._rf_backward = bool(mode)
+        for child in self._backward_children():
+            child.enable_backward(mode)
+        return self
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        """gs: the output gradients as autograd hands them (any strides), s: the scale to bring them to.  Returns (the input's
+        gradient with s taken off again, in the input's layout, or None; {param: grad} still times s).  This default serves a
+        module whose _record converts no layout."""
+        dx, grads = self._backward(tape, _scaled_copy(gs[0], s))
+        _unscale([dx], s)
+        return dx.view(gs[0].shape), grads
+
+    def forward(self, x):
+        if _recording(self):
+            return _RecordedFn.apply(self, x, *self.parameters())
+        return self._record(x, None)
 
 
 class LayerNorm(nn.LayerNorm):
@@ -387,9 +348,8 @@ class RowWise(nn.Module):
         return out
 
 
-class FeedForward(RFModule):
-    """rf.py:270-281."""
-    _rf_backward = False   # enable_backward
+class FeedForward(RecordingModule):
+    """rf.py:270-281.  enable_backward(): the gradients of both Linears (and of the input)."""
 
     def __init__(self, d_emb, d_ff, p_dropout=0.1):
         super().__init__()
@@ -404,8 +364,8 @@ class FeedForward(RFModule):
         numbers)."""
         ph = _p(self.net[2]) if self.training else 0.0
         drops = tuple(d for d in drops if d and d > 0)
+        _check_backward_call(self, tape, None, xn.shape[-1], self.net[0].out_features)
         if tape is not None:
-            _check_backward_call(self, None, xn.shape[-1], self.net[0].out_features)
             tape.update(xn=xn, hdrop=None, drops=[])
         if ph > 0 or drops:
             w1, b1, w2, b2 = self.wt("w1", self.net[0]), _f(self.net[0].bias), self.wt("w2", self.net[3]), _f(self.net[3].bias)
@@ -456,18 +416,10 @@ class FeedForward(RFModule):
         dxn = ops.linear(dh, self.wt_input_grad("w1", l1), None, out_dtype=F32, exact=True)
         return dxn.view(xn.shape), {l1.weight: dw1, l1.bias: db1, l2.weight: dw2, l2.bias: db2}
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd: with grad mode on, forward() records and loss.backward() fills the .grad of both Linears (and of
-        the input, if it requires grad) through the HIP backward kernels.  Stored on this module; returns self."""
-        self._rf_backward = bool(mode)
-        return self
-
-    def forward(self, x):
-        if _recording(self):
-            return _FeedForwardFn.apply(self, x, *self.parameters())
+    def _record(self, x, tape):
         xn = ops.cast(x.contiguous(), T())
         out = ops.zeros(*x.shape, device=x.device, dtype=F32)
-        self.apply_residual(xn, out)
+        self.apply_residual(xn, out, tape=tape)
         return out
 
 
@@ -849,10 +801,9 @@ def gaussian_orthogonal_random_matrix(nb_rows, nb_cols, generator=None):
     return torch.diag(mult) @ mat
 
 
-class PerformerSelfAttention(RFModule):
+class PerformerSelfAttention(RecordingModule):
     """performer_pytorch.SelfAttention as the reference instantiates it (rf.py:313-318, 505-518):
     dim_head=64, nb_features=266, no qkv bias, output bias; softmax-kernel or generalized ReLU features."""
-    _rf_backward = False   # enable_backward (generalized ReLU features only)
 
     def __init__(self, dim, heads=8, dim_head=64, dropout=0.0, generalized_attention=False, **kw):
         super().__init__()
@@ -886,8 +837,8 @@ class PerformerSelfAttention(RFModule):
         k'^T [v | 1] sums are all-reduced (fp32) before the queries are applied (rf.py:505-518 semantics unchanged).
         tape: a dict that receives what _backward needs (xn, the axis, the output dropout's records); the kernels are the same."""
         B, L1, L2, D = xn.shape
+        _check_backward_call(self, tape, seq_group, D)
         if tape is not None:
-            _check_backward_call(self, seq_group, D)
             if not self.generalized:
                 raise NotImplementedError("PerformerSelfAttention: the backward pass covers the generalized (ReLU) feature map only")
             tape.update(xn=xn, axis=axis, drops=[])
@@ -1131,18 +1082,20 @@ class PerformerSelfAttention(RFModule):
         to_out (and of the input, if it requires grad); projection_matrix is a buffer.  Stored on this module; returns self."""
         if mode and not self.generalized:
             raise NotImplementedError("PerformerSelfAttention: the backward pass covers the generalized (ReLU) feature map only")
-        self._rf_backward = bool(mode)
-        return self
+        return super().enable_backward(mode)
 
-    def forward(self, x):
+    def _record(self, x, tape):
         """x [S, n, dim] -> [S, n, dim] (library call surface)."""
-        if _recording(self):
-            return _PerformerFn.apply(self, x, *self.parameters())
         S_, n, D = x.shape
         xn = ops.cast(x.contiguous(), T()).view(1, S_, n, D)
         out = ops.zeros(1, S_, n, D, device=x.device, dtype=F32)
-        self.attend(xn, out, axis=2, drops=(self.p_dropout,) if self.training else ())
+        self.attend(xn, out, axis=2, drops=(self.p_dropout,) if self.training else (), tape=tape)
         return out.view(S_, n, D)
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        dx, grads = self._backward(tape, _scaled_copy(gs[0], s).view(tape["xn"].shape))
+        _unscale([dx], s)
+        return dx.view(gs[0].shape), grads
 
 
 # ================================================================================================
@@ -1517,250 +1470,13 @@ def conv3x3(mod, key, conv, x, dilation, out_dtype=None):
     return out
 
 
-def conv_input_grad_weight(w):
-    """[Co, Ci, k, k] kernel of a stride-1 "same" convolution -> [Ci, Co, k, k]: its input gradient (any dilation) is the same
-    convolution of the output gradient with the kernel rotated 180 degrees and its in / out channels swapped."""
-    return w.flip(-1, -2).transpose(0, 1)
-
-
-def conv3x3_input_grad(mod, key, conv, dy, dilation, residual=None):
-    """Input gradient of conv3x3 on the forward's implicit-GEMM engine (rf_gemm conv mode, conv288 at C = 288) with the repacked
-    kernel: fp32 NHWC (+ residual, in place when given).  The 16-bit modes write the 16-bit type (what the 288-channel engine
-    writes) and widen it; the fp32 mode writes fp32 with the exact fp32 kernel."""
-    B, Hh, Ww, Co = dy.shape
-    Ci = conv.weight.shape[1]
-    wk = mod.cached(("conv_input_grad", key), lambda: conv_input_grad_weight(conv.weight.detach()).permute(0, 2, 3, 1)
-                    .reshape(Ci, 9 * Co).to(T()).contiguous())
-    if T() == F32:
-        out = residual if residual is not None else torch.empty(B, Hh, Ww, Ci, device=dy.device, dtype=F32)
-        return ops.gemm(dy, wk, out, B * Hh * Ww, Ci, 9 * Co, conv=(B, Hh, Ww, Co, dilation), residual=residual, exact=True)
-    o16 = torch.empty(B, Hh, Ww, Ci, device=dy.device, dtype=T())
-    ops.gemm(dy, wk, o16, B * Hh * Ww, Ci, 9 * Co, conv=(B, Hh, Ww, Co, dilation))
-    if residual is not None:
-        return ops.axpby(residual, 1.0, o16, 1.0, residual)
-    return ops.axpby(o16, 1.0, None, 0.0, torch.empty(o16.shape, device=dy.device, dtype=F32))
-
-
-# ================================================================================================
-# backward of PredictionHead / ResNet / ResBlock2D (opt-in per module: enable_backward)
-# ================================================================================================
-def _recording(mod):
-    """record an autograd graph only when the module opted in AND grad mode is on (requires_grad alone never switches it on)"""
-    return getattr(mod, "_rf_backward", False) and torch.is_grad_enabled()
-
-
-def _check_backward_call(mod, row_group, *channels):
-    if row_group is not None:
-        raise NotImplementedError(f"{type(mod).__name__}: the backward pass does not support row-sharded calls (row_group)")
-    for c in channels:
-        if c % 8:
-            raise ValueError(f"{type(mod).__name__}: the backward pass needs channel counts that are multiples of 8, got {c}")
-
-
-def _copy(t):
-    return ops.axpby(t, 1.0, None, 0.0, torch.empty(t.shape, device=t.device, dtype=t.dtype))
-
-
-def _dropout_rec(t, p):
-    """dropout_(t, p) returning what the backward replays: (p, seed, offset), or None when nothing was dropped."""
-    if p is None or p <= 0.0 or t.numel() == 0:
-        return None
-    rec = (p, RT.train_seed, RT.train_offset)
-    dropout_(t, p)
-    return rec
-
-
-def _replay_dropout(g, rec):
-    """multiply g by the forward's mask / (1 - p) (rf_dropout with the recorded seed and offset), in place"""
-    if rec is None:
-        return g
-    p, seed, off = rec
-    return ops.fill(g, 0.0) if p >= 1.0 else ops.dropout(g, p, seed, off)
-
-
-def _grad_scale(gs):
-    """Power of two that brings max |g| into [1, 2) in the fp16 mode, whose 16-bit gradient operands would underflow for small
-    losses; 1 in the other modes.  Exact: every backward step is linear in the gradient, the scale is undone in fp32."""
-    if RT.dtype != torch.float16:
-        return 1.0
-    m = ops.absmax(gs)
-    if not math.isfinite(m) or m == 0.0:
-        return 1.0
-    return 2.0 ** max(-100, min(100, -math.floor(math.log2(m))))
-
-
-def _scaled_copy(g, s):
-    """fresh contiguous fp32 s * g (autograd may hand in expanded or non-contiguous gradients)"""
-    g = g.float().contiguous()
-    return ops.axpby(g, s, None, 0.0, torch.empty(g.shape, device=g.device, dtype=F32))
-
-
-def _unscale(ts, s):
-    if s != 1.0:
-        for t in ts:
-            if t is not None:
-                ops.axpby(t, 1.0 / s, None, 0.0, t)
-
-
-def _conv_weight_grad(dw, w):
-    """fp32 [Co, 9 * Ci] gradient in the forward's [co][tap][ci] layout -> a contiguous [Co, Ci, 3, 3] like the weight"""
-    Co, Ci = w.shape[0], w.shape[1]
-    out = torch.empty(Co, Ci, 3, 3, device=dw.device, dtype=F32)
-    return ops.copy4d(dw, (9 * Ci, 1, Ci, 1), out, (9 * Ci, 9, 1, 1), (Co, Ci, 9, 1))
-
-
-def _param_grads(mod, grads, s):
-    ps = list(mod.parameters())
-    out = [grads.get(p) for p in ps]
-    _unscale(out, s)
-    return tuple(out)
-
-
-class _BlockFn(torch.autograd.Function):
-    """ResBlock2D.forward with enable_backward (NCHW in / out)."""
-
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        xf = x.float().permute(0, 2, 3, 1).contiguous()
-        tape = {}
-        _, o_f = mod.run(ops.cast(xf, T()), xf, tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return o_f.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        mod = ctx.mod
-        s = _grad_scale([g.float().contiguous()])
-        dx, grads = mod._backward(ctx.tape, _scaled_copy(g.permute(0, 2, 3, 1), s))
-        ctx.tape = None
-        _unscale([dx], s)
-        return (None, dx.permute(0, 3, 1, 2) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
-
-
-class _ResNetFn(torch.autograd.Function):
-    """ResNet.forward with enable_backward (NCHW in / out)."""
-
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        xf = x.float().permute(0, 2, 3, 1).contiguous()
-        tape = {}
-        out = mod.run(ops.cast(xf, T()), tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return out.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        mod = ctx.mod
-        s = _grad_scale([g.float().contiguous()])
-        dx, grads = mod._backward(ctx.tape, _scaled_copy(g.permute(0, 2, 3, 1), s), want_dx=ctx.needs_input_grad[1])
-        ctx.tape = None
-        _unscale([dx], s)
-        return (None, dx.permute(0, 3, 1, 2) if dx is not None else None) + _param_grads(mod, grads, s)
-
-
-_HEADS = ("theta", "phi", "dist", "omega")
-
-
-class _HeadFn(torch.autograd.Function):
-    """PredictionHead.forward with enable_backward: pair fp32 NHWC -> the four logit maps (fp32 NHWC)."""
-
-    @staticmethod
-    def forward(ctx, mod, pair, *params):
-        tape = {}
-        out = mod.run(pair, tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return tuple(out[k] for k in _HEADS)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        mod = ctx.mod
-        dpair, grads, s = mod._backward(ctx.tape, dict(zip(_HEADS, gs)), want_dpair=ctx.needs_input_grad[1])
-        ctx.tape = None
-        return (None, dpair) + _param_grads(mod, grads, s)
-
-
-class _PerformerFn(torch.autograd.Function):
-    """PerformerSelfAttention.forward with enable_backward ([S, n, dim] in / out)."""
-
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        S_, n, D = x.shape
-        xn = ops.cast(x.contiguous(), T()).view(1, S_, n, D)
-        out = ops.zeros(1, S_, n, D, device=x.device, dtype=F32)
-        tape = {}
-        mod.attend(xn, out, axis=2, drops=(mod.p_dropout,) if mod.training else (), tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return out.view(S_, n, D)
-
-    @staticmethod
-    def backward(ctx, g):
-        mod = ctx.mod
-        s = _grad_scale([g.float().contiguous()])
-        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, s).view(ctx.tape["xn"].shape))
-        ctx.tape = None
-        _unscale([dx], s)
-        return (None, dx.view(g.shape) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
-
-
-class _FeedForwardFn(torch.autograd.Function):
-    """FeedForward.forward with enable_backward."""
-
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        xn = ops.cast(x.contiguous(), T())
-        out = ops.zeros(*x.shape, device=x.device, dtype=F32)
-        tape = {}
-        mod.apply_residual(xn, out, tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        mod = ctx.mod
-        s = _grad_scale([g.float().contiguous()])
-        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, s))
-        ctx.tape = None
-        _unscale([dx], s)
-        return (None, dx.view(g.shape) if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
-
-
-class _AxialFn(torch.autograd.Function):
-    """PairUpdateWithAxialAttentionLayer / PairUpdateWithAxialAttention .forward with enable_backward (fp32 [B, L, L, d_pair])."""
-
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        x = fresh_f32(x)
-        tape = {}
-        mod.run(x, tape=tape)
-        ctx.mod, ctx.tape = mod, tape
-        return x
-
-    @staticmethod
-    def backward(ctx, g):
-        mod = ctx.mod
-        dx, grads = mod._backward(ctx.tape, _scaled_copy(g, 1.0))
-        ctx.tape = None
-        return (None, dx if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, 1.0)
-
-
-def _pre_norm_residual_bwd(g, sub_backward, sub_tape, x_in, lnm, grads):
-    """Backward of x += f(LayerNorm(x)) for the gradient g of the updated x (fp32, accumulated in place): f's backward runs on
-    a copy of g brought to the fp16 mode's power-of-two scale, the LayerNorm's on the saved fp32 input."""
-    s = _grad_scale([g])
-    dxn, gr = sub_backward(sub_tape, _scaled_copy(g, s))
-    dx, dgamma, dbeta = ops.layernorm_bwd(x_in, dxn, _f(lnm.weight), eps=lnm.eps)
-    gr.update({lnm.weight: dgamma, lnm.bias: dbeta})
-    _unscale([dx] + list(gr.values()), s)
-    ops.axpby(g, 1.0, dx, 1.0, g)
-    grads.update(gr)
-
-
 # ================================================================================================
 # pair axial attention
 # ================================================================================================
-class PairUpdateWithAxialAttentionLayer(RFModule):
-    """rf.py:501-528.  RowWise: sequences along dim 1 (i) for fixed j; ColWise: along dim 2 (rf.py:31-54)."""
-    _rf_backward = False   # enable_backward
+class PairUpdateWithAxialAttentionLayer(RecordingModule):
+    """rf.py:501-528.  RowWise: sequences along dim 1 (i) for fixed j; ColWise: along dim 2 (rf.py:31-54).
+    enable_backward(): the layer, its two Performers and its FeedForward."""
+    _rf_scales_own_grads = True   # per sub-layer: _pre_norm_residual_bwd
 
     def __init__(self, d_pair, d_ff, n_heads, p_dropout, performer_kws):
         super().__init__()
@@ -1784,11 +1500,9 @@ class PairUpdateWithAxialAttentionLayer(RFModule):
         tape: a dict that receives what _backward needs (an fp32 copy of x in front of each sub-layer -- x is updated in place
         -- and the sub-layers' tapes); the kernels and numbers are those of the plain call."""
         l0, l1, l2 = self.layer[0].fn[0], self.layer[1].fn[0], self.layer[2].fn[0]
+        _check_backward_call(self, tape, row_group, x.shape[-1])
         if tape is not None:
-            _check_backward_call(self, row_group, x.shape[-1])
             tape.update(row={}, col={}, ff={})
-        elif row_group is not None and _recording(self):
-            raise NotImplementedError("PairUpdateWithAxialAttentionLayer: the backward pass does not support row-sharded calls")
         snap = (lambda k: tape.__setitem__(k, _copy(x))) if tape is not None else (lambda k: None)
         if row_group is not None and RT.rowshard_attention == "transpose":
             # the direction that crosses the row blocks, on the TRANSPOSED blocks: two transposing exchanges of the fp32 stream
@@ -1825,27 +1539,20 @@ class PairUpdateWithAxialAttentionLayer(RFModule):
         _pre_norm_residual_bwd(g, self.row_attn._backward, tape["row"], tape["x0"], self.layer[0].fn[0], grads)
         return g, grads
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd for the layer, its two Performers and its FeedForward: with grad mode on, forward() records and
-        loss.backward() fills the .grad of every parameter (and of the input, if it requires grad) through the HIP backward
-        kernels; in train() mode the backward replays the forward's dropout masks.  Stored on the modules; returns self."""
-        self._rf_backward = bool(mode)
-        self.row_attn.enable_backward(mode)
-        self.col_attn.enable_backward(mode)
-        self.ff.enable_backward(mode)
-        return self
+    def _backward_children(self):
+        return self.row_attn, self.col_attn, self.ff
 
-    def forward(self, x):
-        if _recording(self):
-            return _AxialFn.apply(self, x, *self.parameters())
+    def _record(self, x, tape):
         x = fresh_f32(x)
-        self.run(x)
+        self.run(x, tape=tape)
         return x
 
 
-class PairUpdateWithAxialAttention(RFModule):
-    """rf.py:531-547."""
-    _rf_backward = False   # enable_backward
+class PairUpdateWithAxialAttention(RecordingModule):
+    """rf.py:531-547.  enable_backward(): the stack and every layer below it (see PairUpdateWithAxialAttentionLayer).  Inside
+    RoseTTAFold.forward only the final block's stack records, and only together with the prediction head."""
+    _rf_scales_own_grads = True
+    _record = PairUpdateWithAxialAttentionLayer._record
 
     def __init__(self, d_pair, d_ff, n_heads, p_dropout, n_encoder_layers, performer_kws={}):
         super().__init__()
@@ -1854,11 +1561,9 @@ class PairUpdateWithAxialAttention(RFModule):
 
     def run(self, x, row_group=None, tape=None):
         """x fp32 in place.  tape: a dict that receives the layers' tapes (see PairUpdateWithAxialAttentionLayer.run)."""
+        _check_backward_call(self, tape, row_group, x.shape[-1])
         if tape is not None:
-            _check_backward_call(self, row_group, x.shape[-1])
             tape["layers"] = [{} for _ in self.layers]
-        elif row_group is not None and _recording(self):
-            raise NotImplementedError("PairUpdateWithAxialAttention: the backward pass does not support row-sharded calls")
         xn = None
         for i, layer in enumerate(self.layers):
             nxt = self.layers[i + 1].layer[0].fn[0] if i + 1 < len(self.layers) else None
@@ -1871,21 +1576,8 @@ class PairUpdateWithAxialAttention(RFModule):
             grads.update(gr)
         return g, grads
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd for the stack and every layer below it (see PairUpdateWithAxialAttentionLayer.enable_backward).
-        Inside RoseTTAFold.forward only the final block's stack records, and only together with the prediction head.
-        Returns self."""
-        self._rf_backward = bool(mode)
-        for layer in self.layers:
-            layer.enable_backward(mode)
-        return self
-
-    def forward(self, x):
-        if _recording(self):
-            return _AxialFn.apply(self, x, *self.parameters())
-        x = fresh_f32(x)
-        self.run(x)
-        return x
+    def _backward_children(self):
+        return self.layers
 
 
 # ================================================================================================
@@ -2172,9 +1864,8 @@ class InitialCoordGenerationWithMsaAndPair(RFModule):
 # ================================================================================================
 # prediction head (ResNet over the pair map)
 # ================================================================================================
-class ResBlock2D(RFModule):
+class ResBlock2D(RecordingModule):
     """resnet.py:15-44."""
-    _rf_backward = False   # enable_backward
 
     def __init__(self, channel, kernel_size, dilation, p_dropout=0.15):
         super().__init__()
@@ -2211,12 +1902,13 @@ class ResBlock2D(RFModule):
         """x_t: T NHWC (conv input), x_f: fp32 copy (residual).  Returns (T, fp32) of elu(block(x)+x).
         row_group / rows_global: x holds a block of the picture's rows (shard.resblock_row_sharded): every convolution first
         fetches `dilation` rows from each neighbouring rank, the InstanceNorm sums are all-reduced.
-        tape: a dict that receives what _backward needs (the recording forward of enable_backward; same kernels, same numbers)."""
+        tape: a dict that receives what _backward needs (same kernels, same numbers): the convolutions' outputs (the norms'
+        inputs), the InstanceNorm statistics, the ELU output before the dropout overwrites it, the dropout's (p, seed, offset),
+        the output."""
         f = self.layer.fn
         kw = {} if row_group is None else {"row_group": row_group, "rows_global": rows_global}
-        if tape is not None:
-            _check_backward_call(self, row_group, x_t.shape[-1])
-            return self._run_recording(x_t, x_f, tape)
+        _check_backward_call(self, tape, row_group, x_t.shape[-1])
+        rec = tape is not None
         if row_group is not None and x_t.shape[0] == 1:
             return self._run_rows_b1(x_t, x_f, row_group, rows_global, next_halo)
 
@@ -2227,31 +1919,23 @@ class ResBlock2D(RFModule):
             xh = shard.exchange_row_halos(x, self.dilation, row_group)
             return shard.drop_row_halos(conv3x3(self, key, c, xh, self.dilation), self.dilation)
 
+        stats = [] if rec else None   # (every name below is rebound as before: the plain call frees what it always freed)
         y = conv("c1", f[0], x_t)
-        y, _ = ops.instnorm(y, _f(f[1].weight), _f(f[1].bias), eps=f[1].eps, act=L.ACT_ELU, out_dtype=T(), **kw)
-        if self.training:
-            dropout_(y, _p(f[3]))   # resnet.py:30
+        if rec:
+            tape.update(x_t=x_t, y1=y)
+        y, _ = ops.instnorm(y, _f(f[1].weight), _f(f[1].bias), eps=f[1].eps, act=L.ACT_ELU, out_dtype=T(), stats_out=stats, **kw)
+        p = _p(f[3]) if self.training else 0.0   # resnet.py:30
+        if rec:
+            tape["a1"] = _copy(y) if p > 0 else y
+            tape["drop"] = _dropout_rec(y, p)
+            tape["a1d"] = y
+        else:
+            dropout_(y, p)
         y = conv("c2", f[4], y)
         o_f, o_t = ops.instnorm(y, _f(f[5].weight), _f(f[5].bias), eps=f[5].eps, residual=x_f, act=L.ACT_ELU,
-                                out_dtype=F32, out2_dtype=T(), **kw)
-        return o_t, o_f
-
-    def _run_recording(self, x_t, x_f, tape):
-        """run() without row blocks, keeping the tensors of the backward: the convolutions' outputs (the norms' inputs), the
-        InstanceNorm statistics, the ELU output before the dropout overwrites it, the dropout's (p, seed, offset), the output."""
-        f = self.layer.fn
-        s1, s2 = [], []
-        y1 = conv3x3(self, "c1", f[0], x_t, self.dilation)
-        a, _ = ops.instnorm(y1, _f(f[1].weight), _f(f[1].bias), eps=f[1].eps, act=L.ACT_ELU, out_dtype=T(), stats_out=s1)
-        a_elu, drop = a, None
-        if self.training:
-            if _p(f[3]) > 0:
-                a_elu = _copy(a)
-            drop = _dropout_rec(a, _p(f[3]))   # resnet.py:30
-        y2 = conv3x3(self, "c2", f[4], a, self.dilation)
-        o_f, o_t = ops.instnorm(y2, _f(f[5].weight), _f(f[5].bias), eps=f[5].eps, residual=x_f, act=L.ACT_ELU,
-                                out_dtype=F32, out2_dtype=T(), stats_out=s2)
-        tape.update(x_t=x_t, y1=y1, s1=s1[0], a1=a_elu, a1d=a, drop=drop, y2=y2, s2=s2[0], o_f=o_f)
+                                out_dtype=F32, out2_dtype=T(), stats_out=stats, **kw)
+        if rec:
+            tape.update(y2=y, s1=stats[0], s2=stats[1], o_f=o_f)
         return o_t, o_f
 
     def _backward(self, tape, g):
@@ -2270,22 +1954,18 @@ class ResBlock2D(RFModule):
         return dx, {f[0].weight: _conv_weight_grad(dw1, f[0].weight), f[1].weight: dg1, f[1].bias: db1,
                     f[4].weight: _conv_weight_grad(dw2, f[4].weight), f[5].weight: dg5, f[5].bias: db5}
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd: with grad mode on, forward() records and loss.backward() fills every parameter's .grad (and the
-        input's, if it requires grad) through the HIP backward kernels.  Stored on this module; returns self."""
-        self._rf_backward = bool(mode)
-        return self
-
-    def forward(self, x):  # NCHW like the reference
-        if _recording(self):
-            return _BlockFn.apply(self, x, *self.parameters())
+    def _record(self, x, tape):  # NCHW like the reference
         xf = x.float().permute(0, 2, 3, 1).contiguous()
-        return self.run(ops.cast(xf, T()), xf)[1].permute(0, 3, 1, 2)
+        return self.run(ops.cast(xf, T()), xf, tape=tape)[1].permute(0, 3, 1, 2)
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        dx, grads = self._backward(tape, _scaled_copy(gs[0].permute(0, 2, 3, 1), s))
+        _unscale([dx], s)
+        return dx.permute(0, 3, 1, 2), grads
 
 
-class ResNet(RFModule):
-    """resnet.py:47-83."""
-    _rf_backward = False   # enable_backward
+class ResNet(RecordingModule):
+    """resnet.py:47-83.  enable_backward(): this ResNet and its ResBlock2Ds."""
 
     def __init__(self, n_res_blocks, in_channels, intermediate_channels, out_channels, dilations=[1, 2, 4, 8],
                  p_dropout=0.15):
@@ -2301,12 +1981,12 @@ class ResNet(RFModule):
 
     def run(self, x_t, row_group=None, rows_global=None, tape=None):
         """x_t: T NHWC -> fp32 NHWC logits.  row_group / rows_global: x_t is a block of the picture's rows (see ResBlock2D.run).
-        tape: a dict that receives what _backward needs (the recording forward of enable_backward; same kernels, same numbers)."""
+        tape: a dict that receives what _backward needs (same kernels, same numbers) and the blocks' tapes."""
         l0, l1 = self.layer[0], self.layer[1]
         kw = {} if row_group is None else {"row_group": row_group, "rows_global": rows_global}
-        if tape is not None:
-            _check_backward_call(self, row_group, x_t.shape[-1], l0.weight.shape[0])
-            return self._run_recording(x_t, tape)
+        _check_backward_call(self, tape, row_group, x_t.shape[-1], l0.weight.shape[0])
+        rec = tape is not None
+        s0 = [] if rec else None
         h = ops.linear(x_t, self.wt("in", l0), None)
         dil = [self.layer[3 + b].dilation for b in range(self.n_res_blocks)] + [0]
         if row_group is not None and h.shape[0] == 1:
@@ -2315,25 +1995,15 @@ class ResNet(RFModule):
             h_f, h_t = ops.instnorm(h, _f(l1.weight), _f(l1.bias), eps=l1.eps, act=L.ACT_ELU, out_dtype=F32,
                                     out2=shard.interior(first, dil[0]), **kw)
         else:
-            h_f, h_t = ops.instnorm(h, _f(l1.weight), _f(l1.bias), eps=l1.eps, act=L.ACT_ELU, out_dtype=F32, out2_dtype=T(), **kw)
+            h_f, h_t = ops.instnorm(h, _f(l1.weight), _f(l1.bias), eps=l1.eps, act=L.ACT_ELU, out_dtype=F32, out2_dtype=T(),
+                                    stats_out=s0, **kw)
+        if rec:
+            tape.update(x_t=x_t, h0=h, s0=s0[0], h_f=h_f, blocks=[{} for _ in range(self.n_res_blocks)])
         for b in range(self.n_res_blocks):
-            h_t, h_f = self.layer[3 + b].run(h_t, h_f, next_halo=dil[b + 1], **kw)
+            h_t, h_f = self.layer[3 + b].run(h_t, h_f, next_halo=dil[b + 1], tape=tape["blocks"][b] if rec else None, **kw)
+        if rec:
+            tape["h_last"] = h_t
         lo = self.layer[3 + self.n_res_blocks]
-        return ops.linear(h_t, self.wt("out", lo), _f(lo.bias), out_dtype=F32)
-
-    def _run_recording(self, x_t, tape):
-        l0, l1 = self.layer[0], self.layer[1]
-        s0 = []
-        h = ops.linear(x_t, self.wt("in", l0), None)
-        h_f, h_t = ops.instnorm(h, _f(l1.weight), _f(l1.bias), eps=l1.eps, act=L.ACT_ELU, out_dtype=F32, out2_dtype=T(),
-                                stats_out=s0)
-        tape.update(x_t=x_t, h0=h, s0=s0[0], h_f=h_f, blocks=[])
-        for b in range(self.n_res_blocks):
-            bt = {}
-            h_t, h_f = self.layer[3 + b].run(h_t, h_f, tape=bt)
-            tape["blocks"].append(bt)
-        lo = self.layer[3 + self.n_res_blocks]
-        tape["h_last"] = h_t
         return ops.linear(h_t, self.wt("out", lo), _f(lo.bias), out_dtype=F32)
 
     def _backward(self, tape, g, want_dx=True):
@@ -2357,24 +2027,26 @@ class ResNet(RFModule):
         dx = ops.linear(dh0, self.wt_input_grad("in", l0), None, out_dtype=F32, exact=True) if want_dx else None
         return dx, grads
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd for this ResNet and its ResBlock2Ds (see ResBlock2D.enable_backward).  Returns self."""
-        self._rf_backward = bool(mode)
-        for m in self.layer:
-            if isinstance(m, ResBlock2D):
-                m.enable_backward(mode)
-        return self
+    def _backward_children(self):
+        return [m for m in self.layer if isinstance(m, ResBlock2D)]
 
-    def forward(self, x):  # NCHW in / NCHW out like the reference
-        if _recording(self):
-            return _ResNetFn.apply(self, x, *self.parameters())
+    def _record(self, x, tape):  # NCHW in / NCHW out like the reference
         xf = x.float().permute(0, 2, 3, 1).contiguous()
-        return self.run(ops.cast(xf, T())).permute(0, 3, 1, 2)
+        return self.run(ops.cast(xf, T()), tape=tape).permute(0, 3, 1, 2)
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        dx, grads = self._backward(tape, _scaled_copy(gs[0].permute(0, 2, 3, 1), s), want_dx=want_dx)
+        _unscale([dx], s)
+        return (dx.permute(0, 3, 1, 2) if dx is not None else None), grads
 
 
-class PredictionHead(RFModule):
-    """rf.py:1130-1172."""
-    _rf_backward = False   # enable_backward
+_HEADS = ("theta", "phi", "dist", "omega")
+
+
+class PredictionHead(RecordingModule):
+    """rf.py:1130-1172.  enable_backward(): the head, its four ResNets and their ResBlock2Ds; forward() then returns logits that
+    take part in autograd."""
+    _rf_scales_own_grads = True   # each ResNet and the projection: _backward
 
     def __init__(self, in_channels, n_res_blocks, p_dropout):
         super().__init__()
@@ -2386,22 +2058,20 @@ class PredictionHead(RFModule):
         self.phi_head = nn.Sequential(ResNet(n_res_blocks, c, c, 19, p_dropout=p_dropout), nn.Identity())
 
     def forward(self, pair):
-        if _recording(self):
-            return dict(zip(_HEADS, _HeadFn.apply(self, pair.float().contiguous(), *self.parameters())))
-        return self.run(pair.float().contiguous())
+        return dict(zip(_HEADS, super().forward(pair.float().contiguous())))
 
-    def enable_backward(self, mode=True):
-        """Opt in to autograd for the head, its four ResNets and their ResBlock2Ds: with grad mode on, forward() returns logits
-        that take part in autograd and loss.backward() fills the .grad of every head parameter (and of the pair input when it
-        requires grad) through the HIP backward kernels.  In train() mode the backward replays the forward's dropout masks.
-        Stored on the modules (no global state); returns self."""
-        self._rf_backward = bool(mode)
-        for name in _HEADS:
-            getattr(self, name + "_head")[0].enable_backward(mode)
-        return self
+    def _record(self, pair, tape):
+        out = self.run(pair, tape=tape)
+        return tuple(out[k] for k in _HEADS)
+
+    def _backward_children(self):
+        return [getattr(self, name + "_head")[0] for name in _HEADS]
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        return self._backward(tape, dict(zip(_HEADS, gs)), want_dpair=want_dx)
 
     def _backward(self, tape, gs, want_dpair=True):
-        """gs: {name: gradient of that logit map}.  Returns (fp32 gradient of pair or None, {param: grad}, 1.0): the unscaled
+        """gs: {name: gradient of that logit map}.  Returns (fp32 gradient of pair or None, {param: grad}): the unscaled
         gradients (each ResNet and the projection scale their own operands in the fp16 mode)."""
         grads, d = {}, {}
         for name in _HEADS:
@@ -2433,7 +2103,7 @@ class PredictionHead(RFModule):
             dpair, dg, dbeta = ops.layernorm_bwd(tape["pair"], dt, _f(lnm.weight), eps=lnm.eps)
             grads.update({lnm.weight: dg, lnm.bias: dbeta})
         _unscale([dw, db, dpair, grads.get(lnm.weight), grads.get(lnm.bias)], s)
-        return (dpair if want_dpair else None), grads, 1.0
+        return (dpair if want_dpair else None), grads
 
     def run(self, pair, row_group=None, tape=None):
         """pair fp32 [B, L, L, C] -> the four logit maps (fp32 NHWC).  row_group: `pair` is this rank's block of rows
@@ -2441,10 +2111,7 @@ class PredictionHead(RFModule):
         transposed sub-blocks from the other ranks, the ResNets exchange halo rows and InstanceNorm sums; returns the same rows
         of the logit maps."""
         B, h, Lr, Cc = pair.shape
-        if tape is not None:
-            _check_backward_call(self, row_group, Cc, self.proj[1].weight.shape[0])
-        elif row_group is not None and getattr(self, "_rf_backward", False) and torch.is_grad_enabled():
-            raise NotImplementedError("PredictionHead: the backward pass does not support row-sharded calls (row_group)")
+        _check_backward_call(self, tape, row_group, Cc, self.proj[1].weight.shape[0])
         kwc = {} if row_group is None else {"row_group": row_group, "rows_global": Lr}
         drop = None
         # Operand conditioning for the 16-bit modes (exact in exact arithmetic): every ResNet starts conv1x1 (no bias) ->
@@ -2462,10 +2129,7 @@ class PredictionHead(RFModule):
             op = ln(self.proj[0], pair)
             x = ops.linear(op, self.wt("p", self.proj[1]), _f(self.proj[1].bias), out_dtype=F32)
             if self.training:
-                if tape is not None:
-                    drop = _dropout_rec(x, _p(self.proj[2]))
-                else:
-                    dropout_(x, _p(self.proj[2]))   # rf.py:1138
+                drop = _dropout_rec(x, _p(self.proj[2]))   # rf.py:1138 (the record goes on the tape, if there is one)
             if cond:
                 ops.center_apply(x, ops.channel_mean(x, **kwc))
         if row_group is None:
@@ -2479,10 +2143,8 @@ class PredictionHead(RFModule):
         xs = ops.axpby(x, 0.5, xt, 0.5, torch.empty(x.shape, device=x.device, dtype=T()))
         x_t = ops.cast(x, T())
         if tape is not None:
-            tape.update(pair=pair, op=op, drop=drop)
-            for name in _HEADS:
-                tape[name] = {}
-            return {"theta": self.theta_head[0].run(x_t, tape=tape["theta"]), "phi": self.phi_head[0].run(x_t, tape=tape["phi"]),
-                    "dist": self.dist_head[0].run(xs, tape=tape["dist"]), "omega": self.omega_head[0].run(xs, tape=tape["omega"])}
-        return {"theta": self.theta_head[0].run(x_t, **kw), "phi": self.phi_head[0].run(x_t, **kw),
-                "dist": self.dist_head[0].run(xs, **kw), "omega": self.omega_head[0].run(xs, **kw)}
+            tape.update(pair=pair, op=op, drop=drop, **{name: {} for name in _HEADS})
+        # x feeds theta / phi, xs = (x + x^T) / 2 feeds dist / omega (rf.py:1160)
+        return {name: getattr(self, name + "_head")[0].run(xs if name in ("dist", "omega") else x_t,
+                                                           tape=tape[name] if tape is not None else None, **kw)
+                for name in _HEADS}

@@ -14,6 +14,7 @@ from .model import (RFModule, Residual, FeedForward, PositionWiseWeightFactor, M
                     MsaUpdateUsingSelfAttention, PairUpdateWithMsa, PairUpdateWithAxialAttention, MsaUpdateWithPair,
                     InitialCoordGenerationWithMsaAndPair, PredictionHead, LayerNorm, Linear, _node_input, _f, ln, T, pad8,
                     CA_IDX, fresh_f32, check_index_range, RT)
+from .backward import _recording
 
 
 # ================================================================================================
@@ -570,8 +571,8 @@ class RoseTTAFold(RFModule):
         under no_grad up to its input; its output feeds the recording head, a detached copy the MSA update and the structure
         track), so the gradient reaches its parameters.  It needs the head: enabling it alone raises ValueError.  The axial
         updates of the two-track and three-track blocks record only when called directly, never inside this forward."""
-        head_grad = torch.is_grad_enabled() and getattr(self.prediction_head, "_rf_backward", False)
-        axial_grad = torch.is_grad_enabled() and getattr(self.final_block.pair_update_with_axial_attention, "_rf_backward", False)
+        head_grad = _recording(self.prediction_head)
+        axial_grad = _recording(self.final_block.pair_update_with_axial_attention)
         if axial_grad and not head_grad:
             raise ValueError("final_block.pair_update_with_axial_attention has backward enabled but prediction_head does not: no "
                              "gradient could reach it (enable_backward() on the head too)")
