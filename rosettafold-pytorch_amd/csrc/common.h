@@ -54,6 +54,11 @@ __device__ __forceinline__ unsigned rf_pack2_h16(float a, float b) {
   const rf_f32x2 v = {a, b};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, rf_h16x2));
 }
+// one global_load_lds of 16 bytes per lane: the wave's 64 pieces land at lds_wave_base + 16 * lane (wave-uniform base)
+__device__ __forceinline__ void rf_glds16(const void* src, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
 // the two halves of a packed pair as floats
 __device__ __forceinline__ float rf_h16_lo(unsigned u) {
 #ifdef RF_H16_IS_F16

@@ -27,11 +27,6 @@ struct Conv288P {
   int nt_store;
 };
 
-__device__ __forceinline__ void conv_glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 __global__ __launch_bounds__(512) void conv3x3_c288_kernel(const Conv288P p) {
   constexpr int C = 288, BM = 256, BN = 288;
   constexpr int WGN = 2, TM = 64, TN = 144, WM = 4, WN = 9;  // 4 x 2 waves, wave tile 64 pixels x 144 channels
@@ -90,10 +85,10 @@ __global__ __launch_bounds__(512) void conv3x3_c288_kernel(const Conv288P p) {
       const int ii = i + di * d;
       const bool ok = ii >= 0 && ii < p.H && off >= 0;
       const char* base = (const char*)(xrow0 + (int64_t)ii * p.W * C + cg * 32);
-      conv_glds16(ok ? base + off : (const char*)g_conv_zero16, a_lds + q * 1024);
+      rf_glds16(ok ? base + off : (const char*)g_conv_zero16, a_lds + q * 1024);
     } else if (q < NPIECES) {
       const char* base = (const char*)(p.w + (di + 1) * 3 * C + cg * 32);
-      conv_glds16(base + off, a_lds + q * 1024);   // (piece q of the buffer: the three weight tiles follow the image)
+      rf_glds16(base + off, a_lds + q * 1024);   // (piece q of the buffer: the three weight tiles follow the image)
     }
   };
 

@@ -60,11 +60,6 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 __device__ __forceinline__ int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
-__device__ __forceinline__ void fv_glds(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // DMA a [nrows][64] bf16 tile (rows `stride` elements apart) into the swizzled LDS image at lds_off
 __device__ __forceinline__ void fv_load_tile(char* smem, int lds_off, const h16_t* g, int64_t stride, int nrows,
                                              int wave, int lane) {
@@ -73,11 +68,10 @@ __device__ __forceinline__ void fv_load_tile(char* smem, int lds_off, const h16_
     const int slot = it * 64 + lane;
     const int row = slot >> 3;
     const int clog = (slot & 7) ^ (row & 7);
-    fv_glds(g + (int64_t)row * stride + clog * 8, smem + lds_off + it * 1024);
+    rf_glds16(g + (int64_t)row * stride + clog * 8, smem + lds_off + it * 1024);
   }
 }
 
-__device__ __forceinline__ unsigned pack2(float a, float b) { return rf_pack2_h16(a, b); }
 __device__ __forceinline__ float rbf(float x) { return h2f(f2h(x)); }
 
 // The value of an MFMA accumulator register that an LDS instruction (the denominator broadcast: __shfl = ds_bpermute_b32) is
@@ -296,10 +290,10 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
               for (int r = 0; r < 4; ++r) f[t][r] = 0.f;
           }
           Frag kfr;
-          kfr.u[0] = pack2(f[0][0], f[0][1]);
-          kfr.u[1] = pack2(f[0][2], f[0][3]);
-          kfr.u[2] = pack2(f[1][0], f[1][1]);
-          kfr.u[3] = pack2(f[1][2], f[1][3]);
+          kfr.u[0] = rf_pack2_h16(f[0][0], f[0][1]);
+          kfr.u[1] = rf_pack2_h16(f[0][2], f[0][3]);
+          kfr.u[2] = rf_pack2_h16(f[1][0], f[1][1]);
+          kfr.u[3] = rf_pack2_h16(f[1][2], f[1][3]);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             ctx[j][i] = rf_mfma16(kfr.v, vf[i].v, ctx[j][i], 0, 0, 0);
@@ -315,8 +309,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
 #pragma unroll
         for (int i = 0; i < FV_DT; ++i) {
           uint2 w;
-          w.x = pack2(FV_CS(ctx[j][i][0]), FV_CS(ctx[j][i][1]));
-          w.y = pack2(FV_CS(ctx[j][i][2]), FV_CS(ctx[j][i][3]));
+          w.x = rf_pack2_h16(FV_CS(ctx[j][i][0]), FV_CS(ctx[j][i][1]));
+          w.y = rf_pack2_h16(FV_CS(ctx[j][i][2]), FV_CS(ctx[j][i][3]));
           *(uint2*)(smem + CTX_OFF + (i * 16 + fr) * FV_CTX_LD + ((m0t + j) * 16 + 4 * fq) * 2) = w;
         }
       }
@@ -430,10 +424,10 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
 #pragma unroll
       for (int t = 0; t < ST; ++t) {
         Frag qfr;
-        qfr.u[0] = pack2(f[0][t][0], f[0][t][1]);
-        qfr.u[1] = pack2(f[0][t][2], f[0][t][3]);
-        qfr.u[2] = pack2(f[1][t][0], f[1][t][1]);
-        qfr.u[3] = pack2(f[1][t][2], f[1][t][3]);
+        qfr.u[0] = rf_pack2_h16(f[0][t][0], f[0][t][1]);
+        qfr.u[1] = rf_pack2_h16(f[0][t][2], f[0][t][3]);
+        qfr.u[2] = rf_pack2_h16(f[1][t][0], f[1][t][1]);
+        qfr.u[3] = rf_pack2_h16(f[1][t][2], f[1][t][3]);
 #pragma unroll
         for (int i = 0; i < FV_DT; ++i)
           num[i][t] = rf_mfma16(cf[i].v, qfr.v, num[i][t], 0, 0, 0);
@@ -451,8 +445,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         uint2 w;
-        w.x = pack2(num[i][t][0] * inv, num[i][t][1] * inv);
-        w.y = pack2(num[i][t][2] * inv, num[i][t][3] * inv);
+        w.x = rf_pack2_h16(num[i][t][0] * inv, num[i][t][1] * inv);
+        w.y = rf_pack2_h16(num[i][t][2] * inv, num[i][t][3] * inv);
         *(uint2*)(orow + i * 16 + 4 * fq) = w;
       }
     }
@@ -736,10 +730,10 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
                 for (int r = 0; r < 4; ++r) f[t][r] = 0.f;
             }
             Frag kfr;
-            kfr.u[0] = pack2(f[0][0], f[0][1]);
-            kfr.u[1] = pack2(f[0][2], f[0][3]);
-            kfr.u[2] = pack2(f[1][0], f[1][1]);
-            kfr.u[3] = pack2(f[1][2], f[1][3]);
+            kfr.u[0] = rf_pack2_h16(f[0][0], f[0][1]);
+            kfr.u[1] = rf_pack2_h16(f[0][2], f[0][3]);
+            kfr.u[2] = rf_pack2_h16(f[1][0], f[1][1]);
+            kfr.u[3] = rf_pack2_h16(f[1][2], f[1][3]);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
               ctx[j][i] = rf_mfma16(kfr.v, vf[i].v, ctx[j][i], 0, 0, 0);
@@ -762,8 +756,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 #pragma unroll
         for (int i = 0; i < FV_DT; ++i) {
           uint2 w;
-          w.x = pack2(FV_CS(ctx[j][i][0]), FV_CS(ctx[j][i][1]));
-          w.y = pack2(FV_CS(ctx[j][i][2]), FV_CS(ctx[j][i][3]));
+          w.x = rf_pack2_h16(FV_CS(ctx[j][i][0]), FV_CS(ctx[j][i][1]));
+          w.y = rf_pack2_h16(FV_CS(ctx[j][i][2]), FV_CS(ctx[j][i][3]));
           *(uint2*)(smem + CTX_OFF + (i * 16 + fr) * FV_CTX_LD + ctx_col(m0t + j, fq)) = w;
         }
       }
@@ -886,10 +880,10 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 #pragma unroll
           for (int t = 0; t < STB; ++t) {
             Frag qfr;
-            qfr.u[0] = pack2(f[0][t][0], f[0][t][1]);
-            qfr.u[1] = pack2(f[0][t][2], f[0][t][3]);
-            qfr.u[2] = pack2(f[1][t][0], f[1][t][1]);
-            qfr.u[3] = pack2(f[1][t][2], f[1][t][3]);
+            qfr.u[0] = rf_pack2_h16(f[0][t][0], f[0][t][1]);
+            qfr.u[1] = rf_pack2_h16(f[0][t][2], f[0][t][3]);
+            qfr.u[2] = rf_pack2_h16(f[1][t][0], f[1][t][1]);
+            qfr.u[3] = rf_pack2_h16(f[1][t][2], f[1][t][3]);
 #pragma unroll
             for (int i = 0; i < FV_DT; ++i)
               num[i][t] = rf_mfma16(cf[i].v, qfr.v, num[i][t], 0, 0, 0);
@@ -907,8 +901,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             uint2 w;
-            w.x = pack2(num[i][t][0] * inv, num[i][t][1] * inv);
-            w.y = pack2(num[i][t][2] * inv, num[i][t][3] * inv);
+            w.x = rf_pack2_h16(num[i][t][0] * inv, num[i][t][1] * inv);
+            w.y = rf_pack2_h16(num[i][t][2] * inv, num[i][t][3] * inv);
             *(uint2*)(orow + i * 16 + 4 * fq) = w;
           }
         }

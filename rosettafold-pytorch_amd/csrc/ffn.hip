@@ -63,11 +63,6 @@ struct FfnP {
   int ntiles, nchunks;
 };
 
-__device__ __forceinline__ void ffn_glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 typedef __attribute__((ext_vector_type(4))) unsigned ffn_u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned ffn_u32x2;
 union FfnFrag {
@@ -203,17 +198,17 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const FfnP p) {
     const int q = t * 8 + wave;
     if (FFN_ABL & 16) return;
     if (i_kind == 1 && q < PIECES && !(FFN_ABL & 4)) {
-      ffn_glds16(i_base + wsrc[t], i_dst + q * 1024);
+      rf_glds16(i_base + wsrc[t], i_dst + q * 1024);
     } else if (i_kind == 0 && q < PIECES) {
-      ffn_glds16(i_base + xsrc[t], i_dst + q * 1024);
+      rf_glds16(i_base + xsrc[t], i_dst + q * 1024);
     } else if (i_kind == 2 && q < CPIECES) {
       // b2 | gamma | beta as one virtual array of 16-byte cells j = 64 q + lane
       const int j = q * 64 + lane;
       const float* src = j < D / 4 ? p.b2 + 4 * j : (j < D / 2 ? p.gamma + (4 * j - D) : p.beta + (4 * j - 2 * D));
       const bool ok = j < 3 * D / 4 && (j < D / 4 || p.ln);
-      ffn_glds16(ok ? (const void*)src : (const void*)p.b2, i_dst + q * 1024);
+      rf_glds16(ok ? (const void*)src : (const void*)p.b2, i_dst + q * 1024);
     } else {
-      ffn_glds16(p.Wp, smem + DUMP);  // every wave issues PD instructions per step: the counted vmcnt relies on it
+      rf_glds16(p.Wp, smem + DUMP);  // every wave issues PD instructions per step: the counted vmcnt relies on it
     }
   };
   auto dma_all = [&]() {

@@ -86,11 +86,6 @@ __device__ __forceinline__ int swz(int row) {
     return (0x78 >> (((row >> 2) & 3) * 2)) & 3;  // 4 chunks per 64-B row: g = {0,2,3,1}[(row>>2)&3]
 }
 
-__device__ __forceinline__ void glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int BM, int BN, int BK, int WGM, int WGN, int AMODE>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_bf16_kernel(const GemmP p) {
   constexpr int NW = WGM * WGN;  // waves per workgroup, arranged WGM x WGN over the tile
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_bf16_kernel(const Gemm
           ok = ok && ii >= 0 && ii < d.conv_h && jj >= 0 && jj < d.conv_w;
         }
         const h16_t* src = ok ? a_src[t] + a_koff : zsrc;
-        glds16(src, a_lds + instr * 1024);
+        rf_glds16(src, a_lds + instr * 1024);
       }
     }
 #pragma unroll
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_bf16_kernel(const Gemm
       const int instr = t * NW + wave;
       if ((B_INSTR % NW == 0) || instr < B_INSTR) {
         const h16_t* src = kvalid ? b_src[t] + b_koff : zsrc;
-        glds16(src, b_lds + instr * 1024);
+        rf_glds16(src, b_lds + instr * 1024);
       }
     }
     // advance this lane's K cursor by one step

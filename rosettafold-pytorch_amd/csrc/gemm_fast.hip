@@ -46,11 +46,6 @@ struct FastP {
   int64_t c_ro, c_co;
 };
 
-__device__ __forceinline__ void fast_glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 template <int BN, bool OUT_F32, bool HAS_RES, bool STAMP = false, bool LN = false, bool CS = false, int BM = 256>
 __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(const FastP p) {
   static_assert(!LN || (OUT_F32 && HAS_RES), "the fused LayerNorm epilogue normalises the updated fp32 residual rows");
@@ -87,18 +82,18 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(const FastP p) {
       const bool kvalid = kt * BK + c_log * 8 < p.K;
 #pragma unroll
       for (int t = 0; t < A_PW; ++t)
-        fast_glds16(kvalid ? Ab + (int64_t)t * 64 * p.lda * 2 + a_lane : (const char*)g_fast_zero16, a_lds + (t * NW + wave) * 1024);
+        rf_glds16(kvalid ? Ab + (int64_t)t * 64 * p.lda * 2 + a_lane : (const char*)g_fast_zero16, a_lds + (t * NW + wave) * 1024);
 #pragma unroll
       for (int t = 0; t < B_PW; ++t)
         if ((B_INSTR % NW == 0) || t * NW + wave < B_INSTR)
-          fast_glds16(kvalid ? Bb + (int64_t)t * 64 * p.ldb * 2 + b_lane : (const char*)g_fast_zero16, b_lds + (t * NW + wave) * 1024);
+          rf_glds16(kvalid ? Bb + (int64_t)t * 64 * p.ldb * 2 + b_lane : (const char*)g_fast_zero16, b_lds + (t * NW + wave) * 1024);
     } else {
 #pragma unroll
-      for (int t = 0; t < A_PW; ++t) fast_glds16(Ab + (int64_t)t * 64 * p.lda * 2 + a_lane, a_lds + (t * NW + wave) * 1024);
+      for (int t = 0; t < A_PW; ++t) rf_glds16(Ab + (int64_t)t * 64 * p.lda * 2 + a_lane, a_lds + (t * NW + wave) * 1024);
 #pragma unroll
       for (int t = 0; t < B_PW; ++t)
         if ((B_INSTR % NW == 0) || t * NW + wave < B_INSTR)
-          fast_glds16(Bb + (int64_t)t * 64 * p.ldb * 2 + b_lane, b_lds + (t * NW + wave) * 1024);
+          rf_glds16(Bb + (int64_t)t * 64 * p.ldb * 2 + b_lane, b_lds + (t * NW + wave) * 1024);
     }
   };
 

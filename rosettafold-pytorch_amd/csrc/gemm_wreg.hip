@@ -44,12 +44,6 @@ struct WregP {
   float rs_alpha;
 };
 
-__device__ __forceinline__ void wreg_glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned wreg_pack2(float a, float b) { return rf_pack2_h16(a, b); }
 
 // KS: K / 32;  TMR: rows per activation tile;  WR: wave rows (8 / WR wave columns);  WCT: 16-column tiles per wave;
 // NSTG: ring depth;  CS: split-C addressing
@@ -135,9 +129,9 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(const WregP p) {
 #pragma unroll
     for (int t = 0; t < PD; ++t) {
       if (live && t * 8 + wave < NI)  // (wave-uniform: scalar branch, exactly one DMA instruction per t)
-        wreg_glds16(Ab + dsrc[t], st + (t * 8 + wave) * 1024);
+        rf_glds16(Ab + dsrc[t], st + (t * 8 + wave) * 1024);
       else
-        wreg_glds16(g_wreg_zero16, smem + DUMP);  // keeps every wave's DMA count per tile at PD
+        rf_glds16(g_wreg_zero16, smem + DUMP);  // keeps every wave's DMA count per tile at PD
     }
   };
 
@@ -265,8 +259,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(const WregP p) {
 #pragma unroll
       for (int j = 0; j < WCT; ++j) {
         uint2 o;
-        o.x = wreg_pack2(fmaxf(acc[i][j][0], lo), fmaxf(acc[i][j][1], lo));
-        o.y = wreg_pack2(fmaxf(acc[i][j][2], lo), fmaxf(acc[i][j][3], lo));
+        o.x = rf_pack2_h16(fmaxf(acc[i][j][0], lo), fmaxf(acc[i][j][1], lo));
+        o.y = rf_pack2_h16(fmaxf(acc[i][j][2], lo), fmaxf(acc[i][j][3], lo));
         *(uint2*)(strip + (i * 16 + fr) * PITCH + (j * 16 + 4 * fq) * 2) = o;
       }
     asm volatile("" ::: "memory");

@@ -54,7 +54,6 @@ struct OuterP {
 __device__ __forceinline__ void outer_glds16(const void* src, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
 }
-__device__ __forceinline__ unsigned outer_pack2(float a, float b) { return rf_pack2_h16(a, b); }
 // workgroup barrier that publishes this wave's LDS writes but leaves its DMAs in flight (a __syncthreads() would drain them)
 __device__ __forceinline__ void outer_lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -232,8 +231,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
         ssum[t] += (d[t][0] + d[t][1]) + (d[t][2] + d[t][3]);
         ssq[t] += (d[t][0] * d[t][0] + d[t][1] * d[t][1]) + (d[t][2] * d[t][2] + d[t][3] * d[t][3]);
         uint2 w;
-        w.x = outer_pack2(d[t][0], d[t][1]);
-        w.y = outer_pack2(d[t][2], d[t][3]);
+        w.x = rf_pack2_h16(d[t][0], d[t][1]);
+        w.y = rf_pack2_h16(d[t][2], d[t][3]);
         asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(a2a), "v"(w), "i"(t * 2048) : "memory");
       }
     };
@@ -426,8 +425,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
         for (int cc = 0; cc < 2; ++cc) {
           const f32x4 v = (acc[rt][cc] - ms.x) * ms.y * g4[cc] + e4[cc];
           uint2 w;
-          w.x = outer_pack2(v[0], v[1]);
-          w.y = outer_pack2(v[2], v[3]);
+          w.x = rf_pack2_h16(v[0], v[1]);
+          w.y = rf_pack2_h16(v[2], v[3]);
           *(uint2*)(irow + cc * 32) = w;
         }
       }
@@ -440,8 +439,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
           const f32x4 gx = *(const f32x4*)(p.g2 + 256 + cc * 16 + 4 * fq), ex = *(const f32x4*)(p.b2 + 256 + cc * 16 + 4 * fq);
           const f32x4 v = (accx[cc] - ms.x) * ms.y * gx + ex;
           uint2 w;
-          w.x = outer_pack2(v[0], v[1]);
-          w.y = outer_pack2(v[2], v[3]);
+          w.x = rf_pack2_h16(v[0], v[1]);
+          w.y = rf_pack2_h16(v[2], v[3]);
           *(uint2*)(irow + cc * 32) = w;
         }
       }

@@ -27,12 +27,6 @@ union TFrag {
 };
 typedef __attribute__((ext_vector_type(4))) short ts16x4;
 
-__device__ __forceinline__ unsigned tpack2(float a, float b) { return rf_pack2_h16(a, b); }
-
-__device__ __forceinline__ void tied_glds16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // logits + softmax
@@ -87,11 +81,11 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 4 + wave;
       if (live && instr < QI)
-        tied_glds16(qb + (int64_t)n * p.n_stride + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
+        rf_glds16(qb + (int64_t)n * p.n_stride + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
       else if (live && instr < QI + KI)
-        tied_glds16(kb + (int64_t)n * p.n_stride + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
+        rf_glds16(kb + (int64_t)n * p.n_stride + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
       else
-        tied_glds16(g_tied_zero16, smem + DUMP);  // keeps every wave's DMA count per step at PW
+        rf_glds16(g_tied_zero16, smem + DUMP);  // keeps every wave's DMA count per step at PW
     }
   };
 
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
     // These are the oldest operations of every wave, so the counted wait of the first step covers them.
     const float* wb = p.w + (int64_t)b * p.w_b + (int64_t)h * p.w_h + it * 64 + (lane & 15) * 4;
     for (int i4 = wave; i4 * 4 < p.N; i4 += 4)
-      tied_glds16(wb + (int64_t)(i4 * 4 + (lane >> 4)) * p.w_n, smem + W_OFF + i4 * 1024);
+      rf_glds16(wb + (int64_t)(i4 * 4 + (lane >> 4)) * p.w_n, smem + W_OFF + i4 * 1024);
   }
 
   f32x4 acc[JT];
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
       const float ws = wrow[n * 64] * p.qscale;  // w[b,h,n, row of this lane] * d_head^-0.5: the same rounding point as q*w (rf.py:252)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        qf.u[e] = tpack2(rf_h16_lo(qf.u[e]) * ws, rf_h16_hi(qf.u[e]) * ws);
+        qf.u[e] = rf_pack2_h16(rf_h16_lo(qf.u[e]) * ws, rf_h16_hi(qf.u[e]) * ws);
     }
     if (!(RF_DBG(p.dbg) & 4)) {
 #pragma unroll
@@ -166,8 +160,8 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
 #pragma unroll
   for (int j = 0; j < JT; ++j) {
     uint2 w;
-    w.x = tpack2(acc[j][0] * inv, acc[j][1] * inv);
-    w.y = tpack2(acc[j][2] * inv, acc[j][3] * inv);
+    w.x = rf_pack2_h16(acc[j][0] * inv, acc[j][1] * inv);
+    w.y = rf_pack2_h16(acc[j][2] * inv, acc[j][3] * inv);
     *(uint2*)(strip + fr * PITCH + (j * 16 + 4 * fq) * 2) = w;
   }
   asm volatile("" ::: "memory");
@@ -245,11 +239,11 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 8 + wave;
       if (live && instr < QI)
-        tied_glds16(qb + noff + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
+        rf_glds16(qb + noff + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
       else if (live)
-        tied_glds16(kb + noff + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
+        rf_glds16(kb + noff + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
       else
-        tied_glds16(g_tied_zero16, smem + DUMP);  // keeps every wave's DMA count per step at PW
+        rf_glds16(g_tied_zero16, smem + DUMP);  // keeps every wave's DMA count per step at PW
     }
   };
   if constexpr (SCALE) {
@@ -257,7 +251,7 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
     // The oldest operations of every wave: the counted wait of the first step covers them.
     const float* wb = p.w + (int64_t)b * p.w_b + (int64_t)h * p.w_h + rb * RB + (lane & 31) * 4;
     for (int i2 = wave; i2 * 2 < p.nper; i2 += 8)
-      tied_glds16(wb + (int64_t)(n0 + i2 * 2 + (lane >> 5)) * p.w_n, smem + W_OFF + i2 * 1024);
+      rf_glds16(wb + (int64_t)(n0 + i2 * 2 + (lane >> 5)) * p.w_n, smem + W_OFF + i2 * 1024);
   }
 
   f32x4 acc[4][4];  // [key tile][query tile]
@@ -291,7 +285,7 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
         const float ws = wrow[t_ * RB + qt * 16] * p.qscale;  // w[b,h,n, query row of this lane] * d_head^-0.5 (rf.py:252)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          qf[qt].u[e] = tpack2(rf_h16_lo(qf[qt].u[e]) * ws, rf_h16_hi(qf[qt].u[e]) * ws);
+          qf[qt].u[e] = rf_pack2_h16(rf_h16_lo(qf[qt].u[e]) * ws, rf_h16_hi(qf[qt].u[e]) * ws);
       }
     }
     if (!(RF_DBG(p.dbg) & 4)) {
@@ -343,8 +337,8 @@ __global__ __launch_bounds__(256) void tied_split_softmax_kernel(const float* pa
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     uint2 o;
-    o.x = tpack2(v[c][0] * inv, v[c][1] * inv);
-    o.y = tpack2(v[c][2] * inv, v[c][3] * inv);
+    o.x = rf_pack2_h16(v[c][0] * inv, v[c][1] * inv);
+    o.y = rf_pack2_h16(v[c][2] * inv, v[c][3] * inv);
     *(uint2*)(att + row * L + c * 256 + lane * 4) = o;
   }
 }
@@ -506,9 +500,9 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 4 + wave;
       if (live && instr < VI)
-        tied_glds16(vb + (int64_t)(instr * 16) * p.v_l + lane_off, st + instr * 1024);
+        rf_glds16(vb + (int64_t)(instr * 16) * p.v_l + lane_off, st + instr * 1024);
       else
-        tied_glds16(g_tied_zero16, smem + DUMP);
+        rf_glds16(g_tied_zero16, smem + DUMP);
     }
   };
   // transposed-read byte offsets inside a stage (tile independent): key rows 32 s + 8 fq + 4 half + (fr >> 2), head dims
@@ -599,8 +593,8 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           uint2 w;
-          w.x = tpack2(acc[t][c][0], acc[t][c][1]);
-          w.y = tpack2(acc[t][c][2], acc[t][c][3]);
+          w.x = rf_pack2_h16(acc[t][c][0], acc[t][c][1]);
+          w.y = rf_pack2_h16(acc[t][c][2], acc[t][c][3]);
           *(uint2*)(ob + (int64_t)(t * 16) * p.o_l + c * 16) = w;
         }
     }

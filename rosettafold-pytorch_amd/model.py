@@ -870,41 +870,24 @@ class PerformerSelfAttention(RecordingModule):
             pcf = pc if gen else self.proj_scaled(log2e=True)
             eps = 1e-3 if gen else 1e-4
             wqkv = self.wcat("qkv", [self.to_q, self.to_k, self.to_v])
-            if RT.head_major_qkv == 1 or (RT.head_major_qkv == 2 and axis == 2):
-                # q|k|v written head-major [B, Lo, 3, H, Ls, 64] straight from the projection GEMM's epilogue: every
-                # (b, o, head) tile the FAVOR kernel DMAs is then one contiguous 8 KB x (Ls/64) block
-                qkv = torch.empty(B, Lo, 3, H, Ls, dh, device=dev, dtype=T())
-                so_c = 3 * H * Ls * dh
-                if axis == 2:
-                    # row m = (b, p1, p2) with the sequence along p2: offset (m / L2) * so_c + (m % L2) * dh -- one launch, the
-                    # register-resident-weight GEMM's split-C epilogue (csrc/gemm_wreg.hip)
-                    ops.gemm(xn, wqkv, qkv, R, W3, D, c_row=(L2, so_c, dh), c_col=(dh, Ls * dh), bias=bqkv)
-                else:
-                    # sequence along p1: offset b * Lo * so_c + p2 * so_c + p1 * dh is a three-level split: one launch per
-                    # batch element (row m = p1 * L2 + p2 inside it: (m / L2) * dh + (m % L2) * so_c)
-                    for b in range(B):
-                        ops.gemm(xn[b], wqkv, qkv[b], RB, W3, D, c_row=(L2, dh, so_c), c_col=(dh, Ls * dh), bias=bqkv)
-                ops.favor_attention(qkv, pcf, o, (Lo * so_c, so_c, dh, Ls * dh), (RB * inner, so * inner, ss * inner),
-                                    0, H * Ls * dh, 2 * H * Ls * dh, B, Lo, H, Ls, dh, m, not gen, eps)
-            else:
-                # whole batch elements per panel (RB rows each: any axis stays addressable inside one element)
-                pr = row_panels(R, W3 * 2, RB)
-                if pr < R and not drops:
-                    nb = pr // RB
-                    qkv = torch.empty(pr, W3, device=dev, dtype=T())
-                    xn2, xr2 = xn.view(R, D), x_res.view(R, -1)
-                    wo = self.wt("o", self.to_out)
-                    nxt, fused = torch.empty(R, xr2.shape[1], device=dev, dtype=T()) if next_ln is not None else None, True
-                    for r0 in range(0, R, pr):
-                        ops.linear(xn2[r0:r0 + pr], wqkv, bqkv, out=qkv)
-                        op = o[r0:r0 + pr]
-                        ops.favor_attention(qkv, pcf, op, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
-                                            0, inner, 2 * inner, nb, Lo, H, Ls, dh, m, not gen, eps)
-                        fused &= ops.linear_residual_ln(op, wo, bo, xr2[r0:r0 + pr], next_ln, nxt[r0:r0 + pr] if nxt is not None else None) is not None
-                    return nxt.view(x_res.shape) if nxt is not None and fused else None
-                qkv = ops.linear(xn, wqkv, bqkv)
-                ops.favor_attention(qkv, pcf, o, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
-                                    0, inner, 2 * inner, B, Lo, H, Ls, dh, m, not gen, eps)
+            # whole batch elements per panel (RB rows each: any axis stays addressable inside one element)
+            pr = row_panels(R, W3 * 2, RB)
+            if pr < R and not drops:
+                nb = pr // RB
+                qkv = torch.empty(pr, W3, device=dev, dtype=T())
+                xn2, xr2 = xn.view(R, D), x_res.view(R, -1)
+                wo = self.wt("o", self.to_out)
+                nxt, fused = torch.empty(R, xr2.shape[1], device=dev, dtype=T()) if next_ln is not None else None, True
+                for r0 in range(0, R, pr):
+                    ops.linear(xn2[r0:r0 + pr], wqkv, bqkv, out=qkv)
+                    op = o[r0:r0 + pr]
+                    ops.favor_attention(qkv, pcf, op, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
+                                        0, inner, 2 * inner, nb, Lo, H, Ls, dh, m, not gen, eps)
+                    fused &= ops.linear_residual_ln(op, wo, bo, xr2[r0:r0 + pr], next_ln, nxt[r0:r0 + pr] if nxt is not None else None) is not None
+                return nxt.view(x_res.shape) if nxt is not None and fused else None
+            qkv = ops.linear(xn, wqkv, bqkv)
+            ops.favor_attention(qkv, pcf, o, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
+                                0, inner, 2 * inner, B, Lo, H, Ls, dh, m, not gen, eps)
             return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
         qk = ops.linear(xn, self.wcat("qk", [self.to_q, self.to_k]), None)  # [R, 2*inner]
         # q' [B,Lo,H,Ls,M_PAD]
@@ -1198,13 +1181,18 @@ class OuterProductMean(RFModule):
         return (RT.fused_outer and ops.is_h16(T()) and P == 32 and N in (64, 128) and Lr % 16 == 0
                 and self.to_out[1].weight.shape[0] == 288)
 
+    def _fold(self):
+        """(packed W * gamma, its row sums, W beta + bias) of ops.outer_fold, cached with the weights."""
+        lnm, lin = self.to_out[0], self.to_out[1]
+        return self.cached("outer_fold", lambda: ops.outer_fold(lin.weight.detach(), lnm.weight.detach(),
+                                                                 lnm.bias.detach(), lin.bias.detach()))
+
     def run_into(self, x_t, y_t, ln2, feat, feat_ld):
         """Fused form with the consumer's LayerNorm (PairUpdateWithMsa.ln_coevol_feat) in the epilogue: writes bf16
         feat[..., 0:288] directly; neither the 1024-wide tensor nor the fp32 result exists."""
-        lnm, lin = self.to_out[0], self.to_out[1]
-        wp, s_, c_ = self.cached("outer_fold", lambda: ops.outer_fold(lin.weight.detach(), lnm.weight.detach(),
-                                                                        lnm.bias.detach(), lin.bias.detach()))
-        return ops.outer_fused(x_t, y_t, wp, s_, c_, None, lnm.eps, ln2=(_f(ln2.weight), _f(ln2.bias), ln2.eps, feat, feat_ld))
+        wp, s_, c_ = self._fold()
+        return ops.outer_fused(x_t, y_t, wp, s_, c_, None, self.to_out[0].eps,
+                               ln2=(_f(ln2.weight), _f(ln2.bias), ln2.eps, feat, feat_ld))
 
     def run(self, x_t, y_t, N):
         """x_t, y_t: T [B, L, P, N] (MSA depth contiguous).  -> fp32 [B,L,L,out]"""
@@ -1215,8 +1203,7 @@ class OuterProductMean(RFModule):
         if self.fused_ok(P, N, Lr):
             # one kernel: outer product over the MSA depth -> LayerNorm(1024) (folded algebraically) -> Linear; the 1024-wide
             # tensor never leaves the chip (csrc/outer.hip)
-            wp, s_, c_ = self.cached("outer_fold", lambda: ops.outer_fold(lin.weight.detach(), lnm.weight.detach(),
-                                                                            lnm.bias.detach(), lin.bias.detach()))
+            wp, s_, c_ = self._fold()
             out = torch.empty(B, Lr, Lr, lin.weight.shape[0], device=x_t.device, dtype=F32)
             return ops.outer_fused(x_t, y_t, wp, s_, c_, out, lnm.eps)
         co = torch.empty(B, Lr, Lr, PP, device=x_t.device, dtype=T())
@@ -1256,14 +1243,7 @@ class OuterProductMean(RFModule):
 
     def forward(self, x, y=None):
         y = x if y is None else y
-        B, N, Lr, P = x.shape
-        Np = pad8(N)
-        mk = ops.zeros if Np != N else torch.empty  # only the K padding needs zeros
-        xt = mk(B, Lr, P, Np, device=x.device, dtype=T())
-        yt = mk(B, Lr, P, Np, device=x.device, dtype=T())
-        for src, dst in ((x, xt), (y, yt)):
-            ops.copy4d(src.contiguous(), (N * Lr * P, P, 1, Lr * P), dst, (Lr * P * Np, P * Np, Np, 1), (B, Lr, P, N))
-        return self.run(xt, yt, Np)
+        return self.run(*ops.outer_operands(x, y, T()))
 
 
 class PairUpdateWithMsa(RFModule):
@@ -1300,7 +1280,6 @@ class PairUpdateWithMsa(RFModule):
         B, N, Lr, D = msa.shape
         P = self.d_proj
         dev = msa.device
-        Np = pad8(N)
         mp_pre = ops.linear(ln(self.proj_msa[0], msa), self.wt("p", self.proj_msa[1]), _f(self.proj_msa[1].bias),
                             out_dtype=F32)
         mp = ln(self.proj_msa[2], mp_pre)  # T [B,N,L,P]
@@ -1312,12 +1291,7 @@ class PairUpdateWithMsa(RFModule):
         ops.copy4d(mp, (N * Lr * P, 0, P, 1), msa1d, (Lr * 2 * P, 0, 2 * P, 1), (B, 1, Lr, P), y_off=P)
         # transposed operands of the outer product: x_t[b,i,u,n] = mp ; y_t = mp * w   (rf.py:472-473)
         mpw = ops.scale_rows(mp, w, B * N * Lr, P)
-        mk = ops.zeros if Np != N else torch.empty  # only the K padding needs zeros
-        xt = mk(B, Lr, P, Np, device=dev, dtype=T())
-        yt = mk(B, Lr, P, Np, device=dev, dtype=T())
-        for src, dst in ((mp, xt), (mpw, yt)):
-            ops.copy4d(src, (N * Lr * P, P, 1, Lr * P), dst, (Lr * P * Np, P * Np, Np, 1), (B, Lr, P, N))
-        return msa1d, xt, yt, Np
+        return (msa1d,) + ops.outer_operands(mp, mpw, T())
 
     # ---- operand conditioning of the 16-bit modes (csrc/condition.hip; tools/precision_probe.py --pum-sweep) ------------------
     # At random init the 1-D features and the projected feature tensor are a per-sample constant plus a part ~20x smaller that
