@@ -486,6 +486,19 @@ int rf_instnorm_bwd(const float* g, const void* act_out, int act_dtype, const vo
 int64_t rf_layernorm_bwd_ws_bytes(int64_t rows, int D);
 int rf_layernorm_bwd(const float* x, const float* g, const float* gamma, float eps, void* dx, int dx_dtype, float* dgamma,
                      float* dbeta, int64_t rows, int D, void* workspace, int64_t ws_bytes, void* stream);
+/* LayerNorm forward and backward of operand-typed rows in one pass (OuterProductMean's backward: x = the recomputed outer
+ * products, g = the gradient behind the Linear, both of `dtype` = the 16-bit type or RF_F32, as the GEMMs wrote them):
+ *   z  = xhat gamma + beta                                         (of dtype: the weight gradient's operand)
+ *   dx = rstd * (g gamma - mean(g gamma) - xhat * mean(g gamma xhat))   (of dtype: the following contractions' operand)
+ *   dgamma[c] (+)= sum_rows g xhat,  dbeta[c] (+)= sum_rows g       (fp32, either may be NULL; accumulate != 0: added to
+ *                                                                   what they hold, so a caller can walk a tensor in pieces)
+ * Statistics are recomputed in fp32 from x (two-pass, like rf_layernorm); nothing of the forward is needed.  dx may alias g and
+ * z may alias x.  D <= 1024, D % 8 == 0 (16-bit) / D % 4 == 0 (fp32), 16-byte aligned tensors, else RF_EALIGN.  The column sums
+ * go through per-block partials added in block order (no atomics).  Workspace: rf_layernorm_bwd_fused_ws_bytes bytes. */
+int64_t rf_layernorm_bwd_fused_ws_bytes(int64_t rows, int D);
+int rf_layernorm_bwd_fused(const void* x, const void* g, int dtype, const float* gamma, const float* beta, float eps, void* dx,
+                           void* z, float* dgamma, float* dbeta, int accumulate, int64_t rows, int D, void* workspace,
+                           int64_t ws_bytes, void* stream);
 /* out[0] = max_e |x[e]| over n fp32 elements (the power-of-two gradient scale of the fp16 build); workspace >= 4096 bytes. */
 int rf_absmax(const float* x, int64_t n, float* out, void* workspace, int64_t ws_bytes, void* stream);
 

@@ -105,6 +105,8 @@ PROTOTYPES = {
     "rf_instnorm_bwd": [vp, vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, i32, i64, i32, vp, i64, vp],
     "rf_layernorm_bwd_ws_bytes": [i64, i32],  # returns int64
     "rf_layernorm_bwd": [vp, vp, vp, f32, vp, i32, vp, vp, i64, i32, vp, i64, vp],
+    "rf_layernorm_bwd_fused_ws_bytes": [i64, i32],  # returns int64
+    "rf_layernorm_bwd_fused": [vp, vp, i32, vp, vp, f32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp],
     "rf_absmax": [vp, i64, vp, vp, i64, vp],
     "rf_linattn_normalize_bwd": [vp, i64, vp, i64, vp, i32, i64, i64, i32, vp],
     "rf_relu_feature_bwd": [vp, vp, vp, i32, i64, i32, i32, vp],
@@ -130,6 +132,7 @@ def _load(path):
     handle.rf_channel_mean_ws_bytes.restype = C.c_int64
     handle.rf_conv_wgrad_ws_bytes.restype = C.c_int64
     handle.rf_layernorm_bwd_ws_bytes.restype = C.c_int64
+    handle.rf_layernorm_bwd_fused_ws_bytes.restype = C.c_int64
     handle.rf_build_info.restype = C.c_char_p
     handle.rf_build_info.argtypes = []
     return handle

@@ -7,6 +7,8 @@ A module gains a backward pass with four things on its class, next to the forwar
   * `_record(x, tape)`, the forward() body with the boundary layout conversion, and `_backward_from_autograd`, its mirror image
     (RecordingModule's default serves a module whose boundary needs none);
   * `_backward_children()`: the sub-modules enable_backward() switches along.
+A module of several inputs (OuterProductMean) sets `_rf_n_inputs = n` on its class: `_record(x_1 .. x_n, tape)` (an optional
+input may be None), and `_backward_from_autograd` receives a tuple of n "wanted" flags and returns a tuple of n gradients.
 _RecordedFn below is the one autograd Function of the package: it ties them to torch.autograd."""
 import math
 
@@ -93,15 +95,15 @@ def _param_grads(mod, grads, s):
 
 
 class _RecordedFn(torch.autograd.Function):
-    """forward() of a module that opted in, under grad mode: apply(mod, x, *mod.parameters()).  Runs mod._record into a fresh
-    tape; the backward hands the output gradients to mod._backward_from_autograd and spreads its {param: grad} over the
-    parameters.  fp16 power-of-two scale (_grad_scale): chosen here over the raw output gradients, applied and taken off dx by
+    """forward() of a module that opted in, under grad mode: apply(mod, x, *mod.parameters()), or with mod._rf_n_inputs = n
+    apply(mod, x_1 .. x_n, *mod.parameters()).  Runs mod._record into a fresh tape; the backward hands the output gradients to
+    mod._backward_from_autograd and spreads its {param: grad} over the parameters (and its n input gradients over the inputs).  fp16 power-of-two scale (_grad_scale): chosen here over the raw output gradients, applied and taken off dx by
     the adaptor, taken off the parameter gradients here -- unless the module scales its own operands (_rf_scales_own_grads)."""
 
     @staticmethod
-    def forward(ctx, mod, x, *params):
+    def forward(ctx, mod, *args):
         tape = {}
-        out = mod._record(x, tape)
+        out = mod._record(*args[:mod._rf_n_inputs], tape)
         ctx.mod, ctx.tape = mod, tape
         return out
 
@@ -109,9 +111,12 @@ class _RecordedFn(torch.autograd.Function):
     def backward(ctx, *gs):
         mod = ctx.mod
         s = 1.0 if mod._rf_scales_own_grads else _grad_scale([g.float().contiguous() for g in gs])
-        dx, grads = mod._backward_from_autograd(ctx.tape, gs, s, ctx.needs_input_grad[1])
+        n = mod._rf_n_inputs
+        want = ctx.needs_input_grad[1:1 + n]
+        dxs, grads = mod._backward_from_autograd(ctx.tape, gs, s, want[0] if n == 1 else want)
         ctx.tape = None
-        return (None, dx if ctx.needs_input_grad[1] else None) + _param_grads(mod, grads, s)
+        dxs = (dxs,) if n == 1 else tuple(dxs)
+        return (None,) + tuple(d if w else None for d, w in zip(dxs, want)) + _param_grads(mod, grads, s)
 
 
 def _pre_norm_residual_bwd(g, sub_backward, sub_tape, x_in, lnm, grads):

@@ -1,5 +1,5 @@
-// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172) and of the pair axial attention (end of
-// file) on gfx950: the weight gradient of a
+// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172), of the pair axial attention (end of
+// file) and of OuterProductMean (rf_layernorm_bwd_fused) on gfx950: the weight gradient of a
 // stride-1 "same" convolution (pixel contraction), InstanceNorm2d(affine) backward, LayerNorm backward, and the absolute
 // maximum the fp16 build scales its gradients by.  Input gradients of the convolutions / Linears run on rf_gemm (the forward's
 // implicit-GEMM engine with a repacked weight); these kernels are what the forward does not already have.
@@ -463,15 +463,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* x, cons
 }
 
 // dbeta[c] = sum_k partials[k][0][c], dgamma[c] = sum_k partials[k][1][c], block order, fp64
+// (acc: the sum is added to what dgamma / dbeta hold -- one caller-ordered fp32 addition per call)
 __global__ __launch_bounds__(256) void layernorm_bwd_finalize_kernel(const float* partials, float* dgamma, float* dbeta, int nblk,
-                                                                     int D) {
+                                                                     int D, int acc) {
   for (int c = blockIdx.x * 256 + threadIdx.x; c < 2 * D; c += gridDim.x * 256) {
     double t = 0.0;
     for (int k = 0; k < nblk; ++k) t += (double)partials[(int64_t)k * 2 * D + c];
     if (c < D) {
-      if (dbeta) dbeta[c] = (float)t;
+      if (dbeta) dbeta[c] = acc ? dbeta[c] + (float)t : (float)t;
     } else if (dgamma) {
-      dgamma[c - D] = (float)t;
+      dgamma[c - D] = acc ? dgamma[c - D] + (float)t : (float)t;
     }
   }
 }
@@ -491,7 +492,178 @@ extern "C" int rf_layernorm_bwd(const float* x, const float* g, const float* gam
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, s, x, g, gamma, eps, dx, dx_dtype, (float*)workspace, rows,
                      D);
   hipLaunchKernelGGL(layernorm_bwd_finalize_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, s, (const float*)workspace, dgamma,
-                     dbeta, (int)nblk, D);
+                     dbeta, (int)nblk, D, 0);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_layernorm_bwd_fused: LayerNorm forward AND backward of a row in one pass over operand-typed rows (OuterProductMean's
+// backward, model.py: x = the recomputed outer products, g = W^T dout, both as the GEMMs wrote them).  One wave per row,
+// 16-byte loads, the row lives in registers: statistics in fp32 (two-pass, like rf_layernorm), then z = LN(x) and
+// dx = rstd * (g gamma - mean(g gamma) - xhat * mean(g gamma xhat)) are written in the operand type, and the wave keeps the
+// column sums of g and g xhat of its rows in registers.  Per block they go to partials[block][2][D] (wave order), which
+// layernorm_bwd_finalize_kernel adds in block order: no atomics.  Against the chain rf_layernorm -> cast -> cast ->
+// rf_layernorm_bwd this reads x and g once instead of three times and never writes an fp32 copy of either.
+// dx may alias g and z may alias x: a wave has read its whole row (both reductions depend on it) before it writes.
+// ================================================================================================
+#define LNF_MAXD 1024
+
+// rows per block: depends on the shape only (the partials' order, hence the result's bits, never on the device)
+static int lnf_rows_per_block(int64_t rows) {
+  int rpb = 8;
+  while (rpb < 64 && rows / rpb > 2048) rpb *= 2;
+  return rpb;
+}
+
+template <bool H16>
+__global__ __launch_bounds__(256) void layernorm_bwd_fused_kernel(const void* x, const void* g, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, float eps, void* dx, void* z,
+                                                                  float* __restrict__ partials, int64_t rows, int D, int rpb) {
+  constexpr int VEC = H16 ? 8 : 4;            // elements of one 16-byte load
+  constexpr int NCH = LNF_MAXD / (64 * VEC);  // 16-byte chunks per lane: chunk index = lane + 64 k
+  __shared__ float red[4][2][LNF_MAXD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nch = D / VEC;
+  float gam[NCH][VEC], bet[NCH][VEC], pg[NCH][VEC], pgx[NCH][VEC];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = (lane + 64 * k) * VEC;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      const bool ok = lane + 64 * k < nch;
+      gam[k][e] = ok ? gamma[c + e] : 0.f;
+      bet[k][e] = ok ? beta[c + e] : 0.f;
+      pg[k][e] = pgx[k][e] = 0.f;
+    }
+  }
+  const float inv_d = 1.f / (float)D;
+  const int64_t r0 = (int64_t)blockIdx.x * rpb;
+  for (int rr = wave; rr < rpb; rr += 4) {
+    const int64_t r = r0 + rr;
+    if (r >= rows) break;  // (wave-uniform)
+    float xv[NCH][VEC], gv[NCH][VEC];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      const int64_t off = r * D + (int64_t)(lane + 64 * k) * VEC;
+      if (lane + 64 * k < nch) {
+        if (H16) {
+          const h16x8 xr = *(const h16x8*)((const h16_t*)x + off);
+          const h16x8 gr = *(const h16x8*)((const h16_t*)g + off);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) {
+            xv[k][e] = h2f((h16_t)xr[e]);
+            gv[k][e] = h2f((h16_t)gr[e]);
+          }
+        } else {
+          const float4 xr = *(const float4*)((const float*)x + off);
+          const float4 gr = *(const float4*)((const float*)g + off);
+          xv[k][0] = xr.x, xv[k][1] = xr.y, xv[k][2] = xr.z, xv[k][3] = xr.w;
+          gv[k][0] = gr.x, gv[k][1] = gr.y, gv[k][2] = gr.z, gv[k][3] = gr.w;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) xv[k][e] = gv[k][e] = 0.f;
+      }
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) s += xv[k][e];
+    }
+    const float mean = wave_sum(s) * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float d = lane + 64 * k < nch ? xv[k][e] - mean : 0.f;
+        q = fmaf(d, d, q);
+      }
+    const float rstd = rsqrtf(wave_sum(q) * inv_d + eps);
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        // (chunks past D hold x = g = gamma = 0: xhat is -mean rstd there, times a zero gradient)
+        const float xh = (xv[k][e] - mean) * rstd;
+        const float gg = gv[k][e] * gam[k][e];
+        xv[k][e] = xh;
+        m1 += gg;
+        m2 = fmaf(gg, xh, m2);
+        pg[k][e] += gv[k][e];
+        pgx[k][e] = fmaf(gv[k][e], xh, pgx[k][e]);
+      }
+    m1 = wave_sum(m1) * inv_d;
+    m2 = wave_sum(m2) * inv_d;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (lane + 64 * k >= nch) continue;
+      const int64_t off = r * D + (int64_t)(lane + 64 * k) * VEC;
+      float dv[VEC], zv[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        dv[e] = rstd * (gv[k][e] * gam[k][e] - m1 - xv[k][e] * m2);
+        zv[e] = fmaf(xv[k][e], gam[k][e], bet[k][e]);
+      }
+      if (H16) {
+        h16x8 dp, zp;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          dp[e] = (short)f2h(dv[e]);
+          zp[e] = (short)f2h(zv[e]);
+        }
+        *(h16x8*)((h16_t*)dx + off) = dp;
+        *(h16x8*)((h16_t*)z + off) = zp;
+      } else {
+        *(float4*)((float*)dx + off) = make_float4(dv[0], dv[1], dv[2], dv[3]);
+        *(float4*)((float*)z + off) = make_float4(zv[0], zv[1], zv[2], zv[3]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      red[wave][0][(lane + 64 * k) * VEC + e] = pg[k][e];
+      red[wave][1][(lane + 64 * k) * VEC + e] = pgx[k][e];
+    }
+  __syncthreads();
+  for (int c = threadIdx.x; c < D; c += 256) {
+    float tg = 0.f, tx = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      tg += red[w][0][c];
+      tx += red[w][1][c];
+    }
+    partials[(int64_t)blockIdx.x * 2 * D + c] = tg;
+    partials[(int64_t)blockIdx.x * 2 * D + D + c] = tx;
+  }
+}
+
+extern "C" int64_t rf_layernorm_bwd_fused_ws_bytes(int64_t rows, int D) {
+  if (rows <= 0 || D <= 0) return 0;
+  return (int64_t)cdiv(rows, lnf_rows_per_block(rows)) * 2 * D * (int64_t)sizeof(float);
+}
+
+extern "C" int rf_layernorm_bwd_fused(const void* x, const void* g, int dtype, const float* gamma, const float* beta, float eps,
+                                      void* dx, void* z, float* dgamma, float* dbeta, int accumulate, int64_t rows, int D,
+                                      void* workspace, int64_t ws_bytes, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!x || !g || !gamma || !beta || !dx || !z || rows <= 0 || D <= 0 || D > LNF_MAXD) return RF_EINVAL;
+  if (!workspace || ws_bytes < rf_layernorm_bwd_fused_ws_bytes(rows, D)) return RF_EINVAL;
+  // 16-byte row pieces: rows of whole vectors, 16-byte aligned bases
+  if (D % (dtype == RF_F32 ? 4 : 8) || ((uintptr_t)x % 16) || ((uintptr_t)g % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)z % 16))
+    return RF_EALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int rpb = lnf_rows_per_block(rows);
+  const unsigned nblk = cdiv(rows, rpb);
+  if (dtype == RF_F32)
+    hipLaunchKernelGGL(layernorm_bwd_fused_kernel<false>, dim3(nblk), dim3(256), 0, s, x, g, gamma, beta, eps, dx, z,
+                       (float*)workspace, rows, D, rpb);
+  else
+    hipLaunchKernelGGL(layernorm_bwd_fused_kernel<true>, dim3(nblk), dim3(256), 0, s, x, g, gamma, beta, eps, dx, z,
+                       (float*)workspace, rows, D, rpb);
+  hipLaunchKernelGGL(layernorm_bwd_finalize_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, s, (const float*)workspace, dgamma,
+                     dbeta, (int)nblk, D, accumulate ? 1 : 0);
   return rf_launch_status();
 }
 

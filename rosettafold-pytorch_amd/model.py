@@ -225,9 +225,11 @@ class RFModule(nn.Module):
 
 
 class RecordingModule(RFModule):
-    """An RFModule of one input with an opt-in HIP backward pass (the protocol: backward.py).  forward() is `_record(x, None)`;
-    once the module opted in and grad mode is on, it is `_record(x, tape)` inside the one autograd Function."""
+    """An RFModule with an opt-in HIP backward pass (the protocol: backward.py).  forward() is `_record(x, None)`; once the
+    module opted in and grad mode is on, it is `_record(x, tape)` inside the one autograd Function.  A module of several
+    tensor inputs sets _rf_n_inputs and brings its own forward() (OuterProductMean)."""
     _rf_backward = False            # enable_backward
+    _rf_n_inputs = 1                # tensor inputs of _record, each with a gradient of its own from _backward_from_autograd
     _rf_scales_own_grads = False    # True: _backward brings its own operands to the fp16 mode's scale (_RecordedFn leaves it at 1)
 
     def _backward_children(self):
@@ -1170,8 +1172,14 @@ class MsaUpdateUsingSelfAttention(RFModule):
 # ================================================================================================
 # pair update with MSA (outer product + 2-conv ResNet)
 # ================================================================================================
-class OuterProductMean(RFModule):
-    """rf.py:412-427."""
+class OuterProductMean(RecordingModule):
+    """rf.py:412-427.  enable_backward(): with grad mode on, forward(x, y=None) records, and loss.backward() fills the .grad of
+    the LayerNorm and the Linear of to_out and of x and y where they require grad (forward(x): x receives the sum of both
+    operands' gradients).  The backward (_backward) rebuilds everything from the 16-bit transposed operands whichever forward
+    path ran, in slabs of pair rows (RT.outer_bwd_slab_bytes).  run_rows (a block of rows) is refused while recording, and
+    P^2 and out_features must be multiples of 8.  run_into is called by PairUpdateWithMsa.run only, which does not go through
+    forward(): it never records, and enable_backward() here changes nothing for the enclosing module."""
+    _rf_n_inputs = 2
 
     def __init__(self, in_features, out_features):
         super().__init__()
@@ -1194,12 +1202,16 @@ class OuterProductMean(RFModule):
         return ops.outer_fused(x_t, y_t, wp, s_, c_, None, self.to_out[0].eps,
                                ln2=(_f(ln2.weight), _f(ln2.bias), ln2.eps, feat, feat_ld))
 
-    def run(self, x_t, y_t, N):
-        """x_t, y_t: T [B, L, P, N] (MSA depth contiguous).  -> fp32 [B,L,L,out]"""
+    def run(self, x_t, y_t, N, tape=None):
+        """x_t, y_t: T [B, L, P, N] (MSA depth contiguous).  -> fp32 [B,L,L,out].  tape: a dict that receives what _backward
+        needs (the two operands; same kernels, same numbers)."""
         B, Lr, P, _ = x_t.shape
         PP = P * P
         lnm = self.to_out[0]
         lin = self.to_out[1]
+        _check_backward_call(self, tape, None, PP, lin.weight.shape[0])
+        if tape is not None:
+            tape.update(x_t=x_t, y_t=y_t)
         if self.fused_ok(P, N, Lr):
             # one kernel: outer product over the MSA depth -> LayerNorm(1024) (folded algebraically) -> Linear; the 1024-wide
             # tensor never leaves the chip (csrc/outer.hip)
@@ -1223,6 +1235,7 @@ class OuterProductMean(RFModule):
     def run_rows(self, x_rows_t, y_t, N):
         """x_rows_t: T [B, h, P, N] (a block of rows), y_t: T [B, L, P, N] -> fp32 [B, h, L, out]: the general path of run()
         on a rectangular block (pair-track row-block sharding)."""
+        _check_backward_call(self, None, "rows")   # a block of rows IS the row-sharded call: refused while recording
         B, h, P, _ = x_rows_t.shape
         Lr = y_t.shape[1]
         PP = P * P
@@ -1242,8 +1255,112 @@ class OuterProductMean(RFModule):
         return out
 
     def forward(self, x, y=None):
-        y = x if y is None else y
-        return self.run(*ops.outer_operands(x, y, T()))
+        if _recording(self):
+            return _RecordedFn.apply(self, x, y, *self.parameters())
+        return self._record(x, y, None)
+
+    def _record(self, x, y, tape):
+        if tape is not None:
+            tape.update(n=x.shape[1], one=y is None)
+        return self.run(*ops.outer_operands(x, x if y is None else y, T()), tape=tape)
+
+    def backward_slab_rows(self, Lr, P):
+        """pair rows per slab of _backward: the slab's three P^2-wide tensors stay under RT.outer_bwd_slab_bytes"""
+        return max(1, min(Lr, RT.outer_bwd_slab_bytes // (3 * Lr * P * P * (2 if ops.is_h16(T()) else 4))))
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        g = gs[0] if gs[0].dtype == F32 and gs[0].is_contiguous() else gs[0].float().contiguous()
+        one = tape["one"]
+        (dx, dy), grads = self._backward(tape, g, s, want_x=want[0], want_y=want[1] or (one and want[0]))
+        B, Lr, P, Np = tape["x_t"].shape
+        N = tape["n"]
+        if one and dx is not None:
+            ops.axpby(dx, 1.0, dy, 1.0, dx)
+            dy = None
+        out = []
+        for d in (dx, dy):   # T-layout [B, L, P, Np] -> [B, N, L, P] (the inverse of ops.outer_operands), scale taken off
+            if d is None:
+                out.append(None)
+                continue
+            _unscale([d], s)
+            out.append(ops.copy4d(d, (Lr * P * Np, P * Np, Np, 1), torch.empty(B, N, Lr, P, device=d.device, dtype=F32),
+                                  (N * Lr * P, P, 1, Lr * P), (B, Lr, P, N)))
+        return tuple(out), grads
+
+    def _backward(self, tape, g, s=1.0, want_x=True, want_y=True):
+        """g: contiguous fp32 [B, L, L, out] gradient of the output (read only), s: the factor its 16-bit copies carry (the fp16
+        mode's scale).  Returns ((dx_t, dy_t) fp32 [B, L, P, Np] in the operands' transposed layout or None, {param: grad}), all
+        still times s.  Per sample and slab of rows i (no [B, L, L, P^2] tensor exists; every sum over slabs is an fp32 addition
+        in slab order):
+            o  = x_t[i] y_t^T                      rf_gemm, as the general forward writes it
+            dz = g W                               rf_gemm
+            do, z = LayerNorm backward / forward   rf_layernorm_bwd_fused, in place on dz / o; dgamma, dbeta accumulate
+            dW += g^T z, db += sum g               rf_conv_wgrad
+            dx_t[i] = do y, dy_t += do^T x[i]      rf_gemm (K chunked over the pair row; do transposed by rf_copy4d for dy)"""
+        x_t, y_t = tape["x_t"], tape["y_t"]
+        B, Lr, P, Np = x_t.shape
+        PP, dev, t = P * P, x_t.device, T()
+        lnm, lin = self.to_out[0], self.to_out[1]
+        Do = lin.weight.shape[0]
+        wt = self.wt_input_grad("w", lin)   # [P^2, out]
+        gamma, beta = _f(lnm.weight), _f(lnm.bias)
+        h = self.backward_slab_rows(Lr, P)
+        # the 16-bit GEMMs take 8-element pieces: with P % 8 the pair row's (j, v) / (i, u) runs are re-laid K-contiguous and
+        # zero-padded; otherwise dx reads do in place (K in chunks of P)
+        direct = t == F32 or P % 8 == 0
+        Kx = pad8(Lr * P)
+        co = torch.empty(h, Lr, PP, device=dev, dtype=t)
+        dz = torch.empty(h, Lr, PP, device=dev, dtype=t)
+        gt = torch.empty(h, Lr, Do, device=dev, dtype=t)
+        dgamma = ops.zeros(PP, device=dev, dtype=F32)   # (the slabs' column sums are added to them)
+        dbeta = ops.zeros(PP, device=dev, dtype=F32)
+        dW = db = None
+        dx_t = torch.empty(B, Lr, P, Np, device=dev, dtype=F32) if want_x else None
+        dy_t = torch.empty(B, Lr, P, Np, device=dev, dtype=F32) if want_y else None
+        first = True
+        for b in range(B):
+            if want_x:   # y as [Np, (j, v)]: the B operand of dx
+                y_n = (ops.zeros if Kx != Lr * P else torch.empty)(Np, Kx, device=dev, dtype=t)
+                ops.copy4d(y_t[b], (0, P * Np, Np, 1), y_n, (0, P, 1, Kx), (1, Lr, P, Np))
+            for i0 in range(0, Lr, h):
+                hs = min(h, Lr - i0)
+                o_s, d_s, g_s = co[:hs], dz[:hs], gt[:hs]
+                ops.gemm(x_t[b, i0:i0 + hs], y_t[b], o_s, hs * P, Lr * P, Np, c_row=(P, Lr * PP, P), c_col=(P, PP), exact=True)
+                ops.axpby(g[b, i0:i0 + hs], s, None, 0.0, g_s)
+                ops.linear(g_s, wt, None, out=d_s, exact=True)
+                if RT.outer_bwd_fused:
+                    ops.layernorm_bwd_fused(o_s, d_s, gamma, beta, eps=lnm.eps, dx=d_s, z=o_s, dgamma=dgamma, dbeta=dbeta)
+                    z_s = o_s
+                else:   # the same step on the older engines (A/B timing): three passes and two fp32 copies of the slab
+                    z_s = ln(lnm, o_s)
+                    do32, dg_s, dbt_s = ops.layernorm_bwd(ops.cast(o_s, F32), ops.cast(d_s, F32), gamma, eps=lnm.eps)
+                    ops.axpby(do32, 1.0, None, 0.0, d_s)
+                    ops.axpby(dgamma, 1.0, dg_s, 1.0, dgamma)
+                    ops.axpby(dbeta, 1.0, dbt_s, 1.0, dbeta)
+                dw_s, db_s = ops.conv_wgrad(g_s, z_s, 1, bias=True)
+                if first:
+                    dW, db = dw_s, db_s
+                else:
+                    ops.axpby(dW, 1.0, dw_s, 1.0, dW)
+                    ops.axpby(db, 1.0, db_s, 1.0, db)
+                first = False
+                if want_x:
+                    c = dx_t[b, i0:i0 + hs]
+                    if direct:
+                        ops.gemm(d_s, y_n, c, hs * P, Np, Lr * P, kc=P, a_row=(P, Lr * PP, P), a_ko=PP, b_row=(0, 0, Kx), b_ko=P,
+                                 exact=True)
+                    else:
+                        a = ops.zeros(hs * P, Kx, device=dev, dtype=t)
+                        ops.copy4d(d_s, (Lr * PP, PP, P, 1), a, (P * Kx, P, Kx, 1), (hs, Lr, P, P))
+                        ops.gemm(a, y_n, c, hs * P, Np, Kx, exact=True)
+                if want_y:   # do^T [(j, v), (i, u)] and x[i] as [Np, (i, u)]
+                    Ky = pad8(hs * P)
+                    mk = ops.zeros if Ky != hs * P else torch.empty
+                    a, x_n = mk(Lr * P, Ky, device=dev, dtype=t), mk(Np, Ky, device=dev, dtype=t)
+                    ops.copy4d(d_s, (Lr * PP, PP, P, 1), a, (P, P * Ky, 1, Ky), (hs, Lr, P, P))
+                    ops.copy4d(x_t[b, i0:i0 + hs], (0, P * Np, Np, 1), x_n, (0, P, 1, Ky), (1, hs, P, Np))
+                    ops.gemm(a, x_n, dy_t[b], Lr * P, Np, Ky, residual=dy_t[b] if i0 else None, exact=True)
+        return (dx_t, dy_t), {lin.weight: dW, lin.bias: db, lnm.weight: dgamma, lnm.bias: dbeta}
 
 
 class PairUpdateWithMsa(RFModule):

@@ -463,6 +463,37 @@ def layernorm_bwd(x, g, gamma, *, eps=1e-5, dx_dtype=F32):
     return dx, dgamma, dbeta
 
 
+def layernorm_bwd_fused(x, g, gamma, beta, *, eps=1e-5, dx=None, z=None, dgamma=None, dbeta=None):
+    """LayerNorm forward and backward over the last dim in one pass (rf_layernorm_bwd_fused): x, g contiguous of one shape and
+    one dtype (fp32 or the 16-bit type); statistics recomputed in fp32.  Returns (dx, z = LN(x), fp32 dgamma [D], fp32 dbeta [D]),
+    dx and z in the operands' dtype.  dx= / z= name the destinations (dx may be g, z may be x); dgamma= / dbeta= given: the
+    column sums are ADDED to them (a tensor walked in pieces, in the caller's order)."""
+    D = x.shape[-1]
+    rows = x.numel() // D
+    dx = torch.empty(x.shape, device=x.device, dtype=x.dtype) if dx is None else dx
+    z = torch.empty(x.shape, device=x.device, dtype=x.dtype) if z is None else z
+    _need_cuda(x, g, gamma, beta, dx, z, dgamma, dbeta)
+    for t in (g, dx, z):
+        if t.dtype != x.dtype or tuple(t.shape) != tuple(x.shape) or not (t.is_contiguous() and x.is_contiguous()):
+            raise ValueError("layernorm_bwd_fused: contiguous x, g, dx and z of one shape and one dtype")
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("layernorm_bwd_fused: pass both dgamma and dbeta to accumulate, or neither")
+    for t in (gamma, beta, dgamma, dbeta):
+        if t is not None and (t.dtype != F32 or t.numel() != D or not t.is_contiguous()):
+            raise ValueError("layernorm_bwd_fused: contiguous fp32 gamma / beta / dgamma / dbeta of D elements")
+    acc = dgamma is not None
+    if not acc:
+        dgamma = torch.empty(D, device=x.device, dtype=F32)
+        dbeta = torch.empty(D, device=x.device, dtype=F32)
+    ws_bytes = int(lib.rf_layernorm_bwd_fused_ws_bytes(rows, D))
+    if ws_bytes <= 0:
+        raise ValueError(f"layernorm_bwd_fused: unsupported shape {tuple(x.shape)}")
+    ws = torch.empty(ws_bytes, device=x.device, dtype=torch.uint8)
+    check(lib.rf_layernorm_bwd_fused(ptr(x), ptr(g), dcode(x.dtype), ptr(gamma), ptr(beta), float(eps), ptr(dx), ptr(z), ptr(dgamma),
+                                     ptr(dbeta), int(acc), rows, D, ptr(ws), ws_bytes, stream()), "rf_layernorm_bwd_fused")
+    return dx, z, dgamma, dbeta
+
+
 def absmax(xs):
     """max |x| over fp32 tensors (rf_absmax; one host read for the whole list)."""
     _need_cuda(*xs)

@@ -32,6 +32,12 @@ class _Runtime:
     fused_outer_ln = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER_LN", "0")))  # LayerNorm(1024) in the outer-product GEMM epilogue
     fused_tied = not bool(int(__import__("os").environ.get("RF_NO_FUSED_TIED", "0")))  # tied-attention logits + softmax in one launch
     fused_outer = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER", "0")))  # outer product -> LN -> Linear in one kernel
+    # OuterProductMean backward (model.py): the pair picture is walked in slabs of rows whose three P^2-wide tensors (outer
+    # products / LN(o), dz / do, do transposed) together stay under this many bytes; RF_OUTER_BWD_SLAB_MB sets it.  The
+    # LayerNorm step of a slab is one launch of rf_layernorm_bwd_fused; RF_NO_FUSED_OUTER_BWD=1 runs it as the chain of the
+    # older engines (rf_layernorm, two casts, rf_layernorm_bwd) for A/B timing (tools/outer_backward_bench.py).
+    outer_bwd_slab_bytes = int(float(__import__("os").environ.get("RF_OUTER_BWD_SLAB_MB", "6")) * (1 << 20))
+    outer_bwd_fused = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER_BWD", "0")))
     tied_v2 = not bool(int(__import__("os").environ.get("RF_TIED_V1", "0")))  # head-major q|k|v + collapsed weights + A.V kernel
     tied_fold_w = not bool(int(__import__("os").environ.get("RF_TIED_NO_FOLD", "0")))  # position weights folded into q by the projection's epilogue
     # pair-track row blocks (shard.forward_row_sharded): how the attention direction that crosses the blocks is computed --
