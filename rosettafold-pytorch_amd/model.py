@@ -17,6 +17,7 @@ exact fp32 tiles for parity runs); LayerNorm / InstanceNorm / softmax statistics
 SE(3) structure module is fp32 end to end, as in the reference (se3_modules.py:164).
 """
 import math
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -33,19 +34,7 @@ N_IDX, CA_IDX, C_IDX = 0, 1, 2  # rf.py:15
 M_FEAT = 266   # performer nb_features = int(64 * ln 64)
 M_PAD = 288    # padded to a multiple of 32 for the MFMA K loop
 VT_ROWS = 80   # 64 value rows + the ones row (k' sums) padded to a multiple of 16
-
-
-def row_panels(rows, bytes_per_row, unit):
-    """Split `rows` into equal panels of whole `unit`s (unit % 256 == 0 keeps every panel on the persistent GEMM path) whose
-    intermediate stays under RT.mall_panel_bytes.  Returns the panel length (== rows when no split applies)."""
-    cap = RT.mall_panel_bytes
-    if cap <= 0 or rows * bytes_per_row <= cap or rows % unit:
-        return rows
-    units = rows // unit
-    for n in range(2, units + 1):
-        if units % n == 0 and (rows // n) * bytes_per_row <= cap and (rows // n) >= 16384:
-            return rows // n
-    return rows
+_SeqGeometry = namedtuple("_SeqGeometry", "B Ls Lo ss so RB R S W2 ctx_scale")   # PerformerSelfAttention._geometry
 
 
 def set_compute_dtype(dtype):
@@ -223,6 +212,16 @@ class RFModule(nn.Module):
     def bcat(self, key, lins):
         return self.cached(("bcat", key), lambda: torch.cat([l.bias.detach() for l in lins], 0).float().contiguous())
 
+    def values_transposed(self, lin, xn, bias):
+        """lin(xn) written key-contiguous: xn T [B,N,L,D] -> v_t T [B,N,D,L], v_t[b,n,(h,d),l] = (W xn[b,n,l] + bias)[(h,d)]
+        (one GEMM per MSA row with the weight as the A operand, so the transposition costs no pass of its own): the B operand
+        of the attention . V GEMMs, which contract over l."""
+        B, N, Lr, D = xn.shape
+        v_t = torch.empty(B, N, D, Lr, device=xn.device, dtype=T())
+        ops.gemm(self.wt("v", lin), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
+                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=bias, bias_mode=L.BIAS_ROW)
+        return v_t
+
 
 class RecordingModule(RFModule):
     """An RFModule with an opt-in HIP backward pass (the protocol: backward.py).  forward() is `_record(x, None)`; once the
@@ -384,16 +383,6 @@ class FeedForward(RecordingModule):
             wp = self.cached("ffn_packed", lambda: ops.ffn_pack(self.net[0].weight, self.net[3].weight, T()))
             return ops.ffn_fused(xn, wp, _f(self.net[0].bias), _f(self.net[3].bias), x_res, next_ln)
         w1, b1, w2, b2 = self.wt("w1", self.net[0]), _f(self.net[0].bias), self.wt("w2", self.net[3]), _f(self.net[3].bias)
-        d_ff, R = w1.shape[0], xn.numel() // xn.shape[-1]
-        pr = row_panels(R, d_ff * xn.element_size(), 256) if x_res.is_contiguous() and xn.is_contiguous() else R
-        if pr < R:  # hidden panel stays in the Infinity Cache between the two GEMMs
-            xn2, xr2 = xn.view(R, -1), x_res.view(R, -1)
-            h = torch.empty(pr, d_ff, device=xn.device, dtype=xn.dtype)
-            nxt, fused = torch.empty(R, xr2.shape[1], device=xn.device, dtype=xn.dtype) if next_ln is not None else None, True
-            for r0 in range(0, R, pr):
-                ops.linear(xn2[r0:r0 + pr], w1, b1, act=L.ACT_RELU, out=h)
-                fused &= ops.linear_residual_ln(h, w2, b2, xr2[r0:r0 + pr], next_ln, nxt[r0:r0 + pr] if nxt is not None else None) is not None
-            return nxt.view(x_res.shape) if nxt is not None and fused else None
         h = ops.linear(xn, w1, b1, act=L.ACT_RELU)
         return ops.linear_residual_ln(h, w2, b2, x_res, next_ln)
 
@@ -592,6 +581,19 @@ class PositionWiseWeightFactor(RFModule):
         ops.poswise(q0, D, k, D, 0, self.d_head, self.d_head, w, None, 0, 0, 0, B, N, Lr, self.n_heads, self.scale, 1.0)
         return self.drop(w)
 
+    def weights_head_major(self, xn):
+        """xn: T [B,N,L,d] -> w fp32 [B,H,N,L], without the to_k projection over the N rows: per head
+        u[b,l,h,:] = W_k[h*dh:(h+1)*dh, :]^T to_q(x_0)[b,l,h*dh:(h+1)*dh], w = softmax_n(scale * xn . u)   (rf.py:205-217,
+        collapsed; to_k's bias is constant over n and drops out of the softmax)."""
+        B, N, Lr, D = xn.shape
+        H, dh = self.n_heads, self.d_head
+        q0 = self.query_proj(xn)
+        wkt = self.cached("wkT", lambda: self.to_k[0].weight.detach().t().contiguous().to(T()))
+        u = torch.empty(B, Lr, H, D, device=xn.device, dtype=T())
+        ops.gemm(q0, wkt, u, B * Lr, D, dh, batch=(H, 1, 1), a_bs=(dh, 0, 0), a_row=(0, 0, D), b_bs=(dh, 0, 0),
+                 b_row=(0, 0, D), c_bs=(D, 0, 0), c_row=(0, 0, H * D))
+        return self.drop(ops.poswise_collapsed(xn, u, self.scale))
+
     def weights_collapsed(self, msa, lnm, m):
         """1-head weights for the structure track, q side in fp32: w = softmax_n(scale * m[b,n,l,:] . u[b,l,:]) with
         u = to_q(LN(msa[:,0])) W_k  (to_k's bias is constant over n and drops out of the softmax).
@@ -669,9 +671,7 @@ class SoftTiedAttentionOverResidues(RFModule):
         bv, bo = _f(self.to_v.bias), _f(self.to_out.bias)
         if RT.condition and RT.condition_values and ops.is_h16(T()):
             bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))
-        v_t = torch.empty(B, N, D, Lr, device=dev, dtype=T())
-        ops.gemm(self.wt("v", self.to_v), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=bv, bias_mode=L.BIAS_ROW)
+        v_t = self.values_transposed(self.to_v, xn, bv)
         # logits[b,h,i,j] = sum_{n,d} q k   (contraction over N*dh, rf.py:254), softmax over j (rf.py:255)
         W3 = 3 * D
         att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
@@ -686,14 +686,21 @@ class SoftTiedAttentionOverResidues(RFModule):
                      b_bs=(N * Lr * W3, dh, 0), b_row=(0, 0, W3), b_ko=Lr * W3, kc=dh,
                      c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr))
             ops.tied_softmax(logits, att, att_sym, H)
-        # out[b,n,i,(h,d)] = sum_j att[b,h,i,j] v[b,n,h,j,d]   (rf.py:257-258)
-        out = torch.empty(B, N, Lr, D, device=dev, dtype=T())
+        out = self.attention_values(att, v_t)
+        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+        return att_sym, xn_next
+
+    def attention_values(self, att, v_t):
+        """out[b,n,i,(h,d)] = sum_j att[b,h,i,j] v[b,n,h,j,d]   (rf.py:257-258): att T [B,H,L,L], v_t T [B,N,D,L]
+        (values_transposed) -> T [B,N,L,D], one GEMM per (b, head) over all N rows."""
+        B, N, D, Lr = v_t.shape
+        H, dh = self.n_heads, self.d_head
+        out = torch.empty(B, N, Lr, D, device=v_t.device, dtype=T())
         ops.gemm(att, v_t, out, Lr, N * dh, Lr, batch=(B, H, 1),
                  a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
                  b_bs=(N * D * Lr, dh * Lr, 0), b_row=(dh, D * Lr, Lr),
                  c_bs=(N * Lr * D, dh, 0), c_row=(0, 0, D), c_col=(dh, Lr * D))
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
-        return att_sym, xn_next
+        return out
 
     def attend_head_major(self, xn, x_res, want_att, next_ln=None, drops=()):
         """The bench path (csrc/tied.hip): one projection GEMM writes q|k|v head-major [B,N,3H,L,32] (every contraction
@@ -703,16 +710,9 @@ class SoftTiedAttentionOverResidues(RFModule):
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
         dev = xn.device
-        pw = self.poswise_weight
         G = 3 * H
         lins = [self.to_q, self.to_k, self.to_v]
-        # u[b,l,h,:] = W_k[h*dh:(h+1)*dh, :]^T to_q(x_0)[b,l,h*dh:(h+1)*dh]   (rf.py:205-217, collapsed)
-        q0 = pw.query_proj(xn)
-        wkt = pw.cached("wkT", lambda: pw.to_k[0].weight.detach().t().contiguous().to(T()))
-        u = torch.empty(B, Lr, H, D, device=dev, dtype=T())
-        ops.gemm(q0, wkt, u, B * Lr, D, dh, batch=(H, 1, 1), a_bs=(dh, 0, 0), a_row=(0, 0, D), b_bs=(dh, 0, 0),
-                 b_row=(0, 0, D), c_bs=(D, 0, 0), c_row=(0, 0, H * D))
-        w = pw.drop(ops.poswise_collapsed(xn, u, pw.scale))  # fp32 [B,H,N,L]
+        w = self.poswise_weight.weights_head_major(xn)  # fp32 [B,H,N,L]
         qkv = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
         # q * w * d_head^-0.5 (rf.py:252) in the projection's epilogue, on the fp32 accumulators: q is rounded once, after
         # the scaling, and the logits kernel neither stages the weights nor rescales its fragments (round 2: 15-20 us of VALU)
@@ -742,13 +742,7 @@ class SoftTiedAttentionOverResidues(RFModule):
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
         dev = xn.device
-        pw = self.poswise_weight
-        q0 = pw.query_proj(xn)
-        wkt = pw.cached("wkT", lambda: pw.to_k[0].weight.detach().t().contiguous().to(T()))
-        u = torch.empty(B, Lr, H, D, device=dev, dtype=T())
-        ops.gemm(q0, wkt, u, B * Lr, D, dh, batch=(H, 1, 1), a_bs=(dh, 0, 0), a_row=(0, 0, D), b_bs=(dh, 0, 0),
-                 b_row=(0, 0, D), c_bs=(D, 0, 0), c_row=(0, 0, H * D))
-        w = pw.drop(ops.poswise_collapsed(xn, u, pw.scale))  # fp32 [B,H,N,L]
+        w = self.poswise_weight.weights_head_major(xn)  # fp32 [B,H,N,L]
         G = 2 * H
         lins = [self.to_q, self.to_k]
         qk = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
@@ -757,18 +751,10 @@ class SoftTiedAttentionOverResidues(RFModule):
         att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
         att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
         ops.tied_logits(qk[:, :, 0:H], qk[:, :, H:], att, att_sym)
-        # v transposed: v_t[b,n,(h,d),l];  out[b,n,i,(h,d)] = sum_j att[b,h,i,j] v[b,n,h,j,d]   (rf.py:257-258)
         bv, bo = _f(self.to_v.bias), _f(self.to_out.bias)
         if RT.condition and RT.condition_values:
             bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))
-        v_t = torch.empty(B, N, D, Lr, device=dev, dtype=T())
-        ops.gemm(self.wt("v", self.to_v), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=bv, bias_mode=L.BIAS_ROW)
-        out = torch.empty(B, N, Lr, D, device=dev, dtype=T())
-        ops.gemm(att, v_t, out, Lr, N * dh, Lr, batch=(B, H, 1),
-                 a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
-                 b_bs=(N * D * Lr, dh * Lr, 0), b_row=(dh, D * Lr, Lr),
-                 c_bs=(N * Lr * D, dh, 0), c_row=(0, 0, D), c_col=(dh, Lr * D))
+        out = self.attention_values(att, self.values_transposed(self.to_v, xn, bv))
         xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
         return att_sym, xn_next
 
@@ -838,7 +824,7 @@ class PerformerSelfAttention(RecordingModule):
         sequence: pair-track row blocks).  Linear attention communicates contexts, not maps: the local
         k'^T [v | 1] sums are all-reduced (fp32) before the queries are applied (rf.py:505-518 semantics unchanged).
         tape: a dict that receives what _backward needs (xn, the axis, the output dropout's records); the kernels are the same."""
-        B, L1, L2, D = xn.shape
+        B, D = xn.shape[0], xn.shape[-1]
         _check_backward_call(self, tape, seq_group, D)
         if tape is not None:
             if not self.generalized:
@@ -846,15 +832,8 @@ class PerformerSelfAttention(RecordingModule):
             tape.update(xn=xn, axis=axis, drops=[])
         recs = tape["drops"] if tape is not None else None
         H, dh, inner = self.heads, self.dim_head, self.inner
-        dev = xn.device
-        Ls, Lo = (L1, L2) if axis == 1 else (L2, L1)
-        ss, so = (L2, 1) if axis == 1 else (1, L2)  # row strides of the sequence / outer index
-        RB = L1 * L2
-        R = B * RB
-        W2 = 2 * inner
-        S = B * Lo * H
+        geo = self._geometry(xn.shape, axis, seq_group)
         m = self.fast_attention.projection_matrix.shape[0]
-        pc = self.proj_scaled()
         gen = self.generalized
         if seq_group is not None and not gen:
             raise NotImplementedError("sequence-sharded attention is built for the generalized (ReLU) feature map of the pair "
@@ -865,46 +844,73 @@ class PerformerSelfAttention(RecordingModule):
             bqkv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out, lead=(self.to_q, self.to_k)))
             bv = bqkv[2 * inner:]
         if seq_group is None and RT.fused_favor and ops.is_h16(T()) and dh == 64 and m == M_FEAT and (
-                Ls in (64, 128, 256) or (gen and Ls > 256 and Ls % 256 == 0)):
+                geo.Ls in (64, 128, 256) or (gen and geo.Ls > 256 and geo.Ls % 256 == 0)):
             # fused path: one projection GEMM (q|k|v) + one persistent kernel; q', k', ctx never leave the chip
+            Ls, Lo, ss, so, RB = geo.Ls, geo.Lo, geo.ss, geo.so, geo.RB
             W3 = 3 * inner
-            o = torch.empty(R, inner, device=dev, dtype=T())
-            pcf = pc if gen else self.proj_scaled(log2e=True)
+            o = torch.empty(geo.R, inner, device=xn.device, dtype=T())
+            pcf = self.proj_scaled(log2e=not gen)
             eps = 1e-3 if gen else 1e-4
-            wqkv = self.wcat("qkv", [self.to_q, self.to_k, self.to_v])
-            # whole batch elements per panel (RB rows each: any axis stays addressable inside one element)
-            pr = row_panels(R, W3 * 2, RB)
-            if pr < R and not drops:
-                nb = pr // RB
-                qkv = torch.empty(pr, W3, device=dev, dtype=T())
-                xn2, xr2 = xn.view(R, D), x_res.view(R, -1)
-                wo = self.wt("o", self.to_out)
-                nxt, fused = torch.empty(R, xr2.shape[1], device=dev, dtype=T()) if next_ln is not None else None, True
-                for r0 in range(0, R, pr):
-                    ops.linear(xn2[r0:r0 + pr], wqkv, bqkv, out=qkv)
-                    op = o[r0:r0 + pr]
-                    ops.favor_attention(qkv, pcf, op, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
-                                        0, inner, 2 * inner, nb, Lo, H, Ls, dh, m, not gen, eps)
-                    fused &= ops.linear_residual_ln(op, wo, bo, xr2[r0:r0 + pr], next_ln, nxt[r0:r0 + pr] if nxt is not None else None) is not None
-                return nxt.view(x_res.shape) if nxt is not None and fused else None
-            qkv = ops.linear(xn, wqkv, bqkv)
+            qkv = ops.linear(xn, self.wcat("qkv", [self.to_q, self.to_k, self.to_v]), bqkv)
             ops.favor_attention(qkv, pcf, o, (RB * W3, so * W3, ss * W3, dh), (RB * inner, so * inner, ss * inner),
                                 0, inner, 2 * inner, B, Lo, H, Ls, dh, m, not gen, eps)
             return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
-        qk = ops.linear(xn, self.wcat("qk", [self.to_q, self.to_k]), None)  # [R, 2*inner]
-        # q' [B,Lo,H,Ls,M_PAD]
-        dq = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=T())
-        ops.gemm(qk, pc, dq, Ls * H, M_PAD, dh, batch=(B, Lo, 1),
+        o = self._linear_attention(xn, geo, bv, seq_group)[-1]
+        return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
+
+    def _geometry(self, shape, axis, seq_group=None):
+        """How the sequences of xn [B, L1, L2, D] along `axis` are addressed: their length Ls and number per sample Lo, the row
+        strides ss / so of the sequence / outer index, rows per sample RB and in all R, sequences times heads S, the q|k row
+        width W2 -- and the scale the context is stored with."""
+        B, L1, L2, _ = shape
+        Ls, Lo = (L1, L2) if axis == 1 else (L2, L1)
+        ss, so = (L2, 1) if axis == 1 else (1, L2)
+        # fp16 operands (range 65504): the context is a sum over the whole sequence, so it is stored scaled by 2^-ceil(log2 Ls_total)
+        # (on the fp32 accumulators, before the rounding) exactly as csrc/favor.hip does in the fused kernel; numerator and
+        # denominator of the final ratio carry the same power of two, the result is unchanged
+        ctx_scale = 1.0
+        if T() == torch.float16:
+            from . import shard
+            ctx_scale = 2.0 ** -math.ceil(math.log2(max(Ls * (shard.group_size(seq_group) if seq_group is not None else 1), 1)))
+        return _SeqGeometry(B, Ls, Lo, ss, so, L1 * L2, B * L1 * L2, B * Lo * self.heads, 2 * self.inner, ctx_scale)
+
+    def _features(self, geo, qk, off, act, dtype):
+        """[B, Lo, H, Ls, M_PAD] = act(x P^T), x = the q (off 0) or k (off inner) block of qk: phi with ACT_RELU_EPS, the
+        pre-activation z with ACT_NONE (the softmax features' input; in fp32, what the backward masks with)."""
+        B, Ls, Lo, ss, so, RB, _, _, W2, _ = geo
+        H, dh = self.heads, self.dim_head
+        out = torch.empty(B, Lo, H, Ls, M_PAD, device=qk.device, dtype=dtype)
+        ops.gemm(qk, self.proj_scaled(), out, Ls * H, M_PAD, dh, batch=(B, Lo, 1), a_off=off,
                  a_bs=(RB * W2, so * W2, 0), a_row=(H, ss * W2, dh),
                  c_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, 0), c_row=(H, M_PAD, Ls * M_PAD),
-                 act=L.ACT_RELU_EPS if gen else L.ACT_NONE, act_nvalid=m, act_eps=1e-3)
-        # k'^T [B,Lo,H,M_PAD,Ls]
-        kt = torch.empty(B, Lo, H, M_PAD, Ls, device=dev, dtype=T())
-        ops.gemm(pc, qk, kt, M_PAD, Ls, dh, batch=(B, Lo, H), b_off=inner,
+                 act=act, act_nvalid=self.fast_attention.projection_matrix.shape[0], act_eps=1e-3)
+        return out
+
+    def _features_t(self, geo, qk, off, act):
+        """The same features transposed, [B, Lo, H, M_PAD, Ls] (sequence index contiguous), in T."""
+        B, Ls, Lo, ss, so, RB, _, _, W2, _ = geo
+        H, dh = self.heads, self.dim_head
+        out = torch.empty(B, Lo, H, M_PAD, Ls, device=qk.device, dtype=T())
+        ops.gemm(self.proj_scaled(), qk, out, M_PAD, Ls, dh, batch=(B, Lo, H), b_off=off,
                  b_bs=(RB * W2, so * W2, dh), b_row=(0, 0, ss * W2),
                  c_bs=(Lo * H * M_PAD * Ls, H * M_PAD * Ls, M_PAD * Ls), c_row=(0, 0, Ls),
-                 act=L.ACT_RELU_EPS if gen else L.ACT_NONE, act_nvalid=-m, act_eps=1e-3)
-        if not gen:
+                 act=act, act_nvalid=-self.fast_attention.projection_matrix.shape[0], act_eps=1e-3)
+        return out
+
+    def _linear_attention(self, xn, geo, bv=None, seq_group=None):
+        """The unfused chain from xn (bv: the value bias of the conditioned form): returns
+        (qk [R, 2 inner], q' [B,Lo,H,Ls,M_PAD], k'^T [B,Lo,H,M_PAD,Ls], [v | 1 | 0]^T [B,Lo,H,80,Ls], context^T [S,80,M_PAD],
+        numerator | denominator fp32 [R * H, 80], o [R, inner])."""
+        B, Ls, Lo, ss, so, RB, R, S, W2, ctx_scale = geo
+        H, dh, inner = self.heads, self.dim_head, self.inner
+        dev = xn.device
+        D = xn.shape[-1]
+        act = L.ACT_RELU_EPS if self.generalized else L.ACT_NONE
+        qk = ops.linear(xn, self.wcat("qk", [self.to_q, self.to_k]), None)
+        dq = self._features(geo, qk, 0, act, T())
+        kt = self._features_t(geo, qk, inner, act)
+        if not self.generalized:
+            m = self.fast_attention.projection_matrix.shape[0]
             xs = (RB * W2, so * W2, dh, ss * W2)
             ops.favor_softmax_features(dq, qk, 0, xs, Lo, H, S, Ls, m, M_PAD, dh, 1, 0)
             ops.favor_softmax_features(kt, qk, inner, xs, Lo, H, S, Ls, m, M_PAD, dh, 0, 1)
@@ -915,15 +921,8 @@ class PerformerSelfAttention(RecordingModule):
         ops.gemm(self.wt("v", self.to_v), xn, vt, inner, Ls, D, batch=(B, Lo, 1),
                  b_bs=(RB * D, so * D, 0), b_row=(0, 0, ss * D),
                  c_bs=(Lo * H * VT_ROWS * Ls, H * VT_ROWS * Ls, 0), c_row=(dh, VT_ROWS * Ls, Ls),
-                 bias=bv, bias_mode=L.BIAS_ROW if bv is not None else None)
+                 bias=bv, bias_mode=L.BIAS_ROW)
         # context^T [S,80,M_PAD] = v^T k'
-        # fp16 operands (range 65504): the context is a sum over the whole sequence, so it is stored scaled by 2^-ceil(log2 Ls_total)
-        # (on the fp32 accumulators, before the rounding) exactly as csrc/favor.hip does in the fused kernel; numerator and
-        # denominator of the final ratio carry the same power of two, the result is unchanged
-        ctx_scale = 1.0
-        if T() == torch.float16:
-            from . import shard as _shard
-            ctx_scale = 2.0 ** -math.ceil(math.log2(max(Ls * (_shard.group_size(seq_group) if seq_group is not None else 1), 1)))
         ctx = torch.empty(S, VT_ROWS, M_PAD, device=dev, dtype=T() if seq_group is None else F32)
         ops.gemm(vt, kt, ctx, VT_ROWS, M_PAD, Ls, batch=(S, 1, 1), a_bs=(VT_ROWS * Ls, 0, 0),
                  b_bs=(M_PAD * Ls, 0, 0), c_bs=(VT_ROWS * M_PAD, 0, 0), alpha=ctx_scale if seq_group is None else 1.0)
@@ -942,7 +941,7 @@ class PerformerSelfAttention(RecordingModule):
                  c_bs=(RB * H * VT_ROWS, so * H * VT_ROWS, VT_ROWS), c_row=(0, 0, ss * H * VT_ROWS))
         o = torch.empty(R, inner, device=dev, dtype=T())
         ops.linattn_normalize(num, VT_ROWS, o, dh, R * H, dh)
-        return project_into_residual(o, self.wt("o", self.to_out), bo, x_res, next_ln, drops, recs=recs)
+        return qk, dq, kt, vt, ctx, num, o
 
     def _backward(self, tape, g):
         """g: fp32 [B, L1, L2, D] gradient of what attend() added to x_res (overwritten).  q|k|v, the features, the context and
@@ -953,65 +952,31 @@ class PerformerSelfAttention(RecordingModule):
         The fp16 mode's context scale s = 2^-ceil(log2 Ls) is carried as in the forward: N and C hold s N, s C, so dN comes out
         as dN / s and dC = s phi_q^T (dN / s).  Returns (fp32 gradient of xn, {param: grad})."""
         xn, axis = tape["xn"], tape["axis"]
-        B, L1, L2, D = xn.shape
+        D = xn.shape[-1]
         H, dh, inner = self.heads, self.dim_head, self.inner
         dev = xn.device
-        Ls, Lo = (L1, L2) if axis == 1 else (L2, L1)
-        ss, so = (L2, 1) if axis == 1 else (1, L2)
-        RB = L1 * L2
-        R = B * RB
-        W2, W3 = 2 * inner, 3 * inner
-        S = B * Lo * H
+        geo = self._geometry(xn.shape, axis)
+        B, Ls, Lo, ss, so, RB, R, S, W2, cs = geo
+        W3 = 3 * inner
         V = VT_ROWS
         m = self.fast_attention.projection_matrix.shape[0]
-        pc = self.proj_scaled()
         pct = self.cached(("proj_t",), lambda: self.proj_scaled().t().contiguous())   # P^T [dh, M_PAD]
-        cs = 2.0 ** -math.ceil(math.log2(max(Ls, 1))) if T() == torch.float16 else 1.0
         for rec in tape["drops"]:
             _replay_dropout(g, rec)
         g_t = ops.cast(g.reshape(R, D), T())
         x2 = xn.reshape(R, D)
 
-        # ---- the forward's unfused chain, with the extra layouts the products below contract over
-        qk = ops.linear(x2, self.wcat("qk", [self.to_q, self.to_k]), None)   # [R, 2 inner]
-        seq_rows = dict(batch=(B, Lo, 1), a_bs=(RB * W2, so * W2, 0), a_row=(H, ss * W2, dh),
-                        c_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, 0), c_row=(H, M_PAD, Ls * M_PAD))
-
-        def feats(off, act, dtype):   # [B, Lo, H, Ls, M_PAD]: phi (act RELU_EPS) or the fp32 pre-activation z (act NONE)
-            out = torch.empty(B, Lo, H, Ls, M_PAD, device=dev, dtype=dtype)
-            ops.gemm(qk, pc, out, Ls * H, M_PAD, dh, a_off=off, act=act, act_nvalid=m, act_eps=1e-3, **seq_rows)
-            return out
-
-        def feats_t(off):             # phi^T [B, Lo, H, M_PAD, Ls]
-            out = torch.empty(B, Lo, H, M_PAD, Ls, device=dev, dtype=T())
-            ops.gemm(pc, qk, out, M_PAD, Ls, dh, batch=(B, Lo, H), b_off=off, b_bs=(RB * W2, so * W2, dh), b_row=(0, 0, ss * W2),
-                     c_bs=(Lo * H * M_PAD * Ls, H * M_PAD * Ls, M_PAD * Ls), c_row=(0, 0, Ls),
-                     act=L.ACT_RELU_EPS, act_nvalid=-m, act_eps=1e-3)
-            return out
-
-        zq, zk = feats(0, L.ACT_NONE, F32), feats(inner, L.ACT_NONE, F32)
-        phq, phk = feats(0, L.ACT_RELU_EPS, T()), feats(inner, L.ACT_RELU_EPS, T())
-        phq_t, kt = feats_t(0), feats_t(inner)
-        vt = ops.zeros(B, Lo, H, V, Ls, device=dev, dtype=T())
-        ones_row = ops.fill(torch.empty(B * Lo * H, Ls, device=dev, dtype=T()), 1.0)
-        ops.copy4d(ones_row, (0, 0, Ls, 1), vt, (0, 0, V * Ls, 1), (1, 1, B * Lo * H, Ls), y_off=dh * Ls)
-        ops.gemm(self.wt("v", self.to_v), xn, vt, inner, Ls, D, batch=(B, Lo, 1), b_bs=(RB * D, so * D, 0), b_row=(0, 0, ss * D),
-                 c_bs=(Lo * H * V * Ls, H * V * Ls, 0), c_row=(dh, V * Ls, Ls))
+        # ---- the forward's unfused chain, then the extra layouts the products below contract over
+        qk, phq, kt, vt, _, num, o = self._linear_attention(xn, geo)
+        zq, zk = self._features(geo, qk, 0, L.ACT_NONE, F32), self._features(geo, qk, inner, L.ACT_NONE, F32)
+        phk = self._features(geo, qk, inner, L.ACT_RELU_EPS, T())
+        phq_t = self._features_t(geo, qk, 0, L.ACT_RELU_EPS)
         v1 = torch.empty(R * H, V, device=dev, dtype=T())   # [v | 1 | 0] rows in the numerator's row layout
-        self._seq_transpose(vt, v1, B, Lo, H, Ls, so, ss, to_rows=True)
+        self._seq_transpose(vt, v1, geo, to_rows=True)
         per_seq = lambda r, c: dict(batch=(S, 1, 1), a_bs=(r, 0, 0), b_bs=(c, 0, 0))   # noqa: E731
-        ctx = torch.empty(S, V, M_PAD, device=dev, dtype=T())   # C^T (e-major), as the forward
-        ops.gemm(vt, kt, ctx, V, M_PAD, Ls, c_bs=(V * M_PAD, 0, 0), alpha=cs, **per_seq(V * Ls, M_PAD * Ls))
-        cj = torch.empty(S, M_PAD, V, device=dev, dtype=T())    # C (feature-major)
+        cj = torch.empty(S, M_PAD, V, device=dev, dtype=T())    # C (feature-major; the chain's context is C^T, e-major)
         ops.gemm(kt, vt, cj, M_PAD, V, Ls, c_bs=(M_PAD * V, 0, 0), alpha=cs, **per_seq(M_PAD * Ls, V * Ls))
         num_rows = dict(batch=(B, Lo, H), a_bs=(RB * H * V, so * H * V, V), a_row=(0, 0, ss * H * V))
-        num = torch.empty(R * H, V, device=dev, dtype=F32)
-        ops.gemm(phq, ctx, num, Ls, V, M_PAD, batch=(B, Lo, H),
-                 a_bs=(Lo * H * Ls * M_PAD, H * Ls * M_PAD, Ls * M_PAD), a_row=(0, 0, M_PAD),
-                 b_bs=(Lo * H * V * M_PAD, H * V * M_PAD, V * M_PAD),
-                 c_bs=(RB * H * V, so * H * V, V), c_row=(0, 0, ss * H * V))
-        o = torch.empty(R, inner, device=dev, dtype=T())
-        ops.linattn_normalize(num, V, o, dh, R * H, dh)
 
         # ---- output projection
         dwo, dbo = ops.conv_wgrad(g_t, o, 1, bias=True)
@@ -1020,7 +985,7 @@ class PerformerSelfAttention(RecordingModule):
         dn = torch.empty(R * H, V, device=dev, dtype=T())
         ops.linattn_normalize_bwd(num, V, do, dh, dn, V, R * H, dh)
         dn_t = torch.empty(B, Lo, H, V, Ls, device=dev, dtype=T())
-        self._seq_transpose(dn_t, dn, B, Lo, H, Ls, so, ss, to_rows=False)
+        self._seq_transpose(dn_t, dn, geo, to_rows=False)
         dc = torch.empty(S, M_PAD, V, device=dev, dtype=T())     # dC (feature-major)
         ops.gemm(phq_t, dn_t, dc, M_PAD, V, Ls, c_bs=(M_PAD * V, 0, 0), alpha=cs, **per_seq(M_PAD * Ls, V * Ls))
         dc_t = torch.empty(S, V, M_PAD, device=dev, dtype=T())   # dC^T (e-major)
@@ -1048,10 +1013,10 @@ class PerformerSelfAttention(RecordingModule):
         return dxn.view(xn.shape), {self.to_q.weight: dw[:inner], self.to_k.weight: dw[inner:W2], self.to_v.weight: dw[W2:],
                                     self.to_out.weight: dwo, self.to_out.bias: dbo}
 
-    @staticmethod
-    def _seq_transpose(seq_major, rows, B, Lo, H, Ls, so, ss, to_rows):
+    def _seq_transpose(self, seq_major, rows, geo, to_rows):
         """[B, Lo, H, 80, Ls] (sequence index innermost) <-> [B, L1, L2, H, 80] (the numerator's rows), one copy per sample."""
-        V = VT_ROWS
+        B, Ls, Lo, ss, so = geo[:5]
+        H, V = self.heads, VT_ROWS
         rs = (so * H * V, ss * H * V, V, 1)          # (o, n, h, e) in the row layout, past the sample offset
         ts = (H * V * Ls, 1, V * Ls, Ls)              # (o, n, h, e) in the sequence-major layout
         for b in range(B):
@@ -1711,57 +1676,54 @@ class MsaUpdateWithPairLayer(RFModule):
         slices are all-gathered so that msa is whole again on every rank."""
         if row_group is not None:
             return self._run_rows(msa, att, xn, row_group)
+        v_t = self._values(msa, xn)
+        if self.training and self.p_dropout and self.p_dropout > 0:
+            add_dropped(msa, lambda tmp: self._add_attention_values(att, v_t, tmp), (self.p_dropout,))
+            return self._feed_forward(msa, next_ln, drops=(self.ff.p_dropout,))
+        self._add_attention_values(att, v_t, msa)
+        return self._feed_forward(msa, next_ln)
+
+    def _run_rows(self, msa, att, xn, row_group):
+        """run() for a block of map rows (see there)."""
+        from . import shard
         B, N, Lr, D = msa.shape
-        H = self.n_heads
-        dv = D // H
-        v_t = torch.empty(B, N, D, Lr, device=msa.device, dtype=T())
-        lin = self.msa2value[1]
+        h = att.shape[2]
+        r0, r1 = shard.shard_range(Lr, shard.group_size(row_group), shard.group_rank(row_group))
+        if r1 - r0 != h:
+            raise ValueError(f"attention rows {h} do not match this rank's share {r1 - r0} of {Lr} positions")
+        v_t = self._values(msa, xn)
+        rows = torch.empty(B, N, h, D, device=msa.device, dtype=F32)   # msa[:, :, r0:r1]
+        if h > 0:
+            ops.copy4d(msa, (N * Lr * D, Lr * D, D, 1), rows, (N * h * D, h * D, D, 1), (B, N, h, D), x_off=r0 * D)
+            self._add_attention_values(att, v_t, rows)
+            self._feed_forward(rows, None)
+        shard.all_gather_positions(rows, msa, row_group)
+        return None
+
+    def _values(self, msa, xn):
+        """msa2value, key-contiguous: T [B,N,D,L] (xn: its pre-norm if the previous GEMM produced it)."""
         if xn is None:
             xn = ln(self.msa2value[0], msa)
-        ops.gemm(self.wt("v", lin), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=_f(lin.bias), bias_mode=L.BIAS_ROW)
-        # msa += att @ v  (rf.py:592-595), scattered back to [b,n,i,(h,d)]
-        def attv(dst):
-            ops.gemm(att, v_t, dst, Lr, N * dv, Lr, batch=(H, B, 1),
-                     a_bs=(B * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
-                     b_bs=(dv * Lr, N * D * Lr, 0), b_row=(dv, D * Lr, Lr),
-                     c_bs=(dv, N * Lr * D, 0), c_row=(0, 0, D), c_col=(dv, Lr * D), residual=dst)
-        if self.training and self.p_dropout and self.p_dropout > 0:
-            add_dropped(msa, attv, (self.p_dropout,))
-            return self.ff.fn[1].apply_residual(ln(self.ff.fn[0], msa), msa, next_ln, drops=(self.ff.p_dropout,))
-        attv(msa)
-        return self.ff.fn[1].apply_residual(ln(self.ff.fn[0], msa), msa, next_ln)
+        return self.values_transposed(self.msa2value[1], xn, _f(self.msa2value[1].bias))
 
-
-def _msa_update_rows(self, msa, att, xn, row_group):
-    """MsaUpdateWithPairLayer.run for a block of map rows (see there)."""
-    from . import shard
-    B, N, Lr, D = msa.shape
-    H = self.n_heads
-    dv = D // H
-    h = att.shape[2]
-    r0, r1 = shard.shard_range(Lr, shard.group_size(row_group), shard.group_rank(row_group))
-    if r1 - r0 != h:
-        raise ValueError(f"attention rows {h} do not match this rank's share {r1 - r0} of {Lr} positions")
-    v_t = torch.empty(B, N, D, Lr, device=msa.device, dtype=T())
-    lin = self.msa2value[1]
-    if xn is None:
-        xn = ln(self.msa2value[0], msa)
-    ops.gemm(self.wt("v", lin), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-             c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=_f(lin.bias), bias_mode=L.BIAS_ROW)
-    rows = torch.empty(B, N, h, D, device=msa.device, dtype=F32)   # msa[:, :, r0:r1]
-    if h > 0:
-        ops.copy4d(msa, (N * Lr * D, Lr * D, D, 1), rows, (N * h * D, h * D, D, 1), (B, N, h, D), x_off=r0 * D)
-        ops.gemm(att, v_t, rows, h, N * dv, Lr, batch=(H, B, 1),
+    def _add_attention_values(self, att, v_t, dst):
+        """dst += att @ v  (rf.py:592-595), scattered back to [b,n,i,(h,d)]: att T [H,B,h,L] (h query rows: all L, or a rank's
+        block), v_t T [B,N,D,L], dst fp32 [B,N,h,D]."""
+        H, B, h, Lr = att.shape
+        N, D = v_t.shape[1], v_t.shape[2]
+        dv = D // H
+        ops.gemm(att, v_t, dst, h, N * dv, Lr, batch=(H, B, 1),
                  a_bs=(B * h * Lr, h * Lr, 0), a_row=(0, 0, Lr),
                  b_bs=(dv * Lr, N * D * Lr, 0), b_row=(dv, D * Lr, Lr),
-                 c_bs=(dv, N * h * D, 0), c_row=(0, 0, D), c_col=(dv, h * D), residual=rows)
-        self.ff.fn[1].apply_residual(ln(self.ff.fn[0], rows), rows, None)
-    shard.all_gather_positions(rows, msa, row_group)
-    return None
+                 c_bs=(dv, N * h * D, 0), c_row=(0, 0, D), c_col=(dv, h * D), residual=dst)
 
+    def _feed_forward(self, x, next_ln, drops=()):
+        return self.ff.fn[1].apply_residual(ln(self.ff.fn[0], x), x, next_ln, drops=drops)
 
-MsaUpdateWithPairLayer._run_rows = _msa_update_rows
+    def forward(self, msa, pair):
+        msa = fresh_f32(msa)
+        self.run(msa, pair_to_att([self], pair.float().contiguous())[0])
+        return msa
 
 
 def pair_to_att(layers, pair, row_group=None):
@@ -1769,39 +1731,20 @@ def pair_to_att(layers, pair, row_group=None):
     one symmetrise+normalise pass, one GEMM for every layer's head logits, per-(layer,head) softmax.
     Returns a list of T [H,B,L,L] ([H,B,h,L] for a block of h pair rows: row_group, the transposed sub-blocks of the
     symmetrisation come from the other ranks)."""
-    B, Lr, _, Dp = pair.shape
-    H = layers[0].n_heads
-    nl = len(layers)
-    if row_group is not None:
-        return _pair_rows_to_att(layers, pair, row_group)
-    xs = ops.sym_layernorm(pair, T(), eps=layers[0].pair2att[1].eps)
+    B, h, Lr, Dp = pair.shape   # (h == L: the whole picture)
     holder = layers[0]
-
-    def fold():
-        ws, bs = zip(*[l.folded_att_proj() for l in layers])
-        return torch.cat(ws, 0).to(T()).contiguous(), torch.cat(bs, 0).contiguous()
-
-    wc, bc = holder.cached(("att_fold", nl), fold)
-    logits = ops.linear(xs, wc, bc, out_dtype=F32)  # [B,L,L,nl*H]
+    H, nl = holder.n_heads, len(layers)
     NH = nl * H
-    if holder.training:
-        dropout_(logits, _p(holder.pair2att[3]))   # rf.py:567: Dropout sits between the projection and the softmax
-    # every (layer, head) softmax in one launch: problem z = li*H + h is column z of the logits
-    att_all = torch.empty(nl, H, B, Lr, Lr, device=pair.device, dtype=T())
-    ops.softmax_batched(logits, 1, Lr * NH, NH, att_all, B * Lr * Lr, Lr, B * Lr, Lr, NH)
-    return [att_all[li] for li in range(nl)]
-
-
-def _pair_rows_to_att(layers, pair, row_group):
-    from . import shard
-    B, h, Lr, Dp = pair.shape
-    H, nl = layers[0].n_heads, len(layers)
-    NH = nl * H
-    xt = shard.transpose_row_sharded(pair, row_group)
-    sym = ops.axpby(pair, 0.5, xt, 0.5, torch.empty_like(pair))
-    one, zero = ops.fill(torch.empty(Dp, device=pair.device, dtype=F32), 1.0), ops.zeros(Dp, device=pair.device, dtype=F32)
-    xs = ops.layernorm(sym, one, zero, eps=layers[0].pair2att[1].eps, out_dtype=T())   # no affine: folded into the projection
-    holder = layers[0]
+    eps = holder.pair2att[1].eps
+    if row_group is None:
+        xs = ops.sym_layernorm(pair, T(), eps=eps)
+    else:
+        from . import shard
+        xt = shard.transpose_row_sharded(pair, row_group)
+        sym = ops.axpby(pair, 0.5, xt, 0.5, torch.empty_like(pair))
+        one, zero = ops.fill(torch.empty(Dp, device=pair.device, dtype=F32), 1.0), ops.zeros(Dp, device=pair.device, dtype=F32)
+        xs = ops.layernorm(sym, one, zero, eps=eps, out_dtype=T())
+    # (neither front applies the LayerNorm's affine: it is folded into the projection)
 
     def fold():
         ws, bs = zip(*[l.folded_att_proj() for l in layers])
@@ -1809,6 +1752,9 @@ def _pair_rows_to_att(layers, pair, row_group):
 
     wc, bc = holder.cached(("att_fold", nl), fold)
     logits = ops.linear(xs, wc, bc, out_dtype=F32)  # [B,h,L,nl*H]
+    if holder.training and row_group is None:   # (the row-sharded forward is the inference path: shard.forward_row_sharded)
+        dropout_(logits, _p(holder.pair2att[3]))   # rf.py:567: Dropout sits between the projection and the softmax
+    # every (layer, head) softmax in one launch: problem z = li*H + h is column z of the logits
     att_all = torch.empty(nl, H, B, h, Lr, device=pair.device, dtype=T())
     if h > 0:
         ops.softmax_batched(logits, 1, Lr * NH, NH, att_all, B * h * Lr, Lr, B * h, Lr, NH)
@@ -1836,15 +1782,6 @@ class MsaUpdateWithPair(RFModule):
         msa = fresh_f32(msa)
         self.run(msa, pair.float().contiguous())
         return msa
-
-
-def _msa_update_with_pair_layer_forward(self, msa, pair):
-    msa = fresh_f32(msa)
-    self.run(msa, pair_to_att([self], pair.float().contiguous())[0])
-    return msa
-
-
-MsaUpdateWithPairLayer.forward = _msa_update_with_pair_layer_forward
 
 
 # ================================================================================================

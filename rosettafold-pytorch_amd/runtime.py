@@ -43,11 +43,6 @@ class _Runtime:
     # pair-track row blocks (shard.forward_row_sharded): how the attention direction that crosses the blocks is computed --
     # "transpose" (two transposing exchanges, fused kernel) or "contexts" (all-reduce of the Performer contexts, GEMM chain)
     rowshard_attention = __import__("os").environ.get("RF_ROWSHARD_ATTENTION", "transpose")
-    # Producer -> consumer chains whose intermediate (q|k|v, feed-forward hidden) is larger than this many bytes are run
-    # panel by panel, so the intermediate panel is still in the 256 MB Infinity Cache when its consumer reads it
-    # (tools/mall_chunk_bench.py: projection + FAVOR alone 958 -> 842 us at 200 MB panels; inside the full forward the
-    # step time did not move, 432 vs 437 ms, so it is opt-in: RF_MALL_PANEL_MB=208).  0 disables.
-    mall_panel_bytes = int(__import__("os").environ.get("RF_MALL_PANEL_MB", "0")) << 20
 
 
 RT = _Runtime()
