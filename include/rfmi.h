@@ -377,6 +377,19 @@ int rf_graph_attention(const void* q, const void* k, const void* v, const void* 
 int rf_graph_attention_dropout(const void* q, const void* k, const void* v, const void* e, int dtype, float* out, int B, int L,
                                int H, int d, float scale, float p, uint64_t seed, uint64_t offset, void* stream);
 
+/* rf_graph_attention under an edge mask (the reference's edge_mask, rf.py:632-655): mask uint8 [B,L,L], nonzero = the edge
+ * (i, j) exists.  A row with at least one edge takes its softmax over its edges only: a masked column gets probability exactly 0
+ * and k, v, e at it are not read (the reference adds -1e9 to its logit, which underflows exp to 0: the same as -inf).  A row
+ * with no edge gets the uniform 1/L over all L columns (every logit 0).  That is what the reference computes whenever every
+ * scaled logit of the row lies in (-32, 32): the float32 spacing at 1e9 is 64, so x - 1e9 rounds to -1e9 for all of them; outside
+ * that bound the reference's empty row is quantisation noise of the -1e9 trick and is not followed.  The work of a row is
+ * proportional to its degree; columns are taken in ascending order, so an all-ones mask gives rf_graph_attention's bits.
+ * p = 0: no dropout; 0 < p < 1: rf_graph_attention_dropout's mask (the same keep/drop decision per [b, h, i, j] element).
+ * RF_EINVAL: mask NULL, p outside [0, 1), H*d > 256, d > 64 or not a power of two, (H*L + L + 8) * 4 bytes of LDS > 64 KB. */
+int rf_graph_attention_masked(const void* q, const void* k, const void* v, const void* e, int dtype, const uint8_t* mask,
+                              float* out, int B, int L, int H, int d, float scale, float p, uint64_t seed, uint64_t offset,
+                              void* stream);
+
 /* nn.Dropout for the training-mode forward (rf.py:18-28, 76, 217, 265-281, 346, 455, 567, 592, 1138; resnet.py:30):
  * y[e] = keep[e] ? x[e] / (1 - p) : 0 over n elements of dtype (fp32 or the build's 16-bit type; y may alias x), keep[e] =
  * word (e % 4) of Philox4x32-10(key = seed, counter = offset + e / 4) >= p * 2^32.  Stateless: the caller gives every call of a

@@ -80,6 +80,7 @@ PROTOTYPES = {
     "rf_tile_1d_feats": [vp, vp, i32, i64, i32, i32, i32, i32, vp],
     "rf_graph_attention": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, vp],
     "rf_graph_attention_dropout": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, u64, u64, vp],
+    "rf_graph_attention_masked": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, f32, u64, u64, vp],
     "rf_dropout": [vp, vp, i32, f32, u64, u64, i64, vp],
     "rf_dist_masked_attention": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "rf_knn_mask": [vp, vp, vp, i32, i32, i32, i32, vp],

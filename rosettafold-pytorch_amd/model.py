@@ -1801,8 +1801,8 @@ class GraphTransformer(RFModule):
         self.n_heads, self.d_out = n_heads, d_node_out
         self.p_dropout = p_dropout   # rf.py:628,658: att_dropout on the attention probabilities
 
-    def run(self, node, edge_t):
-        """node fp32 [B,L,dn]; edge_t T [B,L,L,de] -> fp32 [B,L,H*d]"""
+    def run(self, node, edge_t, mask=None):
+        """node fp32 [B,L,dn]; edge_t T [B,L,L,de] -> fp32 [B,L,H*d]; mask: None (the dense graph) or what edge_mask_u8 returns"""
         B, Lr, _ = node.shape
         H, d = self.n_heads, self.d_out
         nt = ops.cast(node, T())
@@ -1814,15 +1814,29 @@ class GraphTransformer(RFModule):
         if self.training and self.p_dropout and self.p_dropout > 0:
             off = RT.train_offset
             RT.train_offset += (B * H * Lr * Lr + 3) // 4
-            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, dropout=(self.p_dropout, RT.train_seed, off))
+            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, dropout=(self.p_dropout, RT.train_seed, off), mask=mask)
         else:
-            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale)
+            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, mask=mask)
         return ops.linear(nt, self.wt("u", self.node_update), _f(self.node_update.bias), out_dtype=F32, residual=upd)
 
     def forward(self, node_feat, edge_feat, edge_mask):
-        if edge_mask is not None:
-            raise NotImplementedError("edge_mask is unused on the forward path (rf.py:731)")
-        return self.run(node_feat.float().contiguous(), ops.cast(edge_feat.float().contiguous(), T()))
+        """edge_mask [B, L, L] (bool, uint8 or floating point; an edge exists where it equals 1) or None.  A node with at least
+        one edge attends to its edges only.  A node with no edge attends uniformly (1/L) to every node: what the reference's
+        (1 - mask) * -1e9 gives whenever every scaled logit lies in (-32, 32) (the float32 spacing at 1e9 is 64); outside that
+        bound the reference's empty row is rounding noise and is not followed."""
+        node = node_feat.float().contiguous()
+        return self.run(node, ops.cast(edge_feat.float().contiguous(), T()), edge_mask_u8(edge_mask, node))
+
+
+def edge_mask_u8(edge_mask, node):
+    """The reference's edge_mask (rf.py:635) as the kernel's operand: uint8 [B, L, L] on node's device, 1 where the mask equals 1.
+    No host read-back (the masked call stays capturable); any other shape raises ValueError before a launch."""
+    if edge_mask is None:
+        return None
+    B, Lr, _ = node.shape
+    if tuple(edge_mask.shape) != (B, Lr, Lr):
+        raise ValueError(f"edge_mask must have shape [{B}, {Lr}, {Lr}] (b l l), got {tuple(edge_mask.shape)}")
+    return (edge_mask.to(node.device) == 1).to(torch.uint8).contiguous()
 
 
 class GraphTransformerBlock(RFModule):
@@ -1834,13 +1848,14 @@ class GraphTransformerBlock(RFModule):
         self.ln = LayerNorm(d_node_out * n_heads)
         self.to_out = nn.Sequential(Linear(d_node_out * n_heads, d_node_in), nn.ELU())
 
-    def run(self, node, edge_t):
-        h = ln(self.ln, self.attn.run(node, edge_t))
+    def run(self, node, edge_t, mask=None):
+        h = ln(self.ln, self.attn.run(node, edge_t, edge_mask_u8(mask, node)))
         return ops.linear(h, self.wt("o", self.to_out[0]), _f(self.to_out[0].bias), out_dtype=F32, act=L.ACT_ELU,
                           residual=node)
 
     def forward(self, node_feat, edge_feat, edge_mask):
-        return self.run(node_feat.float().contiguous(), ops.cast(edge_feat.float().contiguous(), T()))
+        """edge_mask: as in GraphTransformer.forward."""
+        return self.run(node_feat.float().contiguous(), ops.cast(edge_feat.float().contiguous(), T()), edge_mask)
 
 
 def _node_input(mod, msa, seq_onehot, out_dtype=None):

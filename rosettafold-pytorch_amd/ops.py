@@ -707,9 +707,21 @@ def tile_1d_feats(msa1d, feat, feat_ld, c0, B, L_, P2):
           "rf_tile_1d_feats")
 
 
-def graph_attention(q, k, v, e, out, B, L_, H, d, scale, dropout=None):
-    """dropout = (p, seed, offset): the training-mode form (att_dropout on the probabilities, rf.py:658)."""
+def graph_attention(q, k, v, e, out, B, L_, H, d, scale, dropout=None, mask=None):
+    """dropout = (p, seed, offset): the training-mode form (att_dropout on the probabilities, rf.py:658).
+    mask: uint8 [B, L, L] on the device, nonzero = the edge (i, j) exists (the reference's edge_mask, rf.py:652-655).  A row takes
+    its softmax over its edges only (masked columns: probability exactly 0, their k, v, e are not read); a row with no edge gets
+    the uniform 1/L over all columns -- the reference's result whenever every scaled logit lies in (-32, 32), where the float32
+    x - 1e9 rounds to -1e9 for all of them (include/rfmi.h: rf_graph_attention_masked).  The work follows each row's degree."""
     _need_cuda(q, k, v, e, out)
+    if mask is not None:
+        if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, L_, L_) or not mask.is_contiguous():
+            raise ValueError(f"mask must be a contiguous uint8 [{B}, {L_}, {L_}] tensor, got {mask.dtype} {tuple(mask.shape)}")
+        _need_cuda(mask)
+        pd, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+        check(lib.rf_graph_attention_masked(ptr(q), ptr(k), ptr(v), ptr(e), dcode(q.dtype), ptr(mask), ptr(out), B, L_, H, d, scale,
+                                            float(pd), int(seed), int(off), stream()), "rf_graph_attention_masked")
+        return
     if dropout is not None:
         pd, seed, off = dropout
         check(lib.rf_graph_attention_dropout(ptr(q), ptr(k), ptr(v), ptr(e), dcode(q.dtype), ptr(out), B, L_, H, d, scale,
