@@ -350,9 +350,11 @@ int rf_favor_softmax_features(const void* dash, const void* x, const int64_t xs[
  * entirely on-chip.  qkv: bf16 rows holding q|k|v at column offsets q_off/k_off/v_off (+ h*dim_head); the row of
  * (b,o,s) of head h starts at b*x_strides[0] + o*x_strides[1] + s*x_strides[2] + h*x_strides[3] (elements); out
  * (bf16) likewise with o_strides, head h at column h*dim_head.  pc: bf16 [288][64] projection matrix pre-scaled by dim_head^-1/4, rows >= 266 zero.
- * Supported: dim_head 64, n_features 266, seq_len 64/128/256, and (ReLU kernel) any multiple of 256 walked in 256-row
- * chunks -- the L=1024 configuration (other shapes: use the unfused chain of rf_gemm +
- * rf_favor_softmax_features + rf_linattn_normalize).  softmax_kernel != 0: exp features with the library's
+ * Supported: dim_head 64, n_features 266; any seq_len >= 1 with the ReLU kernel (up to 256 rows in one 64- / 128- / 256-row
+ * tile, longer sequences walked in 256-row chunks with a partial last one), 1 <= seq_len <= 256 with the softmax kernel (its
+ * key maximum spans the whole sequence; longer: RF_EINVAL, use the unfused chain of rf_gemm + rf_favor_softmax_features +
+ * rf_linattn_normalize).  Rows s >= seq_len of an item are neither read nor written: they may belong to another sequence
+ * or lie outside the buffers.  softmax_kernel != 0: exp features with the library's
  * stabilisers (per-row max for q, per-(b,o,h) max for k) and eps; else relu(x)+eps. */
 int rf_favor_attention(const void* qkv, const void* pc, void* out, const int64_t x_strides[4],
                        const int64_t o_strides[3], int q_off, int k_off, int v_off, int n_b, int n_o, int n_h,

@@ -43,6 +43,7 @@ struct FavorAttnP {
   int dbg;      // timing experiments only: 1 = skip the phase-A MFMA loop, 2 = skip the phase-B loop
   float eps;
   float ctx_scale;  // f16 build: 2^-ceil(log2(sequence length)), see FV_CS; 1 in the bf16 build
+  int seq_len;      // true rows per sequence (TAIL instantiations: < nchunks * LS; rows >= seq_len are neither read nor written)
 };
 
 // fp16 range (librfmi_f16.so): the context sum_s k'[s,m] v[s,d] and the k' sums in its ones column grow with the sequence
@@ -60,15 +61,19 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 __device__ __forceinline__ int swz_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
-// DMA a [nrows][64] bf16 tile (rows `stride` elements apart) into the swizzled LDS image at lds_off
+// DMA a [nrows][64] bf16 tile (rows `stride` elements apart) into the swizzled LDS image at lds_off.  TAIL: only the first
+// nvalid (>= 1) source rows exist; the image rows behind them are filled from row nvalid - 1 (the address is clamped, nothing
+// past the sequence is read: those rows belong to the next sequence or to nobody).
+template <bool TAIL = false>
 __device__ __forceinline__ void fv_load_tile(char* smem, int lds_off, const h16_t* g, int64_t stride, int nrows,
-                                             int wave, int lane) {
+                                             int wave, int lane, int nvalid = 0) {
   const int ninstr = nrows * 8 / 64;
   for (int it = wave; it < ninstr; it += 4) {
     const int slot = it * 64 + lane;
     const int row = slot >> 3;
     const int clog = (slot & 7) ^ (row & 7);
-    rf_glds16(g + (int64_t)row * stride + clog * 8, smem + lds_off + it * 1024);
+    const int srow = TAIL ? (row < nvalid ? row : nvalid - 1) : row;
+    rf_glds16(g + (int64_t)srow * stride + clog * 8, smem + lds_off + it * 1024);
   }
 }
 
@@ -93,7 +98,11 @@ union Frag {
   uint2 h[2];
 };
 
-template <int LS, bool SOFTMAX>
+// TAIL (compile time): the sequence holds p.seq_len < nchunks * LS rows.  The aligned instantiations (TAIL = false) carry none
+// of the tail code.  Rule: K / V / Q source rows are clamped to the last valid row (padded rows are finite copies of it, never
+// foreign memory); k' of rows >= seq_len is forced to 0 on the phase-A accumulators (phi(0) = eps, not 0: a padded key would
+// add eps to every k' sum and eps * v to the context); output rows >= seq_len are not stored.
+template <int LS, bool SOFTMAX, bool TAIL>
 __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttnP p) {
   constexpr int ST = LS / 64;    // s-tiles per wave in phase B
   constexpr int NSB = LS / 32;   // s-blocks (pairs of s-tiles) in phase A
@@ -130,12 +139,13 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
   };
 
   const int nch = p.nchunks;  // > 1: long sequence walked in LS-row chunks (no cross-item prefetch then)
+  const int nv = TAIL ? p.seq_len : 0;  // valid rows of the sequence (tail instantiations only)
   int item = blockIdx.x;
   if (item < p.nitems) {
     int64_t xb, ob;
     item_base(item, xb, ob);
-    fv_load_tile(smem, K_OFF, p.qkv + xb + p.k_off, p.x_s, LS, wave, lane);
-    fv_load_tile(smem, V_OFF, p.qkv + xb + p.v_off, p.x_s, LS, wave, lane);
+    fv_load_tile<TAIL>(smem, K_OFF, p.qkv + xb + p.k_off, p.x_s, LS, wave, lane, nv);
+    fv_load_tile<TAIL>(smem, V_OFF, p.qkv + xb + p.v_off, p.x_s, LS, wave, lane, nv);
   }
   bool first = true;
   for (; item < p.nitems; item += gridDim.x) {
@@ -143,7 +153,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
     item_base(item, xb, ob);
     // wait for the K/V DMAs but NOT for the previous item's output stores (the ST*4 youngest operations of this wave):
     // a counted vmcnt lets them drain behind this item's phase A
-    if (first)
+    // (TAIL: a wave whose rows are padding issued fewer stores, the count would reach into the DMAs: wait for everything)
+    if (first || TAIL)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ST * 4) : "memory");
@@ -154,7 +165,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
     auto load_q = [&](int chunk) {
 #pragma unroll
       for (int t = 0; t < ST; ++t) {
-        const int s = chunk * LS + (wave * ST + t) * 16 + fr;
+        int s = chunk * LS + (wave * ST + t) * 16 + fr;
+        if (TAIL) s = s < nv ? s : nv - 1;
         const h16_t* qrow = p.qkv + xb + p.q_off + (int64_t)s * p.x_s;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) qf[t][kk] = *(const h16x8*)(qrow + (kk * 4 + fq) * 8);
@@ -191,7 +203,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
     if constexpr (SOFTMAX) {
       // pass 0: global max of the key logits over (s, m < 266)
       float mx = -INFINITY;
-      for (int u = 0; u < NSB; ++u) {
+      const int nsb0 = TAIL ? (nv + 31) >> 5 : NSB;  // (softmax: one chunk; s-blocks that are all padding are skipped)
+      for (int u = 0; u < nsb0; ++u) {
         h16x8 kf[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -225,14 +238,16 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
 #pragma unroll
       for (int i = 0; i < FV_DT; ++i) ctx[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ck = 0; ck < nch; ++ck) {
+    const int rem = TAIL ? nv - ck * LS : LS;  // valid rows of this chunk (>= 1; the last chunk of a tail sequence is partial)
     if (ck > 0) {  // next LS-row chunk of K and V (everyone is done with the previous one)
       __syncthreads();
-      fv_load_tile(smem, K_OFF, p.qkv + xb + p.k_off + (int64_t)ck * LS * p.x_s, p.x_s, LS, wave, lane);
-      fv_load_tile(smem, V_OFF, p.qkv + xb + p.v_off + (int64_t)ck * LS * p.x_s, p.x_s, LS, wave, lane);
+      fv_load_tile<TAIL>(smem, K_OFF, p.qkv + xb + p.k_off + (int64_t)ck * LS * p.x_s, p.x_s, LS, wave, lane, rem);
+      fv_load_tile<TAIL>(smem, V_OFF, p.qkv + xb + p.v_off + (int64_t)ck * LS * p.x_s, p.x_s, LS, wave, lane, rem);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    for (int u = 0; u < NSB; ++u) {
+    const int nsb = TAIL ? (rem < LS ? (rem + 31) >> 5 : NSB) : NSB;  // s-blocks that are all padding are skipped whole
+    for (int u = 0; u < nsb; ++u) {
       h16x8 kf[2][2];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -289,6 +304,15 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
 #pragma unroll
               for (int r = 0; r < 4; ++r) f[t][r] = 0.f;
           }
+          // padded key rows contribute nothing: only the s-block that holds the tail takes the branch (wave-uniform)
+          if constexpr (TAIL) {
+            if ((u + 1) * 32 > rem) {
+#pragma unroll
+              for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) f[t][r] = (2 * u + t) * 16 + 4 * fq + r < rem ? f[t][r] : 0.f;
+            }
+          }
           Frag kfr;
           kfr.u[0] = rf_pack2_h16(f[0][0], f[0][1]);
           kfr.u[1] = rf_pack2_h16(f[0][2], f[0][3]);
@@ -325,8 +349,8 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
       if (nxt < p.nitems) {  // (with nch > 1 K/V hold the LAST chunk of this item: also free now)
         int64_t xb2, ob2;
         item_base(nxt, xb2, ob2);
-        fv_load_tile(smem, K_OFF, p.qkv + xb2 + p.k_off, p.x_s, LS, wave, lane);
-        fv_load_tile(smem, V_OFF, p.qkv + xb2 + p.v_off, p.x_s, LS, wave, lane);
+        fv_load_tile<TAIL>(smem, K_OFF, p.qkv + xb2 + p.k_off, p.x_s, LS, wave, lane, nv);
+        fv_load_tile<TAIL>(smem, V_OFF, p.qkv + xb2 + p.v_off, p.x_s, LS, wave, lane, nv);
       }
     }
 
@@ -375,6 +399,7 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
       }
     }
     for (int qc = 0; qc < nch; ++qc) {
+    if (TAIL && qc * LS + wave * ST * 16 >= nv) continue;  // this wave's query rows are all padding (no barrier below)
     if (qc > 0) load_q(qc);
     f32x4 num[FV_DT][ST];
 #pragma unroll
@@ -447,7 +472,7 @@ __global__ __launch_bounds__(256, 1) void favor_attention_kernel(const FavorAttn
         uint2 w;
         w.x = rf_pack2_h16(num[i][t][0] * inv, num[i][t][1] * inv);
         w.y = rf_pack2_h16(num[i][t][2] * inv, num[i][t][3] * inv);
-        *(uint2*)(orow + i * 16 + 4 * fq) = w;
+        if (!TAIL || s < nv) *(uint2*)(orow + i * 16 + 4 * fq) = w;
       }
     }
     }  // chunks of Q
@@ -491,7 +516,7 @@ __device__ unsigned long long g_fv_cycles[8];
 // critical path of 4.5 tile-sequences per SIMD instead of 5.  Phase B: the sequence is split over all eight waves.  Same
 // maths, operands and LDS image as above.
 // ------------------------------------------------------------------------------------------------------------------
-template <int LS, bool SOFTMAX>
+template <int LS, bool SOFTMAX, bool TAIL>
 __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAttnP p) {
   constexpr int NSB = LS / 32;                    // s-blocks (pairs of s-tiles) per chunk
   constexpr int NJ = 3;                           // feature tiles of a wave in phase A (wave 0: 3, the others 2)
@@ -521,7 +546,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 
   // [nrows][64] bf16 tile -> swizzled LDS image; a wave's instruction covers 8 rows (row = 8*it + lane/8, rows & 7 == lane/8)
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  auto load_tile8 = [&](int lds_off, const h16_t* gp, int64_t stride, auto nrows_tag) {
+  // nvalid (K / V of a TAIL instantiation; 0 = all rows exist): source rows >= nvalid are read from row nvalid - 1
+  auto load_tile8 = [&](int lds_off, const h16_t* gp, int64_t stride, auto nrows_tag, int nvalid = 0) {
     constexpr int NI = decltype(nrows_tag)::value * 8 / 64;
     int ln = lane;  // opaque: the per-lane source offsets are rebuilt at every call instead of living in (spilled) registers
     asm volatile("" : "+v"(ln));
@@ -531,8 +557,15 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 #pragma unroll
     for (int k = 0; k < (NI + 7) / 8; ++k) {
       const int it = wave + 8 * k;
-      if (NI % 8 == 0 || it < NI)
-        fv_glds_asm(g0 + (int64_t)(8 * it) * stride, __builtin_amdgcn_readfirstlane(lds_base + lds_off + it * 1024));
+      if (NI % 8 == 0 || it < NI) {
+        const unsigned dst = __builtin_amdgcn_readfirstlane(lds_base + lds_off + it * 1024);
+        if (TAIL && nvalid > 0) {
+          const int row = dma_row + 8 * it;
+          fv_glds_asm(gp + (int64_t)(row < nvalid ? row : nvalid - 1) * stride + dma_col, dst);
+        } else {
+          fv_glds_asm(g0 + (int64_t)(8 * it) * stride, dst);
+        }
+      }
     }
   };
   constexpr std::integral_constant<int, LS> LS_TAG{};
@@ -548,12 +581,13 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
   };
   auto ctx_col = [](int tile, int q4) { return ((tile >> 1) * 32 + 8 * q4 + 4 * (tile & 1)) * 2; };
   const int nch = SOFTMAX ? 1 : p.nchunks;  // (the softmax kernel needs the global key max first: whole sequences only, rf_favor_attention checks)
+  const int nv = TAIL ? p.seq_len : 0;      // valid rows of the sequence (tail instantiations only; see favor_attention_kernel)
   int item = blockIdx.x;
   if (item < p.nitems) {
     int64_t xb, ob;
     item_base(item, xb, ob);
-    load_tile8(K_OFF, p.qkv + xb + p.k_off, p.x_s, LS_TAG);
-    load_tile8(V_OFF, p.qkv + xb + p.v_off, p.x_s, LS_TAG);
+    load_tile8(K_OFF, p.qkv + xb + p.k_off, p.x_s, LS_TAG, nv);
+    load_tile8(V_OFF, p.qkv + xb + p.v_off, p.x_s, LS_TAG, nv);
   }
   bool first = true;
   const bool prof = (RF_DBG(p.dbg) & 8) && wave == ((RF_DBG(p.dbg) >> 4) & 7);  // (false at compile time outside the ablation build)
@@ -570,7 +604,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
       t_last = __builtin_readcyclecounter();
       acc_cyc[6] += 1;
     }
-    if (first || wave >= NWB)  // (waves idle in phase B issued no stores: their youngest operations are the DMAs)
+    if (first || wave >= NWB || TAIL)  // (waves idle in phase B issued no stores: their youngest operations are the DMAs;
+                                       //  TAIL: so are those of a wave whose query rows are all padding)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STB * 4) : "memory");
@@ -595,7 +630,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
       if (wave < NWB) {
 #pragma unroll
         for (int t = 0; t < STB; ++t) {
-          const int s = chunk * LS + (wave * STB + t) * 16 + frq;
+          int s = chunk * LS + (wave * STB + t) * 16 + frq;
+          if (TAIL) s = s < nv ? s : nv - 1;
           const h16_t* qrow = p.qkv + xb + p.q_off + (int64_t)s * p.x_s;
 #pragma unroll
           for (int kk = 0; kk < 2; ++kk) qf[t][kk] = *(const h16x8*)(qrow + (kk * 4 + fqq) * 8);
@@ -623,7 +659,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
       }
       // pass 0: global max of the key logits (this wave: its feature tiles x the whole sequence)
       float mx = -INFINITY;
-      for (int u = 0; u < NSB; ++u) {
+      const int nsb0 = TAIL ? (nv + 31) >> 5 : NSB;  // (softmax: one chunk; s-blocks that are all padding are skipped)
+      for (int u = 0; u < nsb0; ++u) {
         h16x8 kf[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -661,13 +698,15 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
 #pragma unroll
       for (int i = 0; i < FV_DT; ++i) ctx[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ck = 0; ck < nch; ++ck) {
+      const int rem = TAIL ? nv - ck * LS : LS;  // valid rows of this chunk (>= 1; the last chunk of a tail sequence is partial)
       if (ck > 0) {
         __syncthreads();
-        load_tile8(K_OFF, p.qkv + xb + p.k_off + (int64_t)ck * LS * p.x_s, p.x_s, LS_TAG);
-        load_tile8(V_OFF, p.qkv + xb + p.v_off + (int64_t)ck * LS * p.x_s, p.x_s, LS_TAG);
+        load_tile8(K_OFF, p.qkv + xb + p.k_off + (int64_t)ck * LS * p.x_s, p.x_s, LS_TAG, rem);
+        load_tile8(V_OFF, p.qkv + xb + p.v_off + (int64_t)ck * LS * p.x_s, p.x_s, LS_TAG, rem);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
+      const int nsb = TAIL ? (rem < LS ? (rem + 31) >> 5 : NSB) : NSB;  // s-blocks that are all padding are skipped whole
       // the K fragments and transposed V fragments of s-block u + 1 are read while s-block u is computed (a wave owns only 2-3
       // feature tiles: without the read-ahead every s-block starts with an exposed LDS round trip)
       h16x8 kf[2][2];
@@ -691,10 +730,10 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
         }
       };
       load_sblock(0, kf, vf);
-      for (int u = 0; u < ((RF_DBG(p.dbg) & 1) ? 0 : NSB); ++u) {
+      for (int u = 0; u < ((RF_DBG(p.dbg) & 1) ? 0 : nsb); ++u) {
         h16x8 kfn[2][2];
         Frag vfn[4];
-        load_sblock(u + 1 < NSB ? u + 1 : u, kfn, vfn);
+        load_sblock(u + 1 < nsb ? u + 1 : u, kfn, vfn);
         f32x4 init[2] = {epsv, epsv};
         if constexpr (SOFTMAX) {
 #pragma unroll
@@ -728,6 +767,15 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
               for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) f[t][r] = 0.f;
+            }
+            // padded key rows contribute nothing: only the s-block that holds the tail takes the branch (wave-uniform)
+            if constexpr (TAIL) {
+              if ((u + 1) * 32 > rem) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                  for (int r = 0; r < 4; ++r) f[t][r] = (2 * u + t) * 16 + 4 * fq + r < rem ? f[t][r] : 0.f;
+              }
             }
             Frag kfr;
             kfr.u[0] = rf_pack2_h16(f[0][0], f[0][1]);
@@ -778,8 +826,8 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
       if (nxt < p.nitems) {
         int64_t xb2, ob2;
         item_base(nxt, xb2, ob2);
-        load_tile8(K_OFF, p.qkv + xb2 + p.k_off, p.x_s, LS_TAG);
-        load_tile8(V_OFF, p.qkv + xb2 + p.v_off, p.x_s, LS_TAG);
+        load_tile8(K_OFF, p.qkv + xb2 + p.k_off, p.x_s, LS_TAG, nv);
+        load_tile8(V_OFF, p.qkv + xb2 + p.v_off, p.x_s, LS_TAG, nv);
       }
     }
     FV_STAMP(3)
@@ -793,7 +841,7 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
           asm volatile("" : "+v"(qf[t][0]), "+v"(qf[t][1]));
         }
       }
-      if (wave < NWB) {
+      if (wave < NWB && (!TAIL || qc * LS + wave * STB * 16 < nv)) {  // (TAIL: not a wave whose query rows are all padding)
         f32x4 qinit[STB];
 #pragma unroll
         for (int t = 0; t < STB; ++t) qinit[t] = epsv;
@@ -903,7 +951,7 @@ __global__ __launch_bounds__(512, 1) void favor_attention_kernel8(const FavorAtt
             uint2 w;
             w.x = rf_pack2_h16(num[i][t][0] * inv, num[i][t][1] * inv);
             w.y = rf_pack2_h16(num[i][t][2] * inv, num[i][t][3] * inv);
-            *(uint2*)(orow + i * 16 + 4 * fq) = w;
+            if (!TAIL || s < nv) *(uint2*)(orow + i * 16 + 4 * fq) = w;
           }
         }
       }
@@ -923,7 +971,7 @@ extern "C" int rf_favor_phase_cycles(unsigned long long* out7, int reset) {
   return 0;
 }
 
-template <int LS, bool SM>
+template <int LS, bool SM, bool TAIL>
 static int launch_favor(const FavorAttnP& p, hipStream_t s) {
   const size_t lds = (size_t)FV_MPAD * 128 + 2 * (size_t)LS * 128 + (size_t)FV_DROWS * FV_CTX_LD + LS * 4 + 64;
   const int ncu = rf_num_cus() > 0 ? rf_num_cus() : 256;
@@ -934,12 +982,12 @@ static int launch_favor(const FavorAttnP& p, hipStream_t s) {
   static const bool force4 = getenv("RF_FAVOR4") != nullptr;
   constexpr bool only4 = SM && LS > 128;  // (the 8-wave form of this variant does not fit 256 registers: never instantiated)
   if (only4 || force4) {
-    auto k = favor_attention_kernel<LS, SM>;
-    if (const int e = rf_enable_big_lds<favor_attention_kernel<LS, SM>>()) return e;
+    auto k = favor_attention_kernel<LS, SM, TAIL>;
+    if (const int e = rf_enable_big_lds<favor_attention_kernel<LS, SM, TAIL>>()) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, p);
   } else if constexpr (!only4) {
-    auto k = favor_attention_kernel8<LS, SM>;
-    if (const int e = rf_enable_big_lds<favor_attention_kernel8<LS, SM>>()) return e;
+    auto k = favor_attention_kernel8<LS, SM, TAIL>;
+    if (const int e = rf_enable_big_lds<favor_attention_kernel8<LS, SM, TAIL>>()) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, p);
   }
   return rf_launch_status();
@@ -950,13 +998,15 @@ extern "C" int rf_favor_attention(const void* qkv, const void* pc, void* out, co
                                   int n_h, int seq_len, int dim_head, int n_features, int softmax_kernel, float eps,
                                   void* stream) {
   if (dim_head != FV_DH || n_features != FV_M) return RF_EINVAL;
-  int nchunks = 1, ls = seq_len;
-  if (seq_len > 256) {  // long sequences: 256-row chunks (ReLU kernel; the softmax kernel needs the global key max first)
-    if (softmax_kernel || seq_len % 256) return RF_EINVAL;
-    nchunks = seq_len / 256;
-    ls = 256;
+  if (seq_len < 1) return RF_EINVAL;
+  // tile: the smallest of 64 / 128 / 256 rows that holds the sequence; longer sequences walk 256-row chunks, the last one
+  // partial (ReLU kernel; the softmax kernel needs the global key max before the first exponential)
+  int nchunks = 1, ls = seq_len <= 64 ? 64 : seq_len <= 128 ? 128 : 256;
+  if (seq_len > 256) {
+    if (softmax_kernel) return RF_EINVAL;
+    nchunks = (seq_len + 255) / 256;
   }
-  if (ls != 64 && ls != 128 && ls != 256) return RF_EINVAL;
+  const bool tail = seq_len != nchunks * ls;  // aligned lengths run the instantiations without any tail code
   if (((uintptr_t)qkv % 16) || ((uintptr_t)pc % 16) || ((uintptr_t)out % 8)) return RF_EALIGN;
   for (int i = 0; i < 3; ++i)
     if (x_strides[i] % 8 || o_strides[i] % 4) return RF_EALIGN;
@@ -973,7 +1023,8 @@ extern "C" int rf_favor_attention(const void* qkv, const void* pc, void* out, co
   p.nitems = n_b * n_o * n_h;
   p.eps = eps;
   p.nchunks = nchunks;
-  p.ctx_scale = 1.0f;
+  p.seq_len = seq_len;
+  p.ctx_scale = 1.0f;  // (f16 build: from the TRUE length, not nchunks * ls)
 #ifdef RF_H16_IS_F16
   for (int n = 1; n < seq_len; n <<= 1) p.ctx_scale *= 0.5f;
 #endif
@@ -982,7 +1033,11 @@ extern "C" int rf_favor_attention(const void* qkv, const void* pc, void* out, co
   if (dbg_rc) return dbg_rc;
   p.dbg = dbg;
   hipStream_t s = (hipStream_t)stream;
-  if (ls == 256) return softmax_kernel ? launch_favor<256, true>(p, s) : launch_favor<256, false>(p, s);
-  if (ls == 128) return softmax_kernel ? launch_favor<128, true>(p, s) : launch_favor<128, false>(p, s);
-  return softmax_kernel ? launch_favor<64, true>(p, s) : launch_favor<64, false>(p, s);
+#define FV_LAUNCH(LS_) \
+  (tail ? (softmax_kernel ? launch_favor<LS_, true, true>(p, s) : launch_favor<LS_, false, true>(p, s)) \
+        : (softmax_kernel ? launch_favor<LS_, true, false>(p, s) : launch_favor<LS_, false, false>(p, s)))
+  if (ls == 256) return FV_LAUNCH(256);
+  if (ls == 128) return FV_LAUNCH(128);
+  return FV_LAUNCH(64);
+#undef FV_LAUNCH
 }

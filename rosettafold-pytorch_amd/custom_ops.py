@@ -85,7 +85,8 @@ def _(q, k, v):
 @torch.library.custom_op("rfmi::performer_attention", mutates_args=(), device_types="cuda")
 def performer_attention(qkv: Tensor, proj: Tensor, heads: int, softmax_kernel: bool) -> Tensor:
     """qkv bf16 [S, n, 3*heads*64] (q | k | v), proj bf16 [288, 64] (pre-scaled by 64^-1/4, rows >= 266 zero; times log2 e
-    for the softmax kernel).  Returns bf16 [S, n, heads*64]."""
+    for the softmax kernel).  Returns bf16 [S, n, heads*64].  Any n >= 1 with the ReLU features, 1 <= n <= 256 with the
+    softmax features (rf_favor_attention's contract; the floor of ops.favor_fused_applies is the model's routing, not this op's)."""
     S, n, W3 = qkv.shape
     inner = W3 // 3
     with _guard(qkv):

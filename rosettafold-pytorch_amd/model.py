@@ -843,9 +843,9 @@ class PerformerSelfAttention(RecordingModule):
         if cond:
             bqkv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out, lead=(self.to_q, self.to_k)))
             bv = bqkv[2 * inner:]
-        if seq_group is None and RT.fused_favor and ops.is_h16(T()) and dh == 64 and m == M_FEAT and (
-                geo.Ls in (64, 128, 256) or (gen and geo.Ls > 256 and geo.Ls % 256 == 0)):
-            # fused path: one projection GEMM (q|k|v) + one persistent kernel; q', k', ctx never leave the chip
+        if seq_group is None and RT.fused_favor and ops.favor_fused_applies(geo.Ls, not gen, dh, m, T()):
+            # fused path: one projection GEMM (q|k|v) + one persistent kernel; q', k', ctx never leave the chip (any sequence
+            # length: the kernel pads its last tile itself, rows past Ls are neither read nor written)
             Ls, Lo, ss, so, RB = geo.Ls, geo.Lo, geo.ss, geo.so, geo.RB
             W3 = 3 * inner
             o = torch.empty(geo.R, inner, device=xn.device, dtype=T())

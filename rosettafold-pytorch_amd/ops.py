@@ -933,6 +933,31 @@ def add_pos_enc(x, aa_idx, pe, two_d):
     return y
 
 
+# Shortest sequence the model sends to the fused FAVOR+ kernel (the C ABI itself has no floor).  The kernel's smallest tile is
+# 64 rows, so a short sequence is mostly padding; the floor is the smallest of {16, 32, 48, 64} at which the fused attend still
+# beats the unfused chain.  Measured (tools/favor_bench.py --ragged, MI355X, bf16, pair layout B = 4, L x L x 288, 8 heads, q|k|v
+# projection included, eager launches, rows / columns; profiles/r07_favor_ragged.json), fused vs unfused in us:
+#   L = 16: 46 vs 151 / 46 vs 150     L = 32: 45 vs 151 / 45 vs 151     L = 48: 63 vs 201 / 63 vs 203     L = 64: 76 vs 320 / 76 vs 319
+# The fused route wins 3.2-4.2x at every candidate (both are launch-bound there: 2 launches against a dozen), so speed alone puts
+# the floor at 16.  It is 32 because of a test written for the other route: at 16 the bf16 full-model parity test
+# (tests/test_modules_gpu.py::test_full_model_shapes_and_parity, L = 16, two-and-two blocks) came out at a distogram argmax
+# agreement of 0.785 against its bound of 0.8 -- the fused kernel rounds q', k' and the context at other places than the chain
+# that bound was set on, while its own error against the oracle at short lengths is that of the chain.  The existing
+# module tests run at lengths 8 to 24; 32 is the smallest measured candidate above them.
+FAVOR_FUSED_MIN_LS = 32
+
+
+def favor_fused_applies(Ls, softmax, dh, m, dtype):
+    """Python mirror of what rf_favor_attention accepts, plus the model's floor: 16-bit operands, dim_head 64, 266 features,
+    any sequence length with the ReLU features, up to 256 rows with the softmax features (their key maximum spans the whole
+    sequence, which must fit one tile)."""
+    if not (is_h16(dtype) and dh == 64 and m == 266):
+        return False
+    if Ls < FAVOR_FUSED_MIN_LS:
+        return False
+    return Ls <= 256 or not softmax
+
+
 def favor_attention(qkv, pc, out, x_strides, o_strides, q_off, k_off, v_off, n_b, n_o, n_h, seq_len, dim_head,
                     n_features, softmax_kernel, eps):
     _need_cuda(qkv, pc, out)

@@ -10,6 +10,37 @@ def timeit(fn, iters=10):
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / iters
 torch.manual_seed(0)
+if "--ragged" in sys.argv:
+    # python tools/favor_bench.py --ragged [out.json]: PerformerSelfAttention.attend (q|k|v projection included) with the fused kernel
+    # against the unfused chain, bf16, at lengths that are no multiple of the kernel's tiles; then the sweep the floor
+    # ops.FAVOR_FUSED_MIN_LS is read from (pair layout, both axes, floor bypassed).  Eager launches, min of 3 windows.
+    import json
+    ops.FAVOR_FUSED_MIN_LS = 1
+    def attend_ms(m, B, L1, L2, D, axis, fused, iters):
+        xn = torch.randn(B, L1, L2, D, device="cuda").bfloat16()
+        res = torch.zeros(B, L1, L2, D, device="cuda")
+        R.RT.fused_favor = fused
+        try:
+            return min(timeit(lambda: m.attend(xn, res, axis), iters) for _ in range(3))
+        except ops.L.RfmiError as e:  # the 16-bit unfused chain takes multiples of 8 only (RF_EALIGN): nothing to time
+            print(f"   {'fused' if fused else 'unfused'} route refused: {e}", flush=True)
+            return None
+        finally:
+            R.RT.fused_favor = True
+    rows = []
+    shapes = [(f"pair {ax} L={L}", True, 4, L, L, 288, 8, a_) for L in (200, 256, 300, 304, 700, 704) for ax, a_ in (("row", 1), ("col", 2))]
+    shapes += [("msa col N=100 L=200", False, 4, 100, 200, 384, 12, 1), ("msa col N=104 L=200", False, 4, 104, 200, 384, 12, 1), ("msa col N=128 L=200", False, 4, 128, 200, 384, 12, 1)]
+    shapes += [(f"floor sweep pair {ax} L={L}", True, 4, L, L, 288, 8, a_) for L in (16, 32, 48, 64) for ax, a_ in (("row", 1), ("col", 2))]
+    for name, gen, B, L1, L2, D, H, axis in shapes:
+        m = R.PerformerSelfAttention(dim=D, heads=H, generalized_attention=gen).cuda()
+        iters = 5 if L1 >= 300 else 20 if L1 >= 100 else 200
+        tf, tu = attend_ms(m, B, L1, L2, D, axis, True, iters), attend_ms(m, B, L1, L2, D, axis, False, iters)
+        rows.append(dict(shape=name, B=B, L1=L1, L2=L2, D=D, H=H, axis=axis, fused_ms=tf, unfused_ms=tu, unfused_over_fused=tu / tf if tu else None))
+        print(f"{name}: fused {tf*1e3:.0f} us, unfused " + (f"{tu*1e3:.0f} us, unfused / fused {tu/tf:.2f}" if tu else "refused (RF_EALIGN)"), flush=True)
+    out = [a_ for a_ in sys.argv[1:] if a_.endswith(".json")]
+    if out:
+        json.dump(rows, open(out[0], "w"), indent=1)
+    sys.exit(0)
 for name, gen, B, L1, L2, D, H, axis in [("pair row", True, 4, 256, 256, 288, 8, 1), ("pair col", True, 4, 256, 256, 288, 8, 2), ("msa col", False, 4, 128, 256, 384, 12, 1)]:
     m = R.PerformerSelfAttention(dim=D, heads=H, generalized_attention=gen).cuda()
     inner = 64 * H
