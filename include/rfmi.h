@@ -188,6 +188,33 @@ int rf_tied_attention(const void* q, const void* k, const void* v, const int64_t
                       void* out, const int64_t o_strides[4], int B, int H, int N, int L, int d_head, float* partial_ws,
                       int64_t partial_ws_elems, void* stream);
 
+/* The tied attention at ANY chain length (rf_version >= 12): rf_tied_softmax, rf_tied_logits, rf_tied_av and rf_tied_attention
+ * with a leading dimension for the attention map.  att_ld = elements between rows of att, element (b,h,i,j) at
+ * ((b*H + h)*L + i)*att_ld + j; att_ld >= L (RF_EINVAL otherwise) and att_ld % 8 == 0 (RF_EALIGN otherwise), so that every
+ * row is 16-byte aligned and att_ld is a legal K for a 16-bit rf_gemm whatever L is.  The entry points above are the
+ * att_ld == L case of the same code, restricted to their own lengths.
+ *   - L is a run-time length: 1 <= L <= 256 for rf_tied_av_ld, rf_tied_attention_ld and the one-pass kernel of
+ *     rf_tied_logits_ld (RF_EINVAL otherwise; rf_tied_logits_ld also keeps L in {512,768,1024} with att_ld == L and the
+ *     workspace, as rf_tied_logits); any L >= 1 for rf_tied_softmax_ld.
+ *   - rows i >= L of att are neither read nor written; columns L <= j < att_ld of every written row are written as exact
+ *     zeros (consumers contract over att_ld), and rf_tied_av_ld relies on them being zeros.
+ *   - no source row >= L of q, k, v or w is addressed; output rows >= L are not stored.
+ *   - att_sym is [B,L,L,H] with sym_ld as in rf_tied_softmax.
+ *   - w (rf_tied_logits_ld / rf_tied_attention_ld, may be NULL): strides {b,h,n} multiples of 4 as before, i.e. every row
+ *     of w is 16-byte aligned: a dense [B,H,N,L] w qualifies only when L % 4 == 0, otherwise pad its rows to 4*ceil(L/4)
+ *     floats (the pad values are read but reach no stored result). */
+int rf_tied_softmax_ld(const float* logits, void* att, int att_dtype, int64_t att_ld, float* att_sym, int64_t sym_ld, int B,
+                       int H, int L, void* stream);
+int rf_tied_logits_ld(const void* q, const void* k, const int64_t qk_strides[4], const float* w, const int64_t w_strides[3],
+                      float qscale, void* att, int64_t att_ld, float* att_sym, int64_t sym_ld, int B, int H, int N, int L,
+                      int d_head, float* partial_ws, int64_t partial_ws_elems, void* stream);
+int rf_tied_av_ld(const void* att, int64_t att_ld, const void* v, const int64_t v_strides[4], void* out,
+                  const int64_t o_strides[4], int B, int H, int N, int L, int d_head, void* stream);
+int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int64_t qk_strides[4], const int64_t v_strides[4],
+                         const float* w, const int64_t w_strides[3], float qscale, void* att, int64_t att_ld, float* att_sym,
+                         int64_t sym_ld, void* out, const int64_t o_strides[4], int B, int H, int N, int L, int d_head,
+                         float* partial_ws, int64_t partial_ws_elems, void* stream);
+
 /* Feed-forward block with its residual in ONE launch (FeedForward, rf.py:270-281, inside the residual wrappers of the
  * encoder / axial layers rf.py:284-354, 483-560):
  *   out[m,:] = residual[m,:] + W2 relu(W1 x[m,:] + b1) + b2          (fp32; out may alias residual: in place)

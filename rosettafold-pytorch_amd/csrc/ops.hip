@@ -501,9 +501,9 @@ extern "C" int rf_softmax(const float* x, int64_t x_rs, int64_t x_cs, void* y, i
   return rf_launch_status();
 }
 
-__global__ __launch_bounds__(256) void att_sym_kernel(const void* att, int dt, float* sym, int64_t sym_ld, int B, int H,
-                                                      int L) {
-  // sym[b,i,j,h] = 0.5*(att[b,h,i,j] + att[b,h,j,i])
+__global__ __launch_bounds__(256) void att_sym_kernel(const void* att, int dt, int64_t att_ld, float* sym, int64_t sym_ld, int B,
+                                                      int H, int L) {
+  // sym[b,i,j,h] = 0.5*(att[b,h,i,j] + att[b,h,j,i]); att rows are att_ld elements apart
   const int64_t n = (int64_t)B * L * L * H;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int h = e % H;
@@ -511,22 +511,48 @@ __global__ __launch_bounds__(256) void att_sym_kernel(const void* att, int dt, f
     const int j = t % L, i = (t / L) % L;
     const int64_t b = t / ((int64_t)L * L);
     const int64_t o = (b * H + h) * L;
-    sym[t * sym_ld + h] = 0.5f * (ld(att, dt, (o + i) * L + j) + ld(att, dt, (o + j) * L + i));
+    sym[t * sym_ld + h] = 0.5f * (ld(att, dt, (o + i) * att_ld + j) + ld(att, dt, (o + j) * att_ld + i));
   }
+}
+
+// zeros in columns [cols, ld) of `rows` rows that are ld elements apart (the pad of an attention map with a leading dimension)
+__global__ __launch_bounds__(256) void zero_pad_columns_kernel(void* y, int dt, int64_t ld, int64_t rows, int cols) {
+  const int pad = (int)(ld - cols);
+  const int64_t n = rows * pad;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+    st(y, dt, (e / pad) * ld + cols + e % pad, 0.f);
+}
+
+static int tied_softmax_launch(const float* logits, void* att, int att_dtype, int64_t att_ld, float* att_sym, int64_t sym_ld,
+                               int B, int H, int L, void* stream) {
+  const int64_t rows = (int64_t)B * H * L;
+  hipLaunchKernelGGL(softmax_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, (int64_t)L,
+                     (int64_t)1, att, att_dtype, att_ld, rows, L, 1.0f);
+  if (att_ld > L) {
+    const int64_t n = rows * (att_ld - L);
+    hipLaunchKernelGGL(zero_pad_columns_kernel, dim3(min(cdiv(n, 256), 8192u)), dim3(256), 0, (hipStream_t)stream, att,
+                       att_dtype, att_ld, rows, L);
+  }
+  if (att_sym) {
+    const int64_t n = (int64_t)B * L * L * H;
+    hipLaunchKernelGGL(att_sym_kernel, dim3(min(cdiv(n, 256), 8192u)), dim3(256), 0, (hipStream_t)stream, att,
+                       att_dtype, att_ld, att_sym, sym_ld, B, H, L);
+  }
+  return rf_launch_status();
 }
 
 extern "C" int rf_tied_softmax(const float* logits, void* att, int att_dtype, float* att_sym, int64_t sym_ld, int B,
                                int H, int L, void* stream) {
   RF_CHECK_DT(att_dtype);
-  const int64_t rows = (int64_t)B * H * L;
-  hipLaunchKernelGGL(softmax_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, (int64_t)L,
-                     (int64_t)1, att, att_dtype, (int64_t)L, rows, L, 1.0f);
-  if (att_sym) {
-    const int64_t n = (int64_t)B * L * L * H;
-    hipLaunchKernelGGL(att_sym_kernel, dim3(min(cdiv(n, 256), 8192u)), dim3(256), 0, (hipStream_t)stream, att,
-                       att_dtype, att_sym, sym_ld, B, H, L);
-  }
-  return rf_launch_status();
+  return tied_softmax_launch(logits, att, att_dtype, L, att_sym, sym_ld, B, H, L, stream);
+}
+
+extern "C" int rf_tied_softmax_ld(const float* logits, void* att, int att_dtype, int64_t att_ld, float* att_sym,
+                                  int64_t sym_ld, int B, int H, int L, void* stream) {
+  RF_CHECK_DT(att_dtype);
+  if (!logits || !att || B <= 0 || H <= 0 || L <= 0 || att_ld < L) return RF_EINVAL;
+  if (att_ld % 8) return RF_EALIGN;
+  return tied_softmax_launch(logits, att, att_dtype, att_ld, att_sym, sym_ld, B, H, L, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1540,7 +1566,7 @@ extern "C" int rf_add_pos_enc(const float* x, const int64_t* aa_idx, const float
   return rf_launch_status();
 }
 
-extern "C" int rf_version(void) { return 11; }
+extern "C" int rf_version(void) { return 12; }
 #ifdef RF_H16_IS_F16
 extern "C" const char* rf_build_info(void) { return "librfmi_f16 gfx950 (MI355X) round-3: 16-bit operand type = IEEE fp16"; }
 #else

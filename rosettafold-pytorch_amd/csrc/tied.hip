@@ -41,9 +41,16 @@ struct TiedP {
   h16_t* att;                                      // [B, H, L, L]
   int B, H, N;
   int dbg;  // timing experiments (RF_TIED_DBG; results are WRONG when set): 1 no DMA after the prologue, 2 fragments read once, 4 no MFMA
+  int len;         // run-time chain length (tail instantiations; the aligned ones use the tile L)
+  int64_t att_ld;  // elements between rows of att (>= len, a multiple of 8; the aligned instantiations use L)
 };
 
-template <int L, bool SCALE>
+// TAIL: the chain has p.len <= L residues (L = the smallest tile that holds it) and att has the row pitch p.att_ld.  Source
+// rows >= len are never addressed (the lane's row is clamped to len - 1: finite copies), logits of keys >= len are -inf before
+// the row maximum (an exact 0 in the sum and in att), query tiles wholly past len are not launched, rows >= len of att are not
+// stored and columns [len, att_ld) of the stored rows are zeros.  Every wave still issues PW DMAs per step (a clamped DMA is
+// a DMA), so the counted waits hold.  The aligned instantiations (TAIL = false) contain none of this.
+template <int L, bool SCALE, bool TAIL>
 __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
   constexpr int JT = L / 16;                 // key tiles of 16 columns
   constexpr int NSTG = L >= 256 ? 6 : 8;     // ring stages
@@ -64,10 +71,11 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
     const int q = nblk >> 3, r = nblk & 7, x = bid & 7;
     lid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
   }
-  constexpr int IT = L / 64;
+  const int IT = TAIL ? (p.len + 63) >> 6 : L / 64;
   const int it = lid % IT, h = (lid / IT) % p.H, b = lid / (IT * p.H);
-  const h16_t* qb = p.q + (int64_t)b * p.b_stride + (int64_t)h * p.h_stride + (int64_t)(it * 64) * p.l_stride;
+  const h16_t* qb = p.q + (int64_t)b * p.b_stride + (int64_t)h * p.h_stride + (TAIL ? 0 : (int64_t)(it * 64) * p.l_stride);
   const h16_t* kb = p.k + (int64_t)b * p.b_stride + (int64_t)h * p.h_stride;
+  const int last = TAIL ? p.len - 1 : 0;  // the last valid row (tail instantiations)
 
   // DMA: an instruction covers 16 rows x 4 chunks (64-byte head slices); lane-linear LDS image with the bank swizzle
   // chunk ^ g((row >> 2) & 3), g = {0, 2, 3, 1}, on the source chunk and on the fragment reads
@@ -80,7 +88,18 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
 #pragma unroll
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 4 + wave;
-      if (live && instr < QI)
+      if constexpr (TAIL) {
+        // per-lane row clamp: the lane's source row is min(row, len - 1)
+        if (live && instr < QI) {
+          const int row = it * 64 + instr * 16 + lrow;
+          rf_glds16(qb + (int64_t)n * p.n_stride + (int64_t)(row < last ? row : last) * p.l_stride + c_log * 8, st + instr * 1024);
+        } else if (live && instr < QI + KI) {
+          const int row = (instr - QI) * 16 + lrow;
+          rf_glds16(kb + (int64_t)n * p.n_stride + (int64_t)(row < last ? row : last) * p.l_stride + c_log * 8, st + instr * 1024);
+        } else {
+          rf_glds16(g_tied_zero16, smem + DUMP);
+        }
+      } else if (live && instr < QI)
         rf_glds16(qb + (int64_t)n * p.n_stride + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
       else if (live && instr < QI + KI)
         rf_glds16(kb + (int64_t)n * p.n_stride + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
@@ -92,7 +111,13 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
   if constexpr (SCALE) {
     // w tile: rows it*64 .. +63 of every MSA row n (256 contiguous bytes each), by DMA: one instruction = 4 MSA rows.
     // These are the oldest operations of every wave, so the counted wait of the first step covers them.
+    // (TAIL: the 16-byte piece is clamped to the one that holds column len - 1; rows of w are 16-byte aligned and hold
+    // 4 ceil(len / 4) floats, whatever sits in the last piece past len scales query rows that are never stored)
     const float* wb = p.w + (int64_t)b * p.w_b + (int64_t)h * p.w_h + it * 64 + (lane & 15) * 4;
+    if constexpr (TAIL) {
+      const int wcol = it * 64 + (lane & 15) * 4, wlast = last & ~3;
+      wb = p.w + (int64_t)b * p.w_b + (int64_t)h * p.w_h + (wcol < wlast ? wcol : wlast);
+    }
     for (int i4 = wave; i4 * 4 < p.N; i4 += 4)
       rf_glds16(wb + (int64_t)(i4 * 4 + (lane >> 4)) * p.w_n, smem + W_OFF + i4 * 1024);
   }
@@ -135,6 +160,14 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
   }
 
   // ---- row softmax: a row lives in the four lanes {fr, fr+16, fr+32, fr+48} ------------------------------------
+  if constexpr (TAIL) {
+    // padded keys: -inf before the maximum (key 0 is always valid, so the maximum of a valid row stays finite)
+#pragma unroll
+    for (int j = 0; j < JT; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (j * 16 + 4 * fq + e > last) acc[j][e] = -INFINITY;
+  }
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < JT; ++j) mx = fmaxf(mx, fmaxf(fmaxf(acc[j][0], acc[j][1]), fmaxf(acc[j][2], acc[j][3])));
@@ -166,13 +199,27 @@ __global__ __launch_bounds__(256) void tied_logits_kernel(const TiedP p) {
   }
   asm volatile("" ::: "memory");
   constexpr int CPR = L * 2 / 16, NCH = 16 * CPR, NIT = NCH / 64;
-  h16_t* arow = p.att + (((int64_t)b * p.H + h) * L + it * 64 + wave * 16) * L;
+  if constexpr (TAIL) {
+    // rows < len only, att_ld / 8 pieces per row: the strip's (columns >= len are the zeros of the masked keys), then zeros
+    const int r0 = it * 64 + wave * 16;
+    const int cpr = (int)(p.att_ld >> 3), nch = 16 * cpr;
+    h16_t* arow = p.att + (((int64_t)b * p.H + h) * p.len + r0) * p.att_ld;
+    for (int idx = lane; idx < nch; idx += 64) {
+      const int r = idx / cpr, c = idx - r * cpr;
+      if (r0 + r > last) break;  // (idx grows with r: every later piece of this lane is past the chain too)
+      f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+      if (c < CPR) v = *(const f32x4*)(strip + r * PITCH + c * 16);
+      *(f32x4*)(arow + (int64_t)r * p.att_ld + c * 8) = v;
+    }
+  } else {
+    h16_t* arow = p.att + (((int64_t)b * p.H + h) * L + it * 64 + wave * 16) * L;
 #pragma unroll
-  for (int t = 0; t < NIT; ++t) {
-    const int idx = lane + 64 * t;
-    const int r = idx / CPR, c = idx % CPR;
-    const f32x4 v = *(const f32x4*)(strip + r * PITCH + c * 16);
-    *(f32x4*)(arow + (int64_t)r * L + c * 8) = v;
+    for (int t = 0; t < NIT; ++t) {
+      const int idx = lane + 64 * t;
+      const int r = idx / CPR, c = idx % CPR;
+      const f32x4 v = *(const f32x4*)(strip + r * PITCH + c * 16);
+      *(f32x4*)(arow + (int64_t)r * L + c * 8) = v;
+    }
   }
 }
 
@@ -343,8 +390,9 @@ __global__ __launch_bounds__(256) void tied_split_softmax_kernel(const float* pa
   }
 }
 
-__global__ __launch_bounds__(256) void tied_att_sym_kernel(const h16_t* att, float* sym, int64_t sym_ld, int B, int H, int L) {
-  // sym[b,i,j,h] = 0.5*(att[b,h,i,j] + att[b,h,j,i])
+__global__ __launch_bounds__(256) void tied_att_sym_kernel(const h16_t* att, int64_t att_ld, float* sym, int64_t sym_ld, int B,
+                                                           int H, int L) {
+  // sym[b,i,j,h] = 0.5*(att[b,h,i,j] + att[b,h,j,i]); att rows are att_ld elements apart
   const int64_t n = (int64_t)B * L * L * H;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
     const int h = e % H;
@@ -352,7 +400,7 @@ __global__ __launch_bounds__(256) void tied_att_sym_kernel(const h16_t* att, flo
     const int j = t % L, i = (t / L) % L;
     const int64_t b = t / ((int64_t)L * L);
     const int64_t o = (b * H + h) * L;
-    sym[t * sym_ld + h] = 0.5f * (h2f(att[(o + i) * L + j]) + h2f(att[(o + j) * L + i]));
+    sym[t * sym_ld + h] = 0.5f * (h2f(att[(o + i) * att_ld + j]) + h2f(att[(o + j) * att_ld + i]));
   }
 }
 
@@ -362,14 +410,16 @@ static int tied_dbg() {  // < 0: the switch is set but this build has no ablatio
   return rc ? rc : v;
 }
 
-template <int L, bool SCALE>
+template <int L, bool SCALE, bool TAIL>
 static int launch_tied(const TiedP& p, hipStream_t s) {
   constexpr int NSTG = L >= 256 ? 6 : 8;
   const size_t lds = (size_t)NSTG * (64 * 64 + L * 64) + 1024 + (SCALE ? (size_t)p.N * 256 : 0);
   if (lds > 160 * 1024) return RF_EINVAL;
-  auto k = tied_logits_kernel<L, SCALE>;
-  if (const int e = rf_enable_big_lds<tied_logits_kernel<L, SCALE>>()) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)(p.B * p.H * (L / 64))), dim3(256), lds, s, p);
+  auto k = tied_logits_kernel<L, SCALE, TAIL>;
+  if (const int e = rf_enable_big_lds<tied_logits_kernel<L, SCALE, TAIL>>()) return e;
+  const int64_t grid = (int64_t)p.B * p.H * (TAIL ? (p.len + 63) / 64 : L / 64);  // (query tiles wholly past len are not launched)
+  if (grid > 0x7fffffffLL) return RF_EINVAL;
+  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, s, p);
   return rf_launch_status();
 }
 
@@ -414,9 +464,19 @@ static int tied_logits_split(const TiedP& p0, int L, float* ws, int64_t ws_elems
   return rf_launch_status();
 }
 
-static int tied_logits_dispatch(const TiedP& p, int L, hipStream_t s) {
-#define RF_TIED(L_) \
-  if (L == L_) return p.w ? launch_tied<L_, true>(p, s) : launch_tied<L_, false>(p, s);
+// the tile of a chain of 1 <= len <= 256 residues: the smallest of 64 / 128 / 192 / 256 that holds it
+static int tied_tile(int len) { return (len + 63) / 64 * 64; }
+
+// one-pass kernel: p.len in 1 .. 256; the tail instantiation iff the chain does not fill its tile or att is not dense
+static int tied_logits_dispatch(const TiedP& p, hipStream_t s) {
+  if (p.len < 1 || p.len > 256) return RF_EINVAL;
+  const int tile = tied_tile(p.len);
+  const bool tail = p.len != tile || p.att_ld != p.len;
+#define RF_TIED(L_)                                                                                   \
+  if (tile == L_) {                                                                                   \
+    if (tail) return p.w ? launch_tied<L_, true, true>(p, s) : launch_tied<L_, false, true>(p, s);    \
+    return p.w ? launch_tied<L_, true, false>(p, s) : launch_tied<L_, false, false>(p, s);            \
+  }
   RF_TIED(256)
   RF_TIED(192)
   RF_TIED(128)
@@ -425,11 +485,11 @@ static int tied_logits_dispatch(const TiedP& p, int L, hipStream_t s) {
   return RF_EINVAL;
 }
 
-static int tied_sym(const void* att, float* att_sym, int64_t sym_ld, int B, int H, int L, hipStream_t s) {
+static int tied_sym(const void* att, int64_t att_ld, float* att_sym, int64_t sym_ld, int B, int H, int L, hipStream_t s) {
   const int64_t n = (int64_t)B * L * L * H;
   unsigned g = (unsigned)((n + 255) / 256);
   if (g > 8192u) g = 8192u;
-  hipLaunchKernelGGL(tied_att_sym_kernel, dim3(g), dim3(256), 0, s, (const h16_t*)att, att_sym, sym_ld, B, H, L);
+  hipLaunchKernelGGL(tied_att_sym_kernel, dim3(g), dim3(256), 0, s, (const h16_t*)att, att_ld, att_sym, sym_ld, B, H, L);
   return rf_launch_status();
 }
 
@@ -445,12 +505,13 @@ extern "C" int rf_tied_logits_softmax(const void* q, const void* k, int64_t b_st
   p.b_stride = b_stride; p.n_stride = n_stride; p.l_stride = l_stride; p.h_stride = d_head;
   p.w = nullptr; p.w_b = p.w_h = p.w_n = 0; p.qscale = 1.f;
   p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
+  p.len = L; p.att_ld = L;
   p.dbg = tied_dbg();
   if (p.dbg < 0) return p.dbg;
   hipStream_t s = (hipStream_t)stream;
-  const int rc = tied_logits_dispatch(p, L, s);
+  const int rc = tied_logits_dispatch(p, s);
   if (rc != 0 || !att_sym) return rc;
-  return tied_sym(att, att_sym, sym_ld, B, H, L, s);
+  return tied_sym(att, L, att_sym, sym_ld, B, H, L, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -466,9 +527,15 @@ struct TiedAvP {
   int64_t o_b, o_n, o_h, o_l;  // element strides of out (head slice contiguous)
   int B, H, N;
   int units_per_wg, nunits;
+  int len;         // run-time chain length (tail instantiations; the aligned ones use the tile L)
+  int64_t att_ld;  // elements between rows of att (tail instantiations; the aligned ones use L)
 };
 
-template <int L>
+// TAIL: p.len <= L residues, att rows p.att_ld apart.  Probability and value rows are clamped to len - 1 (finite copies; the
+// value copies meet the zero probabilities of columns [len, att_ld)), a 16-byte probability piece at a column >= att_ld is
+// not read but taken as zero, output rows >= len are not stored.  A wave whose rows are padding then issues fewer stores than
+// the counted wait assumes (the count would reach into the DMAs), so the tail instantiations wait for everything per unit.
+template <int L, bool TAIL>
 __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
   constexpr int RT = L / 64;    // 16-row query tiles per wave
   constexpr int KS = L / 32;    // contraction steps over the keys
@@ -491,6 +558,7 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
   const int lrow = lane >> 2;
   const int c_src = (lane & 3) ^ (((lrow >> 3) & 1) << 1);
   const int64_t lane_off = (int64_t)lrow * p.v_l + c_src * 8;
+  const int last = TAIL ? p.len - 1 : 0;  // the last valid row (tail instantiations)
   auto stage = [&](int u) {
     char* st = smem + ((u - u0) % NSTG) * STAGE;
     const bool live = u < u1;
@@ -499,7 +567,14 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
 #pragma unroll
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 4 + wave;
-      if (live && instr < VI)
+      if constexpr (TAIL) {
+        if (live && instr < VI) {
+          const int row = instr * 16 + lrow;
+          rf_glds16(vb + (int64_t)(row < last ? row : last) * p.v_l + c_src * 8, st + instr * 1024);
+        } else {
+          rf_glds16(g_tied_zero16, smem + DUMP);
+        }
+      } else if (live && instr < VI)
         rf_glds16(vb + (int64_t)(instr * 16) * p.v_l + lane_off, st + instr * 1024);
       else
         rf_glds16(g_tied_zero16, smem + DUMP);
@@ -527,11 +602,27 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
     const int uend = (bh + 1) * p.N < u1 ? (bh + 1) * p.N : u1;
     h16x8 af[RT][KS];  // att[i = 16 t + fr][32 s + 8 fq .. +7]
     {
-      const h16_t* ab = p.att + ((int64_t)bh * L + wave * (16 * RT)) * L;
+      if constexpr (TAIL) {
+        const h16_t* ab = p.att + (int64_t)bh * p.len * p.att_ld;
 #pragma unroll
-      for (int t = 0; t < RT; ++t)
+        for (int t = 0; t < RT; ++t) {
+          const int row = wave * (16 * RT) + t * 16 + fr;
+          const h16_t* ar = ab + (int64_t)(row < last ? row : last) * p.att_ld;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) af[t][s] = *(const h16x8*)(ab + (int64_t)(t * 16 + fr) * L + s * 32 + fq * 8);
+          for (int s = 0; s < KS; ++s) {
+            TFrag f;
+            f.u[0] = f.u[1] = f.u[2] = f.u[3] = 0u;
+            if (s * 32 + fq * 8 < p.att_ld) f.v = *(const h16x8*)(ar + s * 32 + fq * 8);
+            af[t][s] = f.v;
+          }
+        }
+      } else {
+        const h16_t* ab = p.att + ((int64_t)bh * L + wave * (16 * RT)) * L;
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+          for (int s = 0; s < KS; ++s) af[t][s] = *(const h16x8*)(ab + (int64_t)(t * 16 + fr) * L + s * 32 + fq * 8);
+      }
       // drain here (this also retires every DMA issued so far) and make the fragments opaque, so that the compiler's own
       // wait for these loads sits in front of the unit loop and not inside it
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -542,7 +633,10 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
     }
     for (; u < uend; ++u) {
       // unit u's tile landed once only the younger operations are outstanding: per later unit PW DMAs + 2 RT stores
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * (NSTG - 2) + (NSTG - 1) * 2 * RT) : "memory");
+      if constexpr (TAIL)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * (NSTG - 2) + (NSTG - 1) * 2 * RT) : "memory");
       __builtin_amdgcn_s_barrier();
       stage(u + NSTG - 1);
       const char* st = smem + ((u - u0) % NSTG) * STAGE;
@@ -595,13 +689,13 @@ __global__ __launch_bounds__(256, 1) void tied_av_kernel(const TiedAvP p) {
           uint2 w;
           w.x = rf_pack2_h16(acc[t][c][0], acc[t][c][1]);
           w.y = rf_pack2_h16(acc[t][c][2], acc[t][c][3]);
-          *(uint2*)(ob + (int64_t)(t * 16) * p.o_l + c * 16) = w;
+          if (!TAIL || wave * (16 * RT) + t * 16 + fr <= last) *(uint2*)(ob + (int64_t)(t * 16) * p.o_l + c * 16) = w;
         }
     }
   }
 }
 
-template <int L>
+template <int L, bool TAIL>
 static int launch_tied_av(TiedAvP& p, hipStream_t s) {
   const int ncu = rf_num_cus() > 0 ? rf_num_cus() : 256;
   p.nunits = p.B * p.H * p.N;
@@ -609,15 +703,24 @@ static int launch_tied_av(TiedAvP& p, hipStream_t s) {
   if (grid > p.nunits) grid = p.nunits;
   p.units_per_wg = (p.nunits + grid - 1) / grid;
   grid = (p.nunits + p.units_per_wg - 1) / p.units_per_wg;
-  if (const int e = rf_enable_big_lds<tied_av_kernel<L>>()) return e;
-  hipLaunchKernelGGL(tied_av_kernel<L>, dim3((unsigned)grid), dim3(256), 4 * L * 64 + 1024, s, p);
+  if (const int e = rf_enable_big_lds<tied_av_kernel<L, TAIL>>()) return e;
+  hipLaunchKernelGGL((tied_av_kernel<L, TAIL>), dim3((unsigned)grid), dim3(256), 4 * L * 64 + 1024, s, p);
   return rf_launch_status();
 }
 
-extern "C" int rf_tied_av(const void* att, const void* v, const int64_t v_strides[4], void* out, const int64_t o_strides[4],
-                          int B, int H, int N, int L, int d_head, void* stream) {
+static bool tied_is_tile(int L) { return L == 64 || L == 128 || L == 192 || L == 256; }
+
+// att_ld: elements between rows of att (see rfmi.h).  RF_EINVAL: L outside 1 .. 256 or att_ld < L; RF_EALIGN: att_ld % 8.
+static int tied_ld_check(int L, int64_t att_ld) {
+  if (L < 1 || L > 256 || att_ld < L) return RF_EINVAL;
+  return att_ld % 8 ? RF_EALIGN : 0;
+}
+
+extern "C" int rf_tied_av_ld(const void* att, int64_t att_ld, const void* v, const int64_t v_strides[4], void* out,
+                             const int64_t o_strides[4], int B, int H, int N, int L, int d_head, void* stream) {
   if (!att || !v || !out || B <= 0 || H <= 0 || N <= 0) return RF_EINVAL;
-  if (d_head != 32 || (L != 64 && L != 128 && L != 192 && L != 256)) return RF_EINVAL;
+  if (d_head != 32) return RF_EINVAL;
+  if (const int e = tied_ld_check(L, att_ld)) return e;
   if (((uintptr_t)att % 16) || ((uintptr_t)v % 16) || ((uintptr_t)out % 8)) return RF_EALIGN;
   for (int i = 0; i < 4; ++i)
     if (v_strides[i] % 8 || o_strides[i] % 4) return RF_EALIGN;
@@ -627,22 +730,39 @@ extern "C" int rf_tied_av(const void* att, const void* v, const int64_t v_stride
   p.v_b = v_strides[0]; p.v_n = v_strides[1]; p.v_h = v_strides[2]; p.v_l = v_strides[3];
   p.o_b = o_strides[0]; p.o_n = o_strides[1]; p.o_h = o_strides[2]; p.o_l = o_strides[3];
   p.B = B; p.H = H; p.N = N;
+  p.len = L; p.att_ld = att_ld;
   hipStream_t s = (hipStream_t)stream;
-  if (L == 256) return launch_tied_av<256>(p, s);
-  if (L == 192) return launch_tied_av<192>(p, s);
-  if (L == 128) return launch_tied_av<128>(p, s);
-  return launch_tied_av<64>(p, s);
+  const int tile = tied_tile(L);
+  const bool tail = L != tile || att_ld != L;
+#define RF_TIED_AV(L_) \
+  if (tile == L_) return tail ? launch_tied_av<L_, true>(p, s) : launch_tied_av<L_, false>(p, s);
+  RF_TIED_AV(256)
+  RF_TIED_AV(192)
+  RF_TIED_AV(128)
+#undef RF_TIED_AV
+  return tail ? launch_tied_av<64, true>(p, s) : launch_tied_av<64, false>(p, s);
+}
+
+extern "C" int rf_tied_av(const void* att, const void* v, const int64_t v_strides[4], void* out, const int64_t o_strides[4],
+                          int B, int H, int N, int L, int d_head, void* stream) {
+  if (!tied_is_tile(L)) return RF_EINVAL;
+  return rf_tied_av_ld(att, L, v, v_strides, out, o_strides, B, H, N, L, d_head, stream);
 }
 
 // Logits + softmax of the tied attention on head-major operands (with the position weights folded in when w != NULL), optional
 // symmetrised map.  L in {64, 128, 192, 256} (one-pass kernel, or the contraction-split form at 256 when a workspace is given)
 // or L in {512, 768, 1024} (contraction-split form over 128-query x 256-key tiles: needs the workspace).
-extern "C" int rf_tied_logits(const void* q, const void* k, const int64_t qk_strides[4], const float* w,
-                              const int64_t w_strides[3], float qscale, void* att, float* att_sym, int64_t sym_ld, int B, int H,
-                              int N, int L, int d_head, float* partial_ws, int64_t partial_ws_elems, void* stream) {
+// (rf_tied_logits_ld: the same with a row pitch for att and any 1 <= L <= 256 on the one-pass kernel; the contraction-split
+// forms keep their lengths and a dense att)
+extern "C" int rf_tied_logits_ld(const void* q, const void* k, const int64_t qk_strides[4], const float* w,
+                                 const int64_t w_strides[3], float qscale, void* att, int64_t att_ld, float* att_sym,
+                                 int64_t sym_ld, int B, int H, int N, int L, int d_head, float* partial_ws,
+                                 int64_t partial_ws_elems, void* stream) {
   if (!q || !k || !att || B <= 0 || H <= 0 || N <= 0) return RF_EINVAL;
-  const bool small = L == 64 || L == 128 || L == 192 || L == 256;
-  if (d_head != 32 || !(small || (L % 256 == 0 && L <= 1024))) return RF_EINVAL;
+  const bool small = L >= 1 && L <= 256;
+  const bool dense = att_ld == L;
+  if (d_head != 32 || att_ld < L || !(small || (dense && L > 0 && L % 256 == 0 && L <= 1024))) return RF_EINVAL;
+  if (att_ld % 8) return RF_EALIGN;
   if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16)) return RF_EALIGN;
   for (int i = 0; i < 4; ++i)
     if (qk_strides[i] % 8) return RF_EALIGN;
@@ -656,28 +776,47 @@ extern "C" int rf_tied_logits(const void* q, const void* k, const int64_t qk_str
   p.w_b = w ? w_strides[0] : 0; p.w_h = w ? w_strides[1] : 0; p.w_n = w ? w_strides[2] : 0;
   p.qscale = qscale;
   p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
+  p.len = L; p.att_ld = att_ld;
   p.dbg = tied_dbg();
   if (p.dbg < 0) return p.dbg;
   hipStream_t s = (hipStream_t)stream;
-  int rc = tied_logits_split(p, L, partial_ws, partial_ws_elems, s);
-  if (rc == 1) rc = small ? tied_logits_dispatch(p, L, s) : RF_EINVAL;  // (long rows have no one-pass kernel: the workspace is required)
+  int rc = dense ? tied_logits_split(p, L, partial_ws, partial_ws_elems, s) : 1;
+  if (rc == 1) rc = small ? tied_logits_dispatch(p, s) : RF_EINVAL;  // (long rows have no one-pass kernel: the workspace is required)
   if (rc != 0) return rc;
-  if (att_sym && (rc = tied_sym(att, att_sym, sym_ld, B, H, L, s)) != 0) return rc;
+  if (att_sym && (rc = tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s)) != 0) return rc;
   return 0;
+}
+
+extern "C" int rf_tied_logits(const void* q, const void* k, const int64_t qk_strides[4], const float* w,
+                              const int64_t w_strides[3], float qscale, void* att, float* att_sym, int64_t sym_ld, int B, int H,
+                              int N, int L, int d_head, float* partial_ws, int64_t partial_ws_elems, void* stream) {
+  if (!(tied_is_tile(L) || (L > 0 && L % 256 == 0 && L <= 1024))) return RF_EINVAL;
+  return rf_tied_logits_ld(q, k, qk_strides, w, w_strides, qscale, att, L, att_sym, sym_ld, B, H, N, L, d_head, partial_ws,
+                           partial_ws_elems, stream);
 }
 
 // Tied attention core in one call: rf_tied_logits, then attention . V.  q / k / v / out strides: {b, n, h, l} in elements, the
 // 32-wide head slice contiguous.  L in {64, 128, 192, 256} (attention . V keeps whole probability rows in registers).
+extern "C" int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int64_t qk_strides[4],
+                                    const int64_t v_strides[4], const float* w, const int64_t w_strides[3], float qscale,
+                                    void* att, int64_t att_ld, float* att_sym, int64_t sym_ld, void* out,
+                                    const int64_t o_strides[4], int B, int H, int N, int L, int d_head, float* partial_ws,
+                                    int64_t partial_ws_elems, void* stream) {
+  if (!v || !out) return RF_EINVAL;
+  if (const int e = tied_ld_check(L, att_ld)) return e;
+  const int rc = rf_tied_logits_ld(q, k, qk_strides, w, w_strides, qscale, att, att_ld, att_sym, sym_ld, B, H, N, L, d_head,
+                                   partial_ws, partial_ws_elems, stream);
+  if (rc != 0) return rc;
+  return rf_tied_av_ld(att, att_ld, v, v_strides, out, o_strides, B, H, N, L, d_head, stream);
+}
+
 extern "C" int rf_tied_attention(const void* q, const void* k, const void* v, const int64_t qk_strides[4],
                                  const int64_t v_strides[4], const float* w, const int64_t w_strides[3], float qscale,
                                  void* att, float* att_sym, int64_t sym_ld, void* out, const int64_t o_strides[4], int B,
                                  int H, int N, int L, int d_head, float* partial_ws, int64_t partial_ws_elems, void* stream) {
-  if (!v || !out) return RF_EINVAL;
-  if (L != 64 && L != 128 && L != 192 && L != 256) return RF_EINVAL;
-  const int rc = rf_tied_logits(q, k, qk_strides, w, w_strides, qscale, att, att_sym, sym_ld, B, H, N, L, d_head, partial_ws,
-                                partial_ws_elems, stream);
-  if (rc != 0) return rc;
-  return rf_tied_av(att, v, v_strides, out, o_strides, B, H, N, L, d_head, stream);
+  if (!tied_is_tile(L)) return RF_EINVAL;
+  return rf_tied_attention_ld(q, k, v, qk_strides, v_strides, w, w_strides, qscale, att, L, att_sym, sym_ld, out, o_strides,
+                              B, H, N, L, d_head, partial_ws, partial_ws_elems, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -70,7 +70,7 @@ def _(x, gamma, beta, eps, out_fp32):
 
 @torch.library.custom_op("rfmi::tied_row_attention", mutates_args=(), device_types="cuda")
 def tied_row_attention(q: Tensor, k: Tensor, v: Tensor) -> Tuple[Tensor, Tensor]:
-    """q (already scaled by the position weights and d_h^-0.5, rf.py:252), k, v: bf16 [B, N, L, H, 32].
+    """q (already scaled by the position weights and d_h^-0.5, rf.py:252), k, v: bf16 [B, N, L, H, 32], any 1 <= L <= 256.
     Returns (out bf16 [B, N, L, H*32], symmetrised attention map fp32 [B, L, L, H])."""
     with _guard(q):
         return ops.tied_row_attention(q, k, v)

@@ -215,12 +215,21 @@ class RFModule(nn.Module):
     def values_transposed(self, lin, xn, bias):
         """lin(xn) written key-contiguous: xn T [B,N,L,D] -> v_t T [B,N,D,L], v_t[b,n,(h,d),l] = (W xn[b,n,l] + bias)[(h,d)]
         (one GEMM per MSA row with the weight as the A operand, so the transposition costs no pass of its own): the B operand
-        of the attention . V GEMMs, which contract over l."""
+        of the attention . V GEMMs, which contract over l.  16-bit modes: the key axis has the leading dimension
+        Lp = ops.tied_ld(L) (v_t is [B,N,D,Lp]) with exact zeros in the pad columns, so that the contraction over Lp is a legal K
+        of the 16-bit GEMM at any L; Lp == L, and the buffer is what it always was, when L % 8 == 0."""
         B, N, Lr, D = xn.shape
-        v_t = torch.empty(B, N, D, Lr, device=xn.device, dtype=T())
+        Lp = map_ld(Lr)
+        v_t = (torch.empty if Lp == Lr else ops.zeros)(B, N, D, Lp, device=xn.device, dtype=T())
         ops.gemm(self.wt("v", lin), xn, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
-                 c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=bias, bias_mode=L.BIAS_ROW)
+                 c_bs=(D * Lp, 0, 0), c_row=(0, 0, Lp), bias=bias, bias_mode=L.BIAS_ROW)
         return v_t
+
+
+def map_ld(Lr):
+    """Leading dimension of an attention map [.., L, L] and of key-contiguous values [.., D, L] in the current compute dtype:
+    L in float32, L rounded up to a multiple of 8 in the 16-bit modes (ops.tied_ld; zero pad columns on both operands)."""
+    return ops.tied_ld(Lr) if ops.is_h16(T()) else Lr
 
 
 class RecordingModule(RFModule):
@@ -613,6 +622,11 @@ class PositionWiseWeightFactor(RFModule):
         return w.unsqueeze(-1)  # b N h l 1
 
 
+# Shortest chain that fills no tile of the fused tied-attention kernels (ops.TIED_TILES) and still takes them, on their tail
+# instantiations; below it the general path (rf_gemm + rf_tied_softmax + attention_values) runs.  See DESIGN.md 7g.
+TIED_RAGGED_MIN_L = 40
+
+
 class SoftTiedAttentionOverResidues(RFModule):
     """rf.py:220-267."""
 
@@ -642,6 +656,11 @@ class SoftTiedAttentionOverResidues(RFModule):
         if (RT.fused_tied and RT.tied_v2 and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256) and H <= 16
                 and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16) and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384
                 and (6 if Lr >= 256 else 8) * (4096 + Lr * 64) + 1024 + N * 256 <= 160 * 1024):
+            return self.attend_head_major(xn, x_res, want_att, next_ln, drops)
+        if (RT.fused_tied and RT.tied_v2 and Lr not in ops.TIED_TILES and Lr >= TIED_RAGGED_MIN_L
+                and ops.tied_fused_applies(Lr, N, T(), dh, w=not self.folds_weights(B * N * Lr)) and H <= 16
+                and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)):
+            # a chain that fills no tile: the same route on the tail instantiations of the kernels (rf_tied_attention_ld)
             return self.attend_head_major(xn, x_res, want_att, next_ln, drops)
         if (RT.fused_tied and RT.tied_v2 and RT.tied_fold_w and ops.is_h16(T()) and dh == 32 and Lr in (512, 768, 1024) and H <= 16
                 and ops.gemm_takes_row_scale(B * N * Lr, 2 * D, D) and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)
@@ -674,7 +693,7 @@ class SoftTiedAttentionOverResidues(RFModule):
         v_t = self.values_transposed(self.to_v, xn, bv)
         # logits[b,h,i,j] = sum_{n,d} q k   (contraction over N*dh, rf.py:254), softmax over j (rf.py:255)
         W3 = 3 * D
-        att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
+        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by tied_softmax)
         att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
         if RT.fused_tied and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256):
             # one launch: 6-8-stage DMA ring over the N steps, logits in registers, wave-local softmax (csrc/tied.hip)
@@ -690,15 +709,22 @@ class SoftTiedAttentionOverResidues(RFModule):
         xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
         return att_sym, xn_next
 
+    def folds_weights(self, rows):
+        """the head-major q|k|v projection of `rows` MSA positions folds w * d_head^-0.5 into q (attend_head_major)"""
+        D = self.n_heads * self.d_head
+        return RT.tied_fold_w and self.d_head % 16 == 0 and ops.gemm_takes_row_scale(rows, 3 * D, D)
+
     def attention_values(self, att, v_t):
-        """out[b,n,i,(h,d)] = sum_j att[b,h,i,j] v[b,n,h,j,d]   (rf.py:257-258): att T [B,H,L,L], v_t T [B,N,D,L]
-        (values_transposed) -> T [B,N,L,D], one GEMM per (b, head) over all N rows."""
-        B, N, D, Lr = v_t.shape
+        """out[b,n,i,(h,d)] = sum_j att[b,h,i,j] v[b,n,h,j,d]   (rf.py:257-258): att T [B,H,L,Lp], v_t T [B,N,D,Lp]
+        (values_transposed; Lp = map_ld(L): the contraction runs over Lp, both operands hold zeros in their pad columns)
+        -> T [B,N,L,D], one GEMM per (b, head) over all N rows."""
+        B, N, D, Lp = v_t.shape
+        Lr = att.shape[2]
         H, dh = self.n_heads, self.d_head
         out = torch.empty(B, N, Lr, D, device=v_t.device, dtype=T())
-        ops.gemm(att, v_t, out, Lr, N * dh, Lr, batch=(B, H, 1),
-                 a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
-                 b_bs=(N * D * Lr, dh * Lr, 0), b_row=(dh, D * Lr, Lr),
+        ops.gemm(att, v_t, out, Lr, N * dh, Lp, batch=(B, H, 1),
+                 a_bs=(H * Lr * Lp, Lr * Lp, 0), a_row=(0, 0, Lp),
+                 b_bs=(N * D * Lp, dh * Lp, 0), b_row=(dh, D * Lp, Lp),
                  c_bs=(N * Lr * D, dh, 0), c_row=(0, 0, D), c_col=(dh, Lr * D))
         return out
 
@@ -713,18 +739,25 @@ class SoftTiedAttentionOverResidues(RFModule):
         G = 3 * H
         lins = [self.to_q, self.to_k, self.to_v]
         w = self.poswise_weight.weights_head_major(xn)  # fp32 [B,H,N,L]
+        ragged = Lr not in ops.TIED_TILES
         qkv = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
         # q * w * d_head^-0.5 (rf.py:252) in the projection's epilogue, on the fp32 accumulators: q is rounded once, after
         # the scaling, and the logits kernel neither stages the weights nor rescales its fragments (round 2: 15-20 us of VALU)
         # ... when the projection runs on the kernel whose epilogue knows the row-group scale (d_msa = 288: N = 864 does not)
-        fold = RT.tied_fold_w and dh % 16 == 0 and ops.gemm_takes_row_scale(B * N * Lr, 3 * D, D)
+        fold = self.folds_weights(B * N * Lr)
+        if ragged and not fold and Lr % 4:
+            # the logits kernel stages w by 16-byte pieces: rows padded to a multiple of 4 floats (the pad is read, its values
+            # scale query rows past the chain only, which are never stored)
+            Lw = (Lr + 3) // 4 * 4
+            w = ops.copy4d(w, (H * N * Lr, N * Lr, Lr, 1), ops.zeros(B, H, N, Lw, device=dev, dtype=F32),
+                           (H * N * Lw, N * Lw, Lw, 1), (B, H, N, Lr))
         bqkv, bo = self.bcat("qkv", lins), _f(self.to_out.bias)
         if RT.condition and RT.condition_values:
             bqkv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out, lead=(self.to_q, self.to_k)))
         ops.gemm(xn, self.wcat("qkv", lins), qkv, B * N * Lr, 3 * D, D, bias=bqkv,
                  c_row=(Lr, G * Lr * dh, dh), c_col=(dh, Lr * dh),
                  rs=(w, H * N * Lr, N * Lr, dh, D, self.scale) if fold else None)
-        att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
+        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by the logits kernel)
         att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
         out = torch.empty(B, N, Lr, D, device=dev, dtype=T())
         ops.tied_attention(qkv[:, :, 0:H], qkv[:, :, H:2 * H], qkv[:, :, 2 * H:], out.view(B, N, Lr, H, dh).permute(0, 1, 3, 2, 4),
@@ -1708,7 +1741,7 @@ class MsaUpdateWithPairLayer(RFModule):
 
     def _add_attention_values(self, att, v_t, dst):
         """dst += att @ v  (rf.py:592-595), scattered back to [b,n,i,(h,d)]: att T [H,B,h,L] (h query rows: all L, or a rank's
-        block), v_t T [B,N,D,L], dst fp32 [B,N,h,D]."""
+        block), v_t T [B,N,D,L], dst fp32 [B,N,h,D].  (L here is the operands' key extent map_ld(L): zero pad columns on both.)"""
         H, B, h, Lr = att.shape
         N, D = v_t.shape[1], v_t.shape[2]
         dv = D // H
@@ -1729,8 +1762,8 @@ class MsaUpdateWithPairLayer(RFModule):
 def pair_to_att(layers, pair, row_group=None):
     """Shared front of the MsaUpdateWithPairLayer stack of one block (they all see the same pair):
     one symmetrise+normalise pass, one GEMM for every layer's head logits, per-(layer,head) softmax.
-    Returns a list of T [H,B,L,L] ([H,B,h,L] for a block of h pair rows: row_group, the transposed sub-blocks of the
-    symmetrisation come from the other ranks)."""
+    Returns a list of T [H,B,L,Lp] ([H,B,h,Lp] for a block of h pair rows: row_group, the transposed sub-blocks of the
+    symmetrisation come from the other ranks); Lp = map_ld(L), columns L..Lp are zeros."""
     B, h, Lr, Dp = pair.shape   # (h == L: the whole picture)
     holder = layers[0]
     H, nl = holder.n_heads, len(layers)
@@ -1755,9 +1788,11 @@ def pair_to_att(layers, pair, row_group=None):
     if holder.training and row_group is None:   # (the row-sharded forward is the inference path: shard.forward_row_sharded)
         dropout_(logits, _p(holder.pair2att[3]))   # rf.py:567: Dropout sits between the projection and the softmax
     # every (layer, head) softmax in one launch: problem z = li*H + h is column z of the logits
-    att_all = torch.empty(nl, H, B, h, Lr, device=pair.device, dtype=T())
+    # (16-bit modes: rows Lp = map_ld(L) apart with zeros in the pad columns, the contraction of _add_attention_values runs over Lp)
+    Lp = map_ld(Lr)
+    att_all = (torch.empty if Lp == Lr else ops.zeros)(nl, H, B, h, Lp, device=pair.device, dtype=T())
     if h > 0:
-        ops.softmax_batched(logits, 1, Lr * NH, NH, att_all, B * h * Lr, Lr, B * h, Lr, NH)
+        ops.softmax_batched(logits, 1, Lr * NH, NH, att_all, B * h * Lp, Lp, B * h, Lr, NH)
     return [att_all[li] for li in range(nl)]
 
 

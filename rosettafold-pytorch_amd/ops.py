@@ -225,22 +225,66 @@ def _hstrides(t):
     return I64x4(t.stride(0), t.stride(1), t.stride(2), t.stride(3))
 
 
+TIED_TILES = (64, 128, 192, 256)  # chain lengths that fill a tile of the fused tied-attention kernels
+
+
+def tied_ld(L_):
+    """Leading dimension of a 16-bit attention map (and of key-contiguous values) of a chain of L residues: L rounded up to a
+    multiple of 8, so that every row is 16-byte aligned and the contraction over it is a legal K of the 16-bit GEMM."""
+    return (L_ + 7) // 8 * 8
+
+
+def tied_fused_applies(L_, N, dtype, dh=32, w=True):
+    """Python mirror of what rf_tied_attention_ld accepts (the one-pass logits + softmax kernel, then attention . V): 16-bit
+    operands, d_head 32, 1 <= L <= 256, and a ring + position-weight tile that fit the 160 KB of LDS (w: the weights are
+    applied in the kernel, which stages them four MSA rows per DMA instruction)."""
+    if not (is_h16(dtype) and dh == 32 and 1 <= L_ <= 256 and N >= 1):
+        return False
+    if w and N % 4:
+        return False
+    tile = (L_ + 63) // 64 * 64
+    return (6 if tile >= 256 else 8) * (4096 + tile * 64) + 1024 + (N * 256 if w else 0) <= 160 * 1024
+
+
+def _att_ld(att, L_):
+    """att: [B, H, L, att_ld] contiguous with att_ld >= L (columns past L: the zero pad the kernels write)."""
+    if att.dim() != 4 or not att.is_contiguous() or att.shape[2] != L_ or att.shape[3] < L_:
+        raise ValueError("att must be a contiguous [B, H, L, att_ld] tensor with att_ld >= L")
+    return att.shape[3]
+
+
+def _w_strides(w, B, H, N, L_):
+    if w is None:
+        return I64x3(0, 0, 0)
+    if w.dim() != 4 or w.stride(3) != 1 or tuple(w.shape[:3]) != (B, H, N) or w.shape[3] < L_:
+        raise ValueError("w must be [B, H, N, >= L] with contiguous L")
+    return I64x3(w.stride(0), w.stride(1), w.stride(2))
+
+
 def tied_attention(q, k, v, out, att, w=None, qscale=1.0, att_sym=None, partial_ws=None):
     """Tied MSA-row attention core (csrc/tied.hip).  q, k, v, out: bf16 views indexed [B, N, H, L, 32] (any strides with
-    a contiguous head slice); att: bf16 [B, H, L, L] (workspace + result); w: fp32 [B, H, N, L] position weights folded
-    into the logits kernel (None: q already carries them); att_sym: fp32 [B, L, L, H] or None.  partial_ws: fp32 workspace
-    for the contraction-split logits (L == 256); allocated here when None, pass False to force the one-pass kernel."""
+    a contiguous head slice); att: bf16 [B, H, L, att_ld] (workspace + result; att_ld = L, or any multiple of 8 >= L: the
+    kernels write zeros past column L); w: fp32 [B, H, N, L] position weights folded into the logits kernel (None: q already
+    carries them; rows padded to a multiple of 4 floats when L % 4 != 0); att_sym: fp32 [B, L, L, H] or None.  partial_ws: fp32
+    workspace for the contraction-split logits (L == 256); allocated here when None, pass False to force the one-pass kernel.
+    A chain that fills a tile (L in TIED_TILES, dense att) goes to rf_tied_attention, every other to rf_tied_attention_ld."""
     B, N, H, L_, dh = q.shape
-    if partial_ws is None and L_ == 256 and N % 2 == 0:
+    att_ld = _att_ld(att, L_)
+    if partial_ws is None and L_ == 256 and att_ld == L_ and N % 2 == 0:
         partial_ws = torch.empty((4 if N > 128 else 2) * B * H * L_ * L_, device=q.device, dtype=F32)
     if partial_ws is False:
         partial_ws = None
     _need_cuda(q, k, v, out, att, w, att_sym, partial_ws)
     if q.stride() != k.stride():
         raise ValueError("q and k must share their strides")
-    ws = I64x3(w.stride(0), w.stride(1), w.stride(2)) if w is not None else I64x3(0, 0, 0)
-    if w is not None and (w.stride(3) != 1 or tuple(w.shape) != (B, H, N, L_)):
-        raise ValueError("w must be [B, H, N, L] with contiguous L")
+    ws = _w_strides(w, B, H, N, L_)
+    if not (L_ in TIED_TILES and att_ld == L_):
+        check(lib.rf_tied_attention_ld(ptr(q), ptr(k), ptr(v), C.byref(_hstrides(q)), C.byref(_hstrides(v)), ptr(w), C.byref(ws),
+                                       float(qscale), ptr(att), att_ld, ptr(att_sym),
+                                       att_sym.shape[-1] if att_sym is not None else 0, ptr(out), C.byref(_hstrides(out)), B, H,
+                                       N, L_, dh, ptr(partial_ws), partial_ws.numel() if partial_ws is not None else 0,
+                                       stream()), "rf_tied_attention_ld")
+        return out
     check(lib.rf_tied_attention(ptr(q), ptr(k), ptr(v), C.byref(_hstrides(q)), C.byref(_hstrides(v)), ptr(w), C.byref(ws),
                                 float(qscale), ptr(att), ptr(att_sym), att_sym.shape[-1] if att_sym is not None else 0,
                                 ptr(out), C.byref(_hstrides(out)), B, H, N, L_, dh, ptr(partial_ws),
@@ -249,6 +293,30 @@ def tied_attention(q, k, v, out, att, w=None, qscale=1.0, att_sym=None, partial_
 
 
 COUNTERS = {"tied_logits_long": 0}  # launches of paths a test wants to see taken
+
+
+def tied_logits_ld(q, k, att, w=None, qscale=1.0, att_sym=None):
+    """rf_tied_logits_ld on head-major q / k views [B, N, H, L, 32], one-pass kernel: att 16-bit [B, H, L, att_ld] (see
+    tied_attention), any 1 <= L <= 256."""
+    B, N, H, L_, dh = q.shape
+    att_ld = _att_ld(att, L_)
+    _need_cuda(q, k, att, w, att_sym)
+    if q.stride() != k.stride():
+        raise ValueError("q and k must share their strides")
+    check(lib.rf_tied_logits_ld(ptr(q), ptr(k), C.byref(_hstrides(q)), ptr(w), C.byref(_w_strides(w, B, H, N, L_)), float(qscale),
+                                ptr(att), att_ld, ptr(att_sym), att_sym.shape[-1] if att_sym is not None else 0, B, H, N, L_, dh,
+                                None, 0, stream()), "rf_tied_logits_ld")
+    return att
+
+
+def tied_av_ld(att, v, out):
+    """rf_tied_av_ld: att 16-bit [B, H, L, att_ld] with zeros past column L, v / out views [B, N, H, L, 32], 1 <= L <= 256."""
+    B, N, H, L_, dh = v.shape
+    att_ld = _att_ld(att, L_)
+    _need_cuda(att, v, out)
+    check(lib.rf_tied_av_ld(ptr(att), att_ld, ptr(v), C.byref(_hstrides(v)), ptr(out), C.byref(_hstrides(out)), B, H, N, L_, dh,
+                            stream()), "rf_tied_av_ld")
+    return out
 
 
 def tied_logits(q, k, att, att_sym=None, qscale=1.0):
@@ -272,10 +340,11 @@ def tied_logits(q, k, att, att_sym=None, qscale=1.0):
 
 
 def tied_row_attention(q, k, v):
-    """Functional form for the dispatcher op: q, k, v h16 [B, N, L, H, 32] -> (out [B, N, L, H*32], att_sym [B, L, L, H])."""
+    """Functional form for the dispatcher op: q, k, v h16 [B, N, L, H, 32] -> (out [B, N, L, H*32], att_sym [B, L, L, H]).
+    L in TIED_TILES, or any 1 <= L <= 256 (the attention map then has the leading dimension tied_ld(L): rf_tied_attention_ld)."""
     B, N, L_, H, dh = q.shape
     out = torch.empty(B, N, L_, H * dh, device=q.device, dtype=q.dtype)
-    att = torch.empty(B, H, L_, L_, device=q.device, dtype=q.dtype)
+    att = torch.empty(B, H, L_, tied_ld(L_), device=q.device, dtype=q.dtype)
     sym = torch.empty(B, L_, L_, H, device=q.device, dtype=F32)
     hm = lambda t: t.permute(0, 1, 3, 2, 4)  # noqa: E731  [B, N, H, L, 32] view
     tied_attention(hm(q.contiguous()), hm(k.contiguous()), hm(v.contiguous()), hm(out.view(B, N, L_, H, dh)), att, att_sym=sym)
@@ -345,8 +414,14 @@ def poswise_collapsed(xn, u, scale):
 
 
 def tied_softmax(logits, att, att_sym=None, sym_ld=0):
+    """att = softmax over the last dim of fp32 logits [B, H, L, L] (+ the symmetrised map); att [B, H, L, L], or
+    [B, H, L, att_ld] with att_ld a multiple of 8 above L: the pad columns are written as zeros (rf_tied_softmax_ld)."""
     B, H, L_, _ = logits.shape
     _need_cuda(logits, att, att_sym)
+    if att.shape[-1] != L_:
+        check(lib.rf_tied_softmax_ld(ptr(logits), ptr(att), dcode(att.dtype), _att_ld(att, L_), ptr(att_sym), sym_ld, B, H, L_,
+                                     stream()), "rf_tied_softmax_ld")
+        return
     check(lib.rf_tied_softmax(ptr(logits), ptr(att), dcode(att.dtype), ptr(att_sym), sym_ld, B, H, L_, stream()),
           "rf_tied_softmax")
 

@@ -11,6 +11,40 @@ def timeit(fn, iters=20):
     for _ in range(iters): fn()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / iters
+if "--ragged" in sys.argv:
+    # python tools/tied_bench.py --ragged [out.json]: SoftTiedAttentionOverResidues.attend (projections, position weights and output
+    # projection included) at the config-2 MSA shape, bf16, at chain lengths that fill no tile of the fused kernels (and at 256 and
+    # 304 for scale): the route the model takes against the general path (rf_gemm logits + rf_tied_softmax + v^T GEMM + generic
+    # A.V; RT.tied_v2 = False), and the same with the symmetrised map.  Eager launches, min of 3 windows.
+    import json
+    B, H, N, D = 4, 12, 128, 384
+    m = R.SoftTiedAttentionOverResidues(D, H, 0.0, return_att=True).cuda()
+    def attend_ms(L, v2, want_att, iters):
+        xn = torch.randn(B, N, L, D, device="cuda").bfloat16()
+        res = torch.zeros(B, N, L, D, device="cuda")
+        R.RT.tied_v2 = v2
+        try:
+            return min(timeit(lambda: m.attend(xn, res, want_att), iters) for _ in range(3))
+        except ops.L.RfmiError as e:  # (a tree without the padded leading dimension refuses L % 8 != 0: RF_EALIGN)
+            print(f"   tied_v2={v2} refused: {e}", flush=True)
+            return None
+        finally:
+            R.RT.tied_v2 = True
+    rows = []
+    for L in (100, 137, 200, 255, 256, 304, 700, 17, 40, 72):  # (the last three: where a floor R.model.TIED_RAGGED_MIN_L would sit)
+        fused_route = L in ops.TIED_TILES or (L >= R.model.TIED_RAGGED_MIN_L and
+                                              ops.tied_fused_applies(L, N, torch.bfloat16, w=not m.folds_weights(B * N * L)))
+        iters = 5 if L >= 300 else 20
+        for want_att in (False, True):
+            td, tg = attend_ms(L, True, want_att, iters), attend_ms(L, False, want_att, iters)
+            rows.append(dict(L=L, B=B, N=N, D=D, H=H, want_att=want_att, default_route="fused" if fused_route else "general",
+                             default_ms=td, general_ms=tg, general_over_default=tg / td if td and tg else None))
+            f = lambda t: f"{t*1e3:.0f} us" if t else "refused"  # noqa: E731
+            print(f"L={L} att_sym={want_att}: default ({rows[-1]['default_route']}) {f(td)}, general {f(tg)}", flush=True)
+    out = [a_ for a_ in sys.argv[1:] if a_.endswith(".json")]
+    if out:
+        json.dump(rows, open(out[0], "w"), indent=1)
+    sys.exit(0)
 B, H, N, L, dh = 4, 12, 128, 256, 32
 D = H * dh
 fl = 2.0 * B * H * L * L * N * dh
