@@ -34,9 +34,10 @@ extern "C" {
 #define RF_BF16 1
 #define RF_F16 2
 /* rf_gemm_desc.ab_dtype only: A and B are fp32 in memory and each element x is split in the kernel into bf16 pieces
- * hi = bf16(x), lo = bf16(x - hi) (round to nearest even; lo = 0 when hi is not finite, so inf / NaN propagate as on the
- * exact path).  C = hi_a.hi_b + hi_a.lo_b + lo_a.hi_b with fp32 accumulation (v_mfma_f32_16x16x32_bf16, three per product;
- * lo.lo is dropped): the "high" float32 matmul precision of PyTorch.  The same bf16 pieces in both libraries, so librfmi.so and
+ * hi = bf16(x), lo = bf16(x - hi) (round to nearest even; lo = 0 when hi is not finite, and the two cross products take hi with
+ * its non-finite elements zeroed, so inf / NaN enter through hi_a.hi_b alone and propagate as on the exact path).
+ * C = hi_a.hi_b + hi_a.lo_b + lo_a.hi_b with fp32 accumulation (v_mfma_f32_16x16x32_bf16, three per product; lo.lo is
+ * dropped): the "high" float32 matmul precision of PyTorch.  The same bf16 pieces in both libraries, so librfmi.so and
  * librfmi_f16.so give identical results.  Error bound per element (|x| < 3.39e38, the bf16 range):
  *   |C - C_exact| <= (3 * 2^-16 + K * 2^-23) * sum_k |a_k| |b_k|   (+ the fp32 rounding of alpha / bias / residual)
  * (each dropped piece -- lo.lo, and the rounding of lo on either side -- is at most 2^-16 |a b|; random data sits orders of
@@ -74,6 +75,11 @@ extern "C" {
  * a_rc/b_rc/c_rc/c_cc <= 0 mean "no split" (offset = m*..ri, n).
  * RF_AMODE_CONV3X3: A is NHWC [conv_n, conv_h, conv_w, conv_c], m = pixel index, k = tap*C + c
  * (tap = 3*(di+1)+(dj+1)), zero padding, dilation conv_dil; a_* strides are ignored.
+ * Non-finite values: the result is NaN wherever the exact product, or the input of the activation, is NaN, in every kernel
+ * family and operand type (a Linear does not turn a NaN into -inf, a ReLU does not turn it into 0: RF_ACT_RELU and
+ * RF_ACT_RELU_EPS keep NaN like torch.relu); rf_ffn_fused's hidden ReLU follows the same rule.  +-inf leaves with its sign.
+ * alpha must be finite and non-zero: RF_EINVAL otherwise, for every ab_dtype (a product scaled by zero is a fill, not a
+ * contraction: rf_fill; the 16-bit kernels start their accumulators at bias / alpha).
  */
 typedef struct rf_gemm_desc {
   int32_t M, N, K;

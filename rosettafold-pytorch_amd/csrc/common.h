@@ -97,6 +97,10 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// NaN-propagating maximum, one v_maximum3_f32 on gfx950.  fmaxf returns its non-NaN argument: the branch-free epilogue
+// max(acc, lo) would hand a NaN product on as lo (-inf for a Linear, 0 behind a ReLU).  rf_gemm and rf_ffn_fused promise NaN there.
+__device__ __forceinline__ float rf_max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
 // Training-mode dropout mask (rf_dropout, csrc/ops.hip; replayed by the backward kernels): Philox4x32-10 keyed by the 64-bit

@@ -364,10 +364,10 @@ __global__ __launch_bounds__(512) void ffn_fused_kernel(const FfnP p) {
       // ReLU + rounding in registers: the accumulators of the two hidden tiles ARE this token tile's MFMA-B fragment of step B
       // (k slot 8 fq + j <-> h = 16 (j >> 2) + 4 fq + (j & 3)); the group's other token tile comes from the partner wave
       FfnFrag own;
-      own.u[0] = rf_pack2_h16(fmaxf(h[0][0], 0.f), fmaxf(h[0][1], 0.f));
-      own.u[1] = rf_pack2_h16(fmaxf(h[0][2], 0.f), fmaxf(h[0][3], 0.f));
-      own.u[2] = rf_pack2_h16(fmaxf(h[1][0], 0.f), fmaxf(h[1][1], 0.f));
-      own.u[3] = rf_pack2_h16(fmaxf(h[1][2], 0.f), fmaxf(h[1][3], 0.f));
+      own.u[0] = rf_pack2_h16(rf_max_nan(h[0][0], 0.f), rf_max_nan(h[0][1], 0.f));
+      own.u[1] = rf_pack2_h16(rf_max_nan(h[0][2], 0.f), rf_max_nan(h[0][3], 0.f));
+      own.u[2] = rf_pack2_h16(rf_max_nan(h[1][0], 0.f), rf_max_nan(h[1][1], 0.f));
+      own.u[3] = rf_pack2_h16(rf_max_nan(h[1][2], 0.f), rf_max_nan(h[1][3], 0.f));
       if (!(FFN_ABL & 32)) ffn_lds_write16(xb_own, own.q);
       // ---- step B: Y^T[n][tok] += W2[n, chunk] H[tok, chunk] on this wave's half of the columns, both token tiles ---------
       {

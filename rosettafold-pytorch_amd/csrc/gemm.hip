@@ -49,9 +49,9 @@ __device__ __forceinline__ void batch_decode(const rf_gemm_desc& d, int z, int& 
 __device__ __forceinline__ float elu_call(float x) { return x > 0.f ? x : __expf(x) - 1.f; }
 
 __device__ __forceinline__ float apply_act(float v, int act, float eps, bool valid) {
-  if (act == RF_ACT_RELU) return fmaxf(v, 0.f);
+  if (act == RF_ACT_RELU) return rf_max_nan(v, 0.f);
   if (act == RF_ACT_ELU) return elu_call(v);
-  if (act == RF_ACT_RELU_EPS) return valid ? fmaxf(v, 0.f) + eps : 0.f;
+  if (act == RF_ACT_RELU_EPS) return valid ? rf_max_nan(v, 0.f) + eps : 0.f;
   return v;
 }
 
@@ -365,8 +365,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_bf16_kernel(const Gemm
 #pragma unroll
               for (int j = 0; j < WN; ++j) {
                 const int nl = j * 16 + 4 * fq;
-                const float v0 = fmaxf(acc[i][j][0] * alpha, lo), v1 = fmaxf(acc[i][j][1] * alpha, lo);
-                const float v2 = fmaxf(acc[i][j][2] * alpha, lo), v3 = fmaxf(acc[i][j][3] * alpha, lo);
+                const float v0 = rf_max_nan(acc[i][j][0] * alpha, lo), v1 = rf_max_nan(acc[i][j][1] * alpha, lo);
+                const float v2 = rf_max_nan(acc[i][j][2] * alpha, lo), v3 = rf_max_nan(acc[i][j][3] * alpha, lo);
                 if constexpr (ESZ == 4) {
                   *(float4*)(lrow + nl * 4) = make_float4(v0, v1, v2, v3);
                 } else {
@@ -649,6 +649,16 @@ __device__ __forceinline__ void split2_bf16(float x0, float x1, unsigned (&out)[
   }
 }
 
+// a fragment of 8 bf16 with its non-finite elements (exponent all ones) replaced by +0.  Per packed pair: the exponent field
+// plus one carries into bit 15 / 31 exactly when it is all ones; (s | (s - (s >> 15))) widens that bit to its 16-bit half.
+typedef __attribute__((ext_vector_type(4))) unsigned rf_u32x4;
+__device__ __forceinline__ h16x8 bf16x8_finite_or_zero(h16x8 v) {
+  rf_u32x4 u = __builtin_bit_cast(rf_u32x4, v);
+  const rf_u32x4 s = ((u & 0x7f807f80u) + 0x00800080u) & 0x80008000u;
+  u &= ~(s | (s - (s >> 15)));
+  return __builtin_bit_cast(h16x8, u);
+}
+
 __device__ __forceinline__ float b_elem_f32(const rf_gemm_desc& d, const float* Bb, int n, int k) {
   if (n >= d.N || k >= d.K) return 0.f;
   return Bb[split_off(n, d.b_rc, d.b_ro, d.b_ri) + (int64_t)(k / d.kc) * d.b_ko + (k % d.kc)];
@@ -785,6 +795,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32split_kernel(const GemmP p) {
         bfr[s][j] = *(const h16x8*)(b_lds + s * B_IMG + (row * SPR + (fq ^ swz<BK>(row))) * 16);
       }
     }
+    // Only piece 0 can be inf / NaN (split2_bf16), and it must reach the accumulator through the leading product alone, where
+    // it meets the other operand's piece 0 (its sign, and 0 only for a true 0): against a later piece -- either sign, or 0 for a
+    // value bf16 holds exactly -- it gave inf - inf or inf * 0 where the exact product is +-inf.  The cross terms therefore take
+    // piece 0 with its non-finite elements zeroed; finite operands are untouched (the same bits as before).
+    h16x8 afz[WM], bfz[WN];
+#pragma unroll
+    for (int i = 0; i < WM; ++i) afz[i] = bf16x8_finite_or_zero(af[0][i]);
+#pragma unroll
+    for (int j = 0; j < WN; ++j) bfz[j] = bf16x8_finite_or_zero(bfr[0][j]);
     // pieces (sa, sb) with sa + sb = o, o from P - 1 down to 0: the small cross terms enter the accumulator before the
     // leading product
 #pragma unroll
@@ -794,9 +813,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32split_kernel(const GemmP p) {
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
-          for (int j = 0; j < WN; ++j)
+          for (int j = 0; j < WN; ++j) {
+            const h16x8 bb = (o > 0 && o - sa == 0) ? bfz[j] : bfr[o - sa][j];
+            const h16x8 aa = (o > 0 && sa == 0) ? afz[i] : af[sa][i];
             // weights as MFMA-A, activations as MFMA-B: D[n_local][m_local], as in the other two kernels
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[o - sa][j], af[sa][i], acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bb, aa, acc[i][j], 0, 0, 0);
+          }
   }
   const int64_t c_z = z0 * d.c_bs[0] + z1 * d.c_bs[1] + z2 * d.c_bs[2];
 #pragma unroll
@@ -899,6 +921,8 @@ extern "C" int rf_gemm(const rf_gemm_desc* dd, void* stream) {
   p.d.tile_cfg &= 0xff;
   rf_gemm_desc& d = p.d;
   if (d.M <= 0 || d.N <= 0 || d.K <= 0) return RF_EINVAL;
+  // a product scaled by zero is a fill, and the 16-bit kernels start their accumulators at bias / alpha: refused for every operand type
+  if (d.alpha == 0.f || !__builtin_isfinite(d.alpha)) return RF_EINVAL;
   if (d.rs && (d.ab_dtype != RF_H16 || d.tile_cfg != 0 || d.rs_rpb <= 0 || d.rs_cg <= 0 || d.rs_cg % 16 || d.rs_ncols <= 0 ||
                d.rs_ncols % d.rs_cg))
     return RF_EINVAL;

@@ -263,8 +263,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fast_kernel(const FastP p) {
 #pragma unroll
             for (int j = 0; j < WN; ++j) {
               const int nl = j * 16 + 4 * fq;
-              const float v0 = fmaxf(acc[i][j][0], lo), v1 = fmaxf(acc[i][j][1], lo);
-              const float v2 = fmaxf(acc[i][j][2], lo), v3 = fmaxf(acc[i][j][3], lo);
+              const float v0 = rf_max_nan(acc[i][j][0], lo), v1 = rf_max_nan(acc[i][j][1], lo);
+              const float v2 = rf_max_nan(acc[i][j][2], lo), v3 = rf_max_nan(acc[i][j][3], lo);
               if constexpr (OUT_F32) {
                 *(f32x4*)(lrow + nl * 4) = (f32x4){v0, v1, v2, v3};
               } else {

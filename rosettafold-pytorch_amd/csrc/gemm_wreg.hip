@@ -259,8 +259,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wreg_kernel(const WregP p) {
 #pragma unroll
       for (int j = 0; j < WCT; ++j) {
         uint2 o;
-        o.x = rf_pack2_h16(fmaxf(acc[i][j][0], lo), fmaxf(acc[i][j][1], lo));
-        o.y = rf_pack2_h16(fmaxf(acc[i][j][2], lo), fmaxf(acc[i][j][3], lo));
+        o.x = rf_pack2_h16(rf_max_nan(acc[i][j][0], lo), rf_max_nan(acc[i][j][1], lo));
+        o.y = rf_pack2_h16(rf_max_nan(acc[i][j][2], lo), rf_max_nan(acc[i][j][3], lo));
         *(uint2*)(strip + (i * 16 + fr) * PITCH + (j * 16 + 4 * fq) * 2) = o;
       }
     asm volatile("" ::: "memory");

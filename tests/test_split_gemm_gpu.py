@@ -17,6 +17,8 @@ import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib as L  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 
+import gemm_oracle as O  # noqa: E402
+
 DEV = "cuda"
 
 
@@ -42,42 +44,9 @@ def run(A, B, C, *a, exact=False, **kw):
     return C, fam
 
 
-def act_ref(x, act, nvalid, eps, mrow, ncol):
-    if act == L.ACT_RELU:
-        return x.clamp_min(0)
-    if act == L.ACT_ELU:
-        return F.elu(x)
-    if act == L.ACT_RELU_EPS:
-        valid = (mrow < -nvalid) if nvalid < 0 else (ncol < nvalid)
-        return torch.where(valid, x.clamp_min(0) + eps, torch.zeros_like(x))
-    return x
-
-
-def check_bound(got, Ae, Be, K, *, alpha=1.0, bias=None, bias_mode=None, res=None, act=L.ACT_NONE, nvalid=0, eps=0.0, c16=False):
-    """got [M, N] (gathered from C) against the float64 product of the effective operands Ae [.., M, K], Be [.., N, K]"""
-    Ad, Bd = Ae.double().cpu(), Be.double().cpu()
-    prod = alpha * (Ad @ Bd.transpose(-1, -2))
-    mag = abs(alpha) * (Ad.abs() @ Bd.abs().transpose(-1, -2))
-    M, N = prod.shape[-2:]
-    x = prod
-    if bias is not None:
-        b = bias.double().cpu()
-        x = x + (b[None, :] if bias_mode in (None, L.BIAS_COL) else b[:, None])
-    mrow = torch.arange(M)[:, None].expand(M, N)
-    ncol = torch.arange(N)[None, :].expand(M, N)
-    x = act_ref(x, act, nvalid, eps, mrow, ncol)
-    if res is not None:
-        x = x + res.double().cpu()
-    tol = (3 * 2.0 ** -16 + K * 2.0 ** -23) * mag + 2.0 ** -22 * (x.abs() + prod.abs()) + 1e-30
-    if act == L.ACT_ELU:
-        tol = tol + 4e-6 * x.abs()
-    if c16:  # rounding of the 16-bit output
-        tol = tol + 2.0 ** -8 * x.abs()
-    err = (got.double().cpu() - x).abs()
-    assert torch.isfinite(got).all()
-    worst = (err / tol).max().item()
-    assert worst <= 1.0, worst
-    return err
+def check_bound(got, Ae, Be, K, **kw):
+    """the shared per-element check (tests/gemm_oracle.py) with this kernel's operand-precision term"""
+    return O.check_bound(got, Ae, Be, K, op_term=3 * 2.0 ** -16 + K * 2.0 ** -23, **kw)
 
 
 # ------------------------------------------------------------------------------------------------ plain / batched
@@ -280,6 +249,8 @@ def test_rejects_what_the_exact_path_rejects():
         dict(act=L.ACT_BLOCK_LN32, block_ln=(g, b, 1e-5)),
         dict(ln=(lnout, g[:N], b[:N], 1e-5)),
         dict(rs=(rs, M, M, 16, 32, 1.0)),
+        dict(alpha=0.0), dict(alpha=-0.0), dict(alpha=math.inf), dict(alpha=math.nan),  # a product scaled by zero is a fill
+        dict(alpha=0.0, bias=torch.ones(N, device=DEV)),
     ]
     for kw in bad:
         r3 = _rc(lambda: ops.gemm(A, B, C, M, N, K, **kw))
