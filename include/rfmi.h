@@ -141,6 +141,25 @@ int rf_layernorm(const void* x, int x_dtype, int64_t x_ld, void* y, int y_dtype,
  * MsaUpdateWithPairLayer.pair2att of a block: Symmetrization + LayerNorm, rf.py:550-566). */
 int rf_sym_layernorm(const float* pair, void* y, int y_dtype, int B, int L, int D, float eps, void* stream);
 
+/* Introspection for tests and measurement tools, like rf_gemm_last_family: the kernel the calling thread's last successful
+ * rf_layernorm, rf_sym_layernorm, rf_instnorm_stats, rf_instnorm_apply, rf_axpby or rf_tile_1d_feats launched (-1 none; after
+ * a call that returned an error the value is unspecified).  Host-side only, no kernel sees it.
+ *    1 / 2    layernorm_rows8 (D = 288 / 384, fp32 in, 16-byte aligned, leading dimensions % 4 == 0)
+ *    3 / 4    the same kernels in rf_sym_layernorm
+ *    5 / 6    layernorm_vec with 2 / 4 chunks per lane (fp32 in, D % 4 == 0, 128 <= D <= 512 / 512 < D <= 1024, aligned)
+ *    7        layernorm_vec_bf16 (16-bit in, D % 8 == 0, 512 < D <= 1024, no activation, aligned)
+ *    8 / 9    layernorm_narrow (D = 32 / 64, fp32 in, aligned; takes groups and act)
+ *   10 .. 16  the generic one-wave-per-row kernel with 1, 2, 5, 6, 8, 16, 36 values per lane
+ *             (D <= 64, 128, 320, 384, 512, 1024, 2304): any dtype, alignment, leading dimension, groups
+ *   20 .. 26  the same seven instantiations in rf_sym_layernorm
+ *   30 / 31   rf_instnorm_stats: generic (128 pixels per block) / vectorised (16-bit in, C % 8 == 0, aligned; 512 pixels)
+ *   32        rf_instnorm_apply: generic (also the centre-only form)
+ *   33 / 34   rf_instnorm_apply vectorised, every thread keeping one channel chunk / re-deriving the chunk from the index
+ *             (the grid stride is no multiple of C / 8: ceil(HW * (C / 8) / 256) < (C / 8) / gcd(C / 8, 256), small pictures)
+ *   40 / 41   rf_axpby scalar / 4 elements per thread (n % 4 == 0, aligned)
+ *   42 / 43   rf_tile_1d_feats scalar / 4 channels per thread (P2, c0, feat_ld % 4 == 0, aligned) */
+int rf_rowops_last_route(void);
+
 /* Row softmax with strides: for r in [0,rows): y[r*y_rs + c] = softmax_c(scale * x[r*x_rs + c*x_cs]).
  * (rf.py:215,255,569,657,914). */
 int rf_softmax(const float* x, int64_t x_rs, int64_t x_cs, void* y, int y_dtype, int64_t y_rs, int64_t rows,

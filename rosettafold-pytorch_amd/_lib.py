@@ -121,6 +121,7 @@ PROTOTYPES = {
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],
+    "rf_rowops_last_route": [],
     "rf_version": [],
     "rf_h16_dtype": [],
 }

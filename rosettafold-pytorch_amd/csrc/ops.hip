@@ -9,6 +9,11 @@
 
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
+// rf_rowops_last_route (include/rfmi.h has the table of codes): set on the host by every dispatcher of this file that chooses
+// between kernels, read by the tests to assert the route a case took.  No kernel sees it.
+static thread_local int g_last_route = -1;
+extern "C" int rf_rowops_last_route(void) { return g_last_route; }
+
 __device__ __forceinline__ float block_sum(float v, float* red) {  // 256 threads
   v = wave_sum(v);
   const int w = threadIdx.x >> 6;
@@ -374,6 +379,7 @@ __global__ __launch_bounds__(256) void layernorm_narrow_kernel(const float* x, i
 template <bool SYM>
 static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, int64_t y_ld, int64_t rows, int D,
                      const float* g, const float* b, float eps, int L, int groups, int act, hipStream_t s) {
+  g_last_route = -1;
   if (rows <= 0 || D <= 0 || D > 2304) return RF_EINVAL;
   if (SYM && x_dt == RF_F32 && (D == 288 || D == 384) && x_ld % 4 == 0 && y_ld % 4 == 0 && ((uintptr_t)x % 16) == 0 &&
       ((uintptr_t)y % 16) == 0 && (!g || (((uintptr_t)g % 16) == 0 && ((uintptr_t)b % 16) == 0))) {
@@ -382,6 +388,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
       hipLaunchKernelGGL((layernorm_rows8_kernel<9, true>), dim3(gr), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, act, L);
     else
       hipLaunchKernelGGL((layernorm_rows8_kernel<12, true>), dim3(gr), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, act, L);
+    g_last_route = D == 288 ? 3 : 4;
     return rf_launch_status();
   }
   if (!SYM && x_dt == RF_F32 && groups <= 1 && D % 4 == 0 && D >= 128 && D <= 1024 && x_ld % 4 == 0 && y_ld % 4 == 0 &&
@@ -393,6 +400,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
         hipLaunchKernelGGL((layernorm_rows8_kernel<9>), dim3(gr), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, act);
       else
         hipLaunchKernelGGL((layernorm_rows8_kernel<12>), dim3(gr), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, act);
+      g_last_route = D == 288 ? 1 : 2;
       return rf_launch_status();
     }
     const unsigned gv = (unsigned)(rows < 8192 * LN_RPI ? cdiv(rows, 4 * LN_RPI) : 2048);
@@ -400,6 +408,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
       hipLaunchKernelGGL((layernorm_vec_kernel<2, LN_RPI>), dim3(gv), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, D, g, b, eps, act);
     else
       hipLaunchKernelGGL((layernorm_vec_kernel<4, 2>), dim3(gv), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, D, g, b, eps, act);
+    g_last_route = D <= 512 ? 5 : 6;
     return rf_launch_status();
   }
   const bool al16 = ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && (!g || (((uintptr_t)g % 16) == 0 && ((uintptr_t)b % 16) == 0));
@@ -407,6 +416,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
       y_ld % 8 == 0 && al16) {
     const unsigned gv = (unsigned)(rows < 8192 ? cdiv(rows, 4) : 2048);
     hipLaunchKernelGGL((layernorm_vec_bf16_kernel<2>), dim3(gv), dim3(256), 0, s, (const h16_t*)x, x_ld, y, y_dt, y_ld, rows, D, g, b, eps);
+    g_last_route = 7;
     return rf_launch_status();
   }
   if (!SYM && x_dt == RF_F32 && (D == 32 || D == 64) && x_ld % 4 == 0 && y_ld % 4 == 0 && al16) {
@@ -416,6 +426,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
       hipLaunchKernelGGL((layernorm_narrow_kernel<8>), dim3(gv), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, groups, act);
     else
       hipLaunchKernelGGL((layernorm_narrow_kernel<16>), dim3(gv), dim3(256), 0, s, (const float*)x, x_ld, y, y_dt, y_ld, rows, g, b, eps, groups, act);
+    g_last_route = D == 32 ? 8 : 9;
     return rf_launch_status();
   }
   const dim3 grid(cdiv(rows, 4)), blk(256);
@@ -428,6 +439,7 @@ static int launch_ln(const void* x, int x_dt, int64_t x_ld, void* y, int y_dt, i
   else if (D <= 1024) RF_LN(16);
   else RF_LN(36);
 #undef RF_LN
+  g_last_route = (SYM ? 20 : 10) + (D <= 64 ? 0 : D <= 128 ? 1 : D <= 320 ? 2 : D <= 384 ? 3 : D <= 512 ? 4 : D <= 1024 ? 5 : 6);
   return rf_launch_status();
 }
 
@@ -848,6 +860,7 @@ extern "C" int rf_instnorm_stats(const void* x, int x_dtype, void* sums, int B, 
                        (hipStream_t)stream, (const h16_t*)x, (double*)sums, partials, HW, C);
     hipLaunchKernelGGL(instnorm_finalize_kernel, dim3(cdiv(2 * C, 32), B), dim3(256), 0, (hipStream_t)stream, partials,
                        (double*)sums, (int)nblk, C);
+    g_last_route = 31;
     return rf_launch_status();
   }
   const unsigned nblk = cdiv(HW, IN_PIX);
@@ -855,6 +868,7 @@ extern "C" int rf_instnorm_stats(const void* x, int x_dtype, void* sums, int B, 
                      partials, HW, C);
   hipLaunchKernelGGL(instnorm_finalize_kernel, dim3(cdiv(2 * C, 32), B), dim3(256), 0, (hipStream_t)stream, partials,
                      (double*)sums, (int)nblk, C);
+  g_last_route = 30;
   return rf_launch_status();
 }
 
@@ -898,11 +912,13 @@ extern "C" int rf_instnorm_apply(const void* x, int x_dtype, const void* sums, c
     hipLaunchKernelGGL(instnorm_apply_vec_kernel, dim3(gx, B), dim3(256), 2 * C * sizeof(float), (hipStream_t)stream,
                        (const h16_t*)x, (const double*)sums, gamma, beta, eps, residual, act, y, y_dtype, y2, y2_dtype,
                        HW, C);
+    g_last_route = ((int64_t)gx * 256) % (C / 8) == 0 ? 33 : 34;  // the kernel's own test for its fixed-chunk index mode
     return rf_launch_status();
   }
   hipLaunchKernelGGL(instnorm_apply_kernel, dim3(min(cdiv(total, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, x,
                      x_dtype, (const double*)sums, gamma, beta, eps, residual, act, y, y_dtype, y2, y2_dtype, HW, C,
                      total);
+  g_last_route = 32;
   return rf_launch_status();
 }
 
@@ -1026,10 +1042,12 @@ extern "C" int rf_axpby(const void* x, int x_dtype, float a, const void* z, int 
     const int64_t n4 = n / 4;
     hipLaunchKernelGGL(axpby_vec_kernel, dim3(min(cdiv(n4, 512), 16384u)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, a, z,
                        z_dtype, b, y, y_dtype, n4);
+    g_last_route = 41;
     return rf_launch_status();
   }
   hipLaunchKernelGGL(axpby_kernel, dim3(min(cdiv(n, 256), 32768u)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, a, z,
                      z_dtype, b, y, y_dtype, n);
+  g_last_route = 40;
   return rf_launch_status();
 }
 
@@ -1167,11 +1185,13 @@ extern "C" int rf_tile_1d_feats(const float* msa1d, void* feat, int dtype, int64
     const int64_t total4 = (int64_t)B * L * L * (2 * P2 / 4);
     hipLaunchKernelGGL(tile_1d_vec_kernel, dim3(min(cdiv(total4, 256), 32768u)), dim3(256), 0, (hipStream_t)stream, msa1d, feat,
                        dtype, feat_ld, c0, L, P2, total4);
+    g_last_route = 43;
     return rf_launch_status();
   }
   const int64_t total = (int64_t)B * L * L * 2 * P2;
   hipLaunchKernelGGL(tile_1d_kernel, dim3(min(cdiv(total, 256), 32768u)), dim3(256), 0, (hipStream_t)stream, msa1d, feat,
                      dtype, feat_ld, c0, L, P2, total);
+  g_last_route = 42;
   return rf_launch_status();
 }
 
