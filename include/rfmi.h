@@ -587,6 +587,39 @@ int rf_relu_feature_bwd(const float* dphi, const float* z, void* dz, int dtype, 
 int rf_relu_dropout_bwd(const float* g, const float* hpre, void* dh, int dtype, float p, uint64_t seed, uint64_t offset, int64_t n,
                         void* stream);
 
+/* ---- backward pass of GraphTransformer and its block (csrc/backward.hip; model.py, rf.py:613-676) ---------------------------
+ * Backward of the attention core, one entry point for rf_graph_attention (mask NULL, p = 0), rf_graph_attention_dropout (mask
+ * NULL, p > 0) and rf_graph_attention_masked (mask, any p).  For a row (b, i) and head h, over the row's columns j (all of them,
+ * or the mask's), with keep_j the forward's keep / drop decision of element [b, h, i, j] of the [B, H, L, L] map (seed, offset):
+ *   s_j = scale q_i.(k_j + e_ij),  p = softmax(s),  pd_j = keep_j p_j / (1 - p_drop),  out_i = sum_j pd_j (v_j + e_ij)
+ *   dp_j = keep_j / (1 - p_drop) g_i.(v_j + e_ij),   ds_j = p_j (dp_j - sum_l p_l dp_l)
+ *   dq_i = scale sum_j ds_j (k_j + e_ij)             de_ij = pd_j g_i + scale ds_j q_i
+ *   dk_j = scale sum_i ds_ij q_i                     dv_j = sum_i pd_ij g_i
+ * q, k, v [B,L,H*d] and e [B,L,L,H*d] of dtype (the forward's operands: nothing of size L*L is saved, a block per row recomputes
+ * its logits and probabilities); g fp32 [B,L,H*d] = d out.  Outputs: dq, dk, dv fp32 [B,L,H*d]; de [B,L,L,H*d] of dtype;
+ * pd_map, ds_map fp32 [B,H,L,map_ld] (map_ld >= L).  The maps are fp32 in every build: dk and dv are sums of up to L of their
+ * entries, taken by a second kernel in ascending row order (no atomics: the same bits run to run), and so carry no 16-bit
+ * rounding; they are 2 / (H*d) of the bytes of e.  EVERY element of every output is written by the call -- nothing needs
+ * pre-zeroing: de and both maps are exactly 0 at a masked column, the maps also in the pad columns [L, map_ld).
+ * Under a mask the reads follow the row's degree (the forward's column compaction; k, v, e at a masked column are never read) and
+ * an all-ones mask gives the NULL-mask call's bits.  A row with no edge attends uniformly with the constant logit 0 (the forward's
+ * rule), which does not depend on q, k, e: dq_i = 0 and ds = 0 exactly, and de, dv receive the value path only, pd_j g_i with
+ * p_j = 1 / L (k, v, e of the row are not read).  That is the derivative of the function the forward computes; the reference's
+ * autograd would push a gradient through logits that its own -1e9 rounds away, and is not followed.
+ * Accumulation: the per-channel dot products in fp32; the softmax normaliser, sum_l p_l dp_l, the sums over columns (dq) and over
+ * rows (dk, dv) in fp64 (a row of two or three edges cancels in dp_j - sum_l p_l dp_l), each result rounded once to its type.
+ * e is read twice per row (the second time from L2), de written once.
+ * RF_EINVAL before any launch: a NULL tensor, p outside [0, 1), H*d > 256, d > 64 or not a power of two, map_ld < L, or
+ * (2*H*L + 2*L + 520) * 4 bytes of LDS > 64 KB (twice the forward's logits, plus the column list, its inverse and the partial
+ * dq: at H = 4, L <= 1586; at H = 8, L <= 881). */
+int rf_graph_attention_bwd(const void* q, const void* k, const void* v, const void* e, int dtype, const uint8_t* mask,
+                           const float* g, float* dq, float* dk, float* dv, void* de, float* pd_map, float* ds_map, int64_t map_ld,
+                           int B, int L, int H, int d, float scale, float p, uint64_t seed, uint64_t offset, void* stream);
+/* ELU backward from the activation's value, for y = x + ELU(z) (GraphTransformerBlock's tail, rf.py:674-676; x NULL: y = ELU(z)):
+ *   a = y[e] - x[e],  da[e] = g[e] * (a > 0 ? 1 : a + 1)       g, y, x fp32 [n]; da of dtype [n]
+ * (rf_instnorm_bwd applies the same factor inside its own passes; no stand-alone kernel had it). */
+int rf_elu_bwd(const float* g, const float* y, const float* x, void* da, int dtype, int64_t n, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

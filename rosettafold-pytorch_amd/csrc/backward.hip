@@ -1,5 +1,5 @@
-// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172), of the pair axial attention (end of
-// file) and of OuterProductMean (rf_layernorm_bwd_fused) on gfx950: the weight gradient of a
+// Backward-pass kernels of PredictionHead and its ResNets (resnet.py, rf.py:1130-1172), of the pair axial attention, of
+// OuterProductMean (rf_layernorm_bwd_fused) and of GraphTransformer and its block (end of file) on gfx950: the weight gradient of a
 // stride-1 "same" convolution (pixel contraction), InstanceNorm2d(affine) backward, LayerNorm backward, and the absolute
 // maximum the fp16 build scales its gradients by.  Input gradients of the convolutions / Linears run on rf_gemm (the forward's
 // implicit-GEMM engine with a repacked weight); these kernels are what the forward does not already have.
@@ -764,5 +764,271 @@ extern "C" int rf_relu_dropout_bwd(const float* g, const float* h, void* dh, int
   if (n == 0) return 0;
   hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3(min(cdiv(n, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, g, h, dh, dtype,
                      p > 0.f ? 1 : 0, dropout_threshold(p), 1.f / (1.f - p), seed, offset, n);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_graph_attention_bwd: backward of the GraphTransformer attention core (ops.hip: graph_attention_kernel and its masked /
+// dropout forms; rf.py:647-662).  Block per row (b, i) like the forward; the row's logits and probabilities are recomputed
+// (the forward saves nothing of size L * L).  With HD = H * d channels a block of 256 threads holds G = 256 / HD column
+// groups: thread (cg, c) owns channel c of the columns n = cg, cg + G, ...
+//   phase 0  the row's ascending column list idx[] and its inverse pos[] (the forward's compaction; NULL mask: the identity)
+//   phase 1  one pass over the row's e: s_n = scale q.(k_j + e_ij) and dpd_n = g.(v_j + e_ij), j = idx[n]
+//   phase 2  per head, one wave: p = softmax(s), dp = keep / (1 - p_drop) dpd, ds = p (dp - sum p dp), pd = keep / (1 - p_drop) p
+//   phase 3  the maps pd, ds [B, H, L, map_ld] fp32, zeros at masked columns and in the pad columns
+//   phase 4  second pass over the row's e (L2): dq_i = scale sum ds_n (k_j + e_ij), de_ij = pd g_i + scale ds q_i (0 at a
+//            masked column); the G partial dq are added in group order through LDS
+// A row with no edge: every logit is the constant 0, so ds = 0 and dq = 0 exactly, de_ij = pd_j g_i with p = 1 / L, and
+// k, v, e are not read.  graph_attention_bwd_cols_kernel then takes the sums across rows, dv_j = sum_i pd_ij g_i and
+// dk_j = scale sum_i ds_ij q_i, from the maps in row order: no atomics, the same bits run to run.
+// ================================================================================================
+#define GAB_JT 2  // columns per block of the cross-row kernel
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+static inline size_t gab_lds_bytes(int L, int H) { return ((size_t)2 * H * L + 2 * (size_t)L + 8 + 512) * sizeof(float); }
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void graph_attention_bwd_kernel(const void* q, const void* k, const void* v, const void* e, int dt,
+                                                                  const uint8_t* mask, const float* __restrict__ g,
+                                                                  float* __restrict__ dq, void* de, float* __restrict__ pd_map,
+                                                                  float* __restrict__ ds_map, int map_ld, int L, int H, int d,
+                                                                  float scale, unsigned thresh, float inv_keep, uint64_t seed,
+                                                                  uint64_t offset) {
+  extern __shared__ __attribute__((aligned(16))) float gab_sm[];
+  float* sp = gab_sm;                  // [H][L]: logits, then p, then pd   (row h holds deg entries)
+  float* sd = sp + (size_t)H * L;      // [H][L]: dpd, then dp, then ds
+  int* idx = (int*)(sd + (size_t)H * L);  // [L]: n -> column
+  int* pos = idx + L;                  // [L]: column -> n, -1 at a masked column
+  int* wcnt = pos + L;                 // [8]: edges found by each wave in a 256-column chunk
+  double* red = (double*)(wcnt + 8);   // [256]: the column groups' partial dq (8-byte aligned: every count above is even)
+  const int bi = blockIdx.x, b = bi / L, i = bi % L;
+  const int HD = H * d;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int G = 256 / HD;
+  const int cg = t / HD, c = t - cg * HD;
+  const bool act = cg < G;
+  const int h = c / d;  // (a head's d lanes are lane-aligned: HD and 64 are multiples of d)
+  // ---- phase 0
+  bool empty = false;  // block-uniform
+  int deg = L;
+  if (mask) {
+    const uint8_t* mrow = mask + (int64_t)bi * L;
+    int found = 0;
+    for (int c0 = 0; c0 < L; c0 += 256) {
+      const int j = c0 + t;
+      const bool on = j < L && mrow[j] != 0;
+      const unsigned long long bal = __ballot(on);
+      if (lane == 0) wcnt[wv] = __popcll(bal);
+      __syncthreads();
+      const int w0 = wcnt[0], w1 = wcnt[1], w2 = wcnt[2], w3 = wcnt[3];
+      const int before = found + (wv > 0 ? w0 : 0) + (wv > 1 ? w1 : 0) + (wv > 2 ? w2 : 0);
+      if (on) {
+        const int n = before + __popcll(bal & ((1ull << lane) - 1ull));
+        idx[n] = j;
+        pos[j] = n;
+      } else if (j < L) {
+        pos[j] = -1;
+      }
+      found += w0 + w1 + w2 + w3;
+      __syncthreads();  // wcnt is rewritten by the next chunk
+    }
+    empty = found == 0;
+    deg = empty ? L : found;
+  }
+  if (!mask || empty)
+    for (int n = t; n < L; n += 256) idx[n] = pos[n] = n;
+  __syncthreads();
+  // ---- phase 1
+  const float qv = act ? ld(q, dt, (int64_t)bi * HD + c) : 0.f;
+  const float gv = act ? g[(int64_t)bi * HD + c] : 0.f;
+  if (empty) {
+    for (int x = t; x < H * L; x += 256) sp[x] = sd[x] = 0.f;
+  } else {
+    for (int n0 = 0; n0 < deg; n0 += G) {  // (block-uniform trip count: the shuffles below run with every lane)
+      const int n = n0 + cg;
+      const bool ok = act && n < deg;
+      float s = 0.f, dp = 0.f;
+      if (ok) {
+        const int j = idx[n];
+        const float ev = ld(e, dt, ((int64_t)bi * L + j) * HD + c);
+        s = qv * (ld(k, dt, ((int64_t)b * L + j) * HD + c) + ev);
+        dp = gv * (ld(v, dt, ((int64_t)b * L + j) * HD + c) + ev);
+      }
+      for (int o = d >> 1; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o, 64);
+        dp += __shfl_xor(dp, o, 64);
+      }
+      if (ok && (c % d) == 0) {
+        sp[h * L + n] = s * scale;
+        sd[h * L + n] = dp;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- phase 2 (a lane reads and writes its own entries n = lane + 64 m only)
+  for (int hh = wv; hh < H; hh += 4) {
+    float* ps = sp + hh * L;
+    float* pg = sd + hh * L;
+    const int64_t el0 = (((int64_t)b * H + hh) * L + i) * L;  // element [b, hh, i, 0] of the forward's dropout map
+    float mx = -INFINITY;
+    for (int n = lane; n < deg; n += 64) mx = fmaxf(mx, ps[n]);
+    mx = wave_max(mx);
+    // The normaliser, sum p dp and dp - sum p dp are taken in fp64 (H * L scalars per row, against H * d * L channel terms): the
+    // probabilities then add up to one to fp64 accuracy, and the cancellation in ds, which grows like 1 / (1 - max p) in a row of
+    // two or three edges, loses nothing beyond the fp32 rounding of the logits themselves.
+    double s = 0.0;
+    for (int n = lane; n < deg; n += 64) {
+      const float ex = expf(ps[n] - mx);
+      ps[n] = ex;
+      s += (double)ex;
+    }
+    const double inv = 1.0 / wave_sum_f64(s);
+    double dot = 0.0;
+    for (int n = lane; n < deg; n += 64) {
+      float dp = pg[n];
+      if (DROP) dp = dropout_keep(seed, offset, el0 + idx[n], thresh) ? dp * inv_keep : 0.f;
+      dot = fma((double)ps[n] * inv, (double)dp, dot);
+      pg[n] = dp;
+    }
+    dot = wave_sum_f64(dot);
+    for (int n = lane; n < deg; n += 64) {
+      const double pr = (double)ps[n] * inv;
+      pg[n] = (float)(pr * ((double)pg[n] - dot));
+      float pd = (float)pr;
+      if (DROP) pd = dropout_keep(seed, offset, el0 + idx[n], thresh) ? pd * inv_keep : 0.f;
+      ps[n] = pd;
+    }
+  }
+  __syncthreads();
+  // ---- phase 3
+  for (int x = t; x < H * map_ld; x += 256) {
+    const int hh = x / map_ld, j = x - hh * map_ld;
+    const int n = j < L ? pos[j] : -1;
+    const int64_t o = (((int64_t)b * H + hh) * L + i) * map_ld + j;
+    pd_map[o] = n >= 0 ? sp[hh * L + n] : 0.f;
+    ds_map[o] = n >= 0 ? sd[hh * L + n] : 0.f;
+  }
+  // ---- phase 4
+  double a = 0.0;  // (fp64: one fused multiply-add per column next to three loads and a store)
+  for (int j0 = 0; j0 < L; j0 += G) {
+    const int j = j0 + cg;
+    if (act && j < L) {
+      const int n = pos[j];
+      float dev = 0.f;
+      if (n >= 0) {
+        const float dsv = sd[h * L + n];
+        dev = sp[h * L + n] * gv;
+        if (!empty) {
+          a = fma((double)dsv, (double)ld(k, dt, ((int64_t)b * L + j) * HD + c) + (double)ld(e, dt, ((int64_t)bi * L + j) * HD + c), a);
+          dev = fmaf(scale * dsv, qv, dev);
+        }
+      }
+      st(de, dt, ((int64_t)bi * L + j) * HD + c, dev);
+    }
+  }
+  red[t] = a;
+  __syncthreads();
+  if (t < HD) {
+    double s = 0.0;
+    for (int x = 0; x < G; ++x) s += red[x * HD + t];
+    dq[(int64_t)bi * HD + t] = (float)((double)scale * s);
+  }
+}
+
+// dv[b, j, c] = sum_i pd[b, h, i, j] g[b, i, c],  dk[b, j, c] = scale sum_i ds[b, h, i, j] q[b, i, c]:
+// block = GAB_JT columns of one sample; thread (ig, c) sums channel c of head h over the rows i = ig, ig + G, ... (ascending,
+// fp64: the kernel waits on its loads, not on its arithmetic), and the G = 256 / HD partial sums meet in LDS in group order
+__global__ __launch_bounds__(256) void graph_attention_bwd_cols_kernel(const float* __restrict__ pd_map, const float* __restrict__ ds_map,
+                                                                       int map_ld, const float* __restrict__ g, const void* q, int dt,
+                                                                       float* __restrict__ dk, float* __restrict__ dv, int L, int H,
+                                                                       int d, int tiles, float scale) {
+  __shared__ double red[2 * GAB_JT][256];
+  const int HD = H * d, t = threadIdx.x;
+  const int G = 256 / HD;
+  const int ig = t / HD, c = t - ig * HD;
+  const int b = blockIdx.x / tiles, j0 = (blockIdx.x % tiles) * GAB_JT;
+  const int h = c / d;
+  double av[GAB_JT], ak[GAB_JT];
+#pragma unroll
+  for (int u = 0; u < GAB_JT; ++u) av[u] = ak[u] = 0.0;
+  if (ig < G) {
+    const int64_t m0 = ((int64_t)b * H + h) * L * map_ld + j0;
+#pragma unroll 4
+    for (int i = ig; i < L; i += G) {
+      const float gv = g[((int64_t)b * L + i) * HD + c];
+      const float qv = ld(q, dt, ((int64_t)b * L + i) * HD + c);
+#pragma unroll
+      for (int u = 0; u < GAB_JT; ++u)
+        if (j0 + u < L) {
+          av[u] = fma((double)pd_map[m0 + (int64_t)i * map_ld + u], (double)gv, av[u]);
+          ak[u] = fma((double)ds_map[m0 + (int64_t)i * map_ld + u], (double)qv, ak[u]);
+        }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < GAB_JT; ++u) {
+    red[u][t] = av[u];
+    red[GAB_JT + u][t] = ak[u];
+  }
+  __syncthreads();
+  if (t < HD) {
+#pragma unroll
+    for (int u = 0; u < GAB_JT; ++u)
+      if (j0 + u < L) {
+        double sv = 0.0, sk = 0.0;
+        for (int x = 0; x < G; ++x) {
+          sv += red[u][x * HD + t];
+          sk += red[GAB_JT + u][x * HD + t];
+        }
+        dv[((int64_t)b * L + j0 + u) * HD + t] = (float)sv;
+        dk[((int64_t)b * L + j0 + u) * HD + t] = (float)((double)scale * sk);
+      }
+  }
+}
+
+// include/rfmi.h: rf_graph_attention_bwd
+extern "C" int rf_graph_attention_bwd(const void* q, const void* k, const void* v, const void* e, int dtype, const uint8_t* mask,
+                                      const float* g, float* dq, float* dk, float* dv, void* de, float* pd_map, float* ds_map,
+                                      int64_t map_ld, int B, int L, int H, int d, float scale, float p, uint64_t seed,
+                                      uint64_t offset, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!q || !k || !v || !e || !g || !dq || !dk || !dv || !de || !pd_map || !ds_map) return RF_EINVAL;
+  if (B <= 0 || L <= 0 || H <= 0 || d <= 0 || H * d > 256 || d > 64 || (d & (d - 1)) != 0) return RF_EINVAL;
+  if (!(p >= 0.f) || !(p < 1.f)) return RF_EINVAL;
+  if (map_ld < L || (int64_t)H * map_ld > 0x7fffffff || (int64_t)B * L > 0x7fffffff) return RF_EINVAL;
+  const size_t lds = gab_lds_bytes(L, H);
+  if (lds > 64 * 1024) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (p > 0.f)
+    hipLaunchKernelGGL(graph_attention_bwd_kernel<true>, dim3(B * L), dim3(256), lds, s, q, k, v, e, dtype, mask, g, dq, de, pd_map,
+                       ds_map, (int)map_ld, L, H, d, scale, dropout_threshold(p), 1.f / (1.f - p), seed, offset);
+  else
+    hipLaunchKernelGGL(graph_attention_bwd_kernel<false>, dim3(B * L), dim3(256), lds, s, q, k, v, e, dtype, mask, g, dq, de, pd_map,
+                       ds_map, (int)map_ld, L, H, d, scale, 0u, 1.f, (uint64_t)0, (uint64_t)0);
+  const int tiles = (int)cdiv(L, GAB_JT);
+  hipLaunchKernelGGL(graph_attention_bwd_cols_kernel, dim3((unsigned)B * tiles), dim3(256), 0, s, pd_map, ds_map,
+                     (int)map_ld, g, q, dtype, dk, dv, L, H, d, tiles, scale);
+  return rf_launch_status();
+}
+
+// rf_elu_bwd: da[e] = g[e] * (a > 0 ? 1 : a + 1), a = y[e] - x[e] the ELU's value (x NULL: a = y[e])
+__global__ __launch_bounds__(256) void elu_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
+                                                      const float* __restrict__ x, void* da, int da_dt, int64_t n) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+    const float a = x ? y[e] - x[e] : y[e];
+    st(da, da_dt, e, g[e] * (a > 0.f ? 1.f : a + 1.f));
+  }
+}
+
+extern "C" int rf_elu_bwd(const float* g, const float* y, const float* x, void* da, int dtype, int64_t n, void* stream) {
+  RF_CHECK_DT(dtype);
+  if (!g || !y || !da || n < 0) return RF_EINVAL;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(elu_bwd_kernel, dim3(min(cdiv(n, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, g, y, x, da, dtype, n);
   return rf_launch_status();
 }

@@ -1822,8 +1822,16 @@ class MsaUpdateWithPair(RFModule):
 # ================================================================================================
 # initial coordinates (graph transformer over the dense residue graph)
 # ================================================================================================
-class GraphTransformer(RFModule):
-    """rf.py:613-664."""
+class GraphTransformer(RecordingModule):
+    """rf.py:613-664.  enable_backward(): with grad mode on, forward(node_feat, edge_feat, edge_mask) records, and
+    loss.backward() fills the .grad of the five Linears and of node_feat and edge_feat where they require grad; edge_mask (None
+    included) carries no gradient.  The backward rebuilds q, k, v, e from the saved inputs with the forward's projections and runs
+    rf_graph_attention_bwd (include/rfmi.h); in train() mode it replays the forward's attention dropout.  A node with no edge
+    attends uniformly whatever its logits: its query and every key and edge logit receive no gradient from that row, only the
+    value path does -- the derivative of what the forward computes; the reference's autograd would differentiate logits that its
+    own -1e9 rounds away, and is not followed.  Channel counts (d_node_in, d_edge, n_heads * d_node_out) must be multiples of 8
+    while recording.  InitialCoordGenerationWithMsaAndPair calls run() without a tape: RoseTTAFold.forward never records here."""
+    _rf_n_inputs = 3   # node_feat, edge_feat, edge_mask (no gradient; may be None)
 
     def __init__(self, d_node_in, d_node_out, d_edge, n_heads, p_dropout=0.15):
         super().__init__()
@@ -1836,31 +1844,71 @@ class GraphTransformer(RFModule):
         self.n_heads, self.d_out = n_heads, d_node_out
         self.p_dropout = p_dropout   # rf.py:628,658: att_dropout on the attention probabilities
 
-    def run(self, node, edge_t, mask=None):
-        """node fp32 [B,L,dn]; edge_t T [B,L,L,de] -> fp32 [B,L,H*d]; mask: None (the dense graph) or what edge_mask_u8 returns"""
-        B, Lr, _ = node.shape
-        H, d = self.n_heads, self.d_out
-        nt = ops.cast(node, T())
+    def _projections(self, nt, edge_t):
+        """q, k, v [B,L,H*d] and e [B,L,L,H*d] in T: the forward's four launches (the backward rebuilds them with the same ones)"""
         q = ops.linear(nt, self.wt("q", self.node_to_q), _f(self.node_to_q.bias))
         k = ops.linear(nt, self.wt("k", self.node_to_k), _f(self.node_to_k.bias))
         v = ops.linear(nt, self.wt("v", self.node_to_v), _f(self.node_to_v.bias))
-        e = ops.linear(edge_t, self.wt("e", self.edge_emb), None)
+        return q, k, v, ops.linear(edge_t, self.wt("e", self.edge_emb), None)
+
+    def run(self, node, edge_t, mask=None, tape=None):
+        """node fp32 [B,L,dn]; edge_t T [B,L,L,de] -> fp32 [B,L,H*d]; mask: None (the dense graph) or what edge_mask_u8 returns.
+        tape: a dict that receives what _backward needs (the two inputs, the mask and the dropout record; same kernels, same
+        numbers)."""
+        B, Lr, _ = node.shape
+        H, d = self.n_heads, self.d_out
+        _check_backward_call(self, tape, None, node.shape[-1], edge_t.shape[-1], H * d)
+        nt = ops.cast(node, T())
+        q, k, v, e = self._projections(nt, edge_t)
         upd = torch.empty(B, Lr, H * d, device=node.device, dtype=F32)
+        drop = None
         if self.training and self.p_dropout and self.p_dropout > 0:
-            off = RT.train_offset
+            drop = (self.p_dropout, RT.train_seed, RT.train_offset)
             RT.train_offset += (B * H * Lr * Lr + 3) // 4
-            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, dropout=(self.p_dropout, RT.train_seed, off), mask=mask)
-        else:
-            ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, mask=mask)
+        ops.graph_attention(q, k, v, e, upd, B, Lr, H, d, self.scale, dropout=drop, mask=mask)
+        if tape is not None:
+            tape.update(node=node, edge_t=edge_t, mask=mask, drop=drop)
         return ops.linear(nt, self.wt("u", self.node_update), _f(self.node_update.bias), out_dtype=F32, residual=upd)
+
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, L, H*d] gradient of the output (read only).  Returns (fp32 d node [B,L,dn], fp32 d edge
+        [B,L,L,de], {param: grad}).  With q, k, v, e rebuilt from the saved inputs:
+            dq, dk, dv, de = rf_graph_attention_bwd(q, k, v, e, g)             (the mask and the dropout record replayed)
+            dW_x, db_x = dx^T node, sum dx   for x in q, k, v;   dW_u, db_u = g^T node, sum g;   dW_e = de^T edge     rf_conv_wgrad
+            d node = dq W_q + dk W_k + dv W_v + g W_u,   d edge = de W_e                                               rf_gemm"""
+        node, edge_t = tape["node"], tape["edge_t"]
+        B, Lr, _ = node.shape
+        H, d = self.n_heads, self.d_out
+        nt = ops.cast(node, T())
+        q, k, v, e = self._projections(nt, edge_t)
+        dq, dk, dv, de, _, _ = ops.graph_attention_bwd(q, k, v, e, g, B, Lr, H, d, self.scale, dropout=tape["drop"], mask=tape["mask"])
+        del q, k, v, e
+        grads, dnode = {}, None
+        for key, lin, dx in (("q", self.node_to_q, dq), ("k", self.node_to_k, dk), ("v", self.node_to_v, dv), ("u", self.node_update, g)):
+            dx_t = ops.cast(dx, T())
+            grads[lin.weight], grads[lin.bias] = ops.conv_wgrad(dx_t, nt, 1, bias=True)
+            dnode = ops.linear(dx_t, self.wt_input_grad(key, lin), None, out=dnode, out_dtype=F32, residual=dnode, exact=True)
+        grads[self.edge_emb.weight], _ = ops.conv_wgrad(de, edge_t, 1)
+        dedge = ops.linear(de, self.wt_input_grad("e", self.edge_emb), None, out_dtype=F32, exact=True)
+        return dnode, dedge, grads
+
+    def _record(self, node_feat, edge_feat, edge_mask, tape):
+        node = node_feat.float().contiguous()
+        return self.run(node, ops.cast(edge_feat.float().contiguous(), T()), edge_mask_u8(edge_mask, node), tape=tape)
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        dnode, dedge, grads = self._backward(tape, _scaled_copy(gs[0], s))
+        _unscale([dnode, dedge], s)
+        return (dnode, dedge, None), grads
 
     def forward(self, node_feat, edge_feat, edge_mask):
         """edge_mask [B, L, L] (bool, uint8 or floating point; an edge exists where it equals 1) or None.  A node with at least
         one edge attends to its edges only.  A node with no edge attends uniformly (1/L) to every node: what the reference's
         (1 - mask) * -1e9 gives whenever every scaled logit lies in (-32, 32) (the float32 spacing at 1e9 is 64); outside that
         bound the reference's empty row is rounding noise and is not followed."""
-        node = node_feat.float().contiguous()
-        return self.run(node, ops.cast(edge_feat.float().contiguous(), T()), edge_mask_u8(edge_mask, node))
+        if _recording(self):
+            return _RecordedFn.apply(self, node_feat, edge_feat, edge_mask, *self.parameters())
+        return self._record(node_feat, edge_feat, edge_mask, None)
 
 
 def edge_mask_u8(edge_mask, node):
@@ -1874,8 +1922,13 @@ def edge_mask_u8(edge_mask, node):
     return (edge_mask.to(node.device) == 1).to(torch.uint8).contiguous()
 
 
-class GraphTransformerBlock(RFModule):
-    """rf.py:667-676."""
+class GraphTransformerBlock(RecordingModule):
+    """rf.py:667-676.  enable_backward() (switches `attn` along): with grad mode on, forward(node_feat, edge_feat, edge_mask)
+    records, and loss.backward() fills the .grad of to_out's Linear, the LayerNorm, every Linear of `attn`, and of node_feat and
+    edge_feat where they require grad (see GraphTransformer for the mask, the node with no edge and the channel counts).
+    InitialCoordGenerationWithMsaAndPair calls run() without a tape: RoseTTAFold.forward never records here."""
+    _rf_n_inputs = 3
+    _rf_scales_own_grads = True   # the tail and the attention each at the fp16 mode's scale of their own gradient: _backward
 
     def __init__(self, d_node_in, d_node_out, d_edge, n_heads, p_dropout=0.15):
         super().__init__()
@@ -1883,14 +1936,59 @@ class GraphTransformerBlock(RFModule):
         self.ln = LayerNorm(d_node_out * n_heads)
         self.to_out = nn.Sequential(Linear(d_node_out * n_heads, d_node_in), nn.ELU())
 
-    def run(self, node, edge_t, mask=None):
-        h = ln(self.ln, self.attn.run(node, edge_t, edge_mask_u8(mask, node)))
-        return ops.linear(h, self.wt("o", self.to_out[0]), _f(self.to_out[0].bias), out_dtype=F32, act=L.ACT_ELU,
-                          residual=node)
+    def run(self, node, edge_t, mask=None, tape=None):
+        """tape: a dict that receives what _backward needs (the attention's own tape, its fp32 output, the normalised rows and
+        the block's output; same kernels, same numbers)."""
+        sub = {} if tape is not None else None
+        a = self.attn.run(node, edge_t, edge_mask_u8(mask, node), tape=sub)
+        h = ln(self.ln, a)
+        y = ops.linear(h, self.wt("o", self.to_out[0]), _f(self.to_out[0].bias), out_dtype=F32, act=L.ACT_ELU,
+                       residual=node)
+        if tape is not None:
+            tape.update(attn=sub, a=a, h=h, node=node, y=y.detach())   # (an alias without autograd history: no reference cycle)
+        return y
+
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, L, dn] gradient of the output (read only).  Returns (fp32 d node, fp32 d edge, {param: grad}).
+        y = node + ELU(h W_o + b_o), h = LayerNorm(attn):
+            da = g * ELU'(y - node)                                rf_elu_bwd (the derivative from the activation's value)
+            dW_o, db_o = da^T h, sum da;   dh = da W_o             rf_conv_wgrad, rf_gemm
+            d attn, dgamma, dbeta = LayerNorm backward             rf_layernorm_bwd on the saved attention output
+            d node, d edge = attn backward;   d node += g          the residual
+        In the fp16 mode each of the two stages runs on a copy of its incoming gradient at a power-of-two scale of its own."""
+        lin, lnm = self.to_out[0], self.ln
+        s = _grad_scale([g])
+        da = ops.elu_bwd(_scaled_copy(g, s), tape["y"], tape["node"], T())
+        dw, db = ops.conv_wgrad(da, tape["h"], 1, bias=True)
+        dh = ops.linear(da, self.wt_input_grad("o", lin), None, out_dtype=F32, exact=True)
+        da_, dgamma, dbeta = ops.layernorm_bwd(tape["a"], dh, _f(lnm.weight), eps=lnm.eps)
+        grads = {lin.weight: dw, lin.bias: db, lnm.weight: dgamma, lnm.bias: dbeta}
+        _unscale([da_] + list(grads.values()), s)
+        s = _grad_scale([da_])
+        if s != 1.0:
+            ops.axpby(da_, s, None, 0.0, da_)
+        dnode, dedge, sub = self.attn._backward(tape["attn"], da_)
+        _unscale([dnode, dedge] + list(sub.values()), s)
+        grads.update(sub)
+        ops.axpby(dnode, 1.0, g, 1.0, dnode)
+        return dnode, dedge, grads
+
+    def _backward_children(self):
+        return (self.attn,)
+
+    def _record(self, node_feat, edge_feat, edge_mask, tape):
+        return self.run(node_feat.float().contiguous(), ops.cast(edge_feat.float().contiguous(), T()), edge_mask, tape=tape)
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        g = gs[0] if gs[0].dtype == F32 and gs[0].is_contiguous() else gs[0].float().contiguous()
+        dnode, dedge, grads = self._backward(tape, g)
+        return (dnode, dedge, None), grads
 
     def forward(self, node_feat, edge_feat, edge_mask):
         """edge_mask: as in GraphTransformer.forward."""
-        return self.run(node_feat.float().contiguous(), ops.cast(edge_feat.float().contiguous(), T()), edge_mask)
+        if _recording(self):
+            return _RecordedFn.apply(self, node_feat, edge_feat, edge_mask, *self.parameters())
+        return self._record(node_feat, edge_feat, edge_mask, None)
 
 
 def _node_input(mod, msa, seq_onehot, out_dtype=None):

@@ -621,6 +621,47 @@ def relu_dropout_bwd(g, hpre, out_dtype, drop=None):
     return dh
 
 
+def graph_attention_bwd(q, k, v, e, g, B, L_, H, d, scale, dropout=None, mask=None):
+    """Backward of graph_attention in any of its forms (rf_graph_attention_bwd): q, k, v [B, L, H*d] and e [B, L, L, H*d] the
+    forward's operands (contiguous, one dtype), g contiguous fp32 [B, L, H*d] = d out; dropout = the forward's (p, seed, offset)
+    or None; mask = the forward's uint8 [B, L, L] or None.  Returns (dq, dk, dv fp32 [B, L, H*d], de [B, L, L, H*d] in the
+    operands' dtype, pd, ds fp32 [B, H, L, L]): pd the probabilities after dropout, ds the logits' gradient, both exactly 0 at a
+    masked column, like de.  A row with no edge: dq = 0, ds = 0, de = pd g with p = 1 / L -- the derivative of the uniform
+    attention the forward computes there (the reference's autograd differentiates logits its own -1e9 rounds away)."""
+    _need_cuda(q, k, v, e, g, mask)
+    HD = H * d
+    for t_ in (q, k, v):
+        if t_.dtype != e.dtype or tuple(t_.shape) != (B, L_, HD) or not t_.is_contiguous():
+            raise ValueError(f"graph_attention_bwd: contiguous q, k, v [{B}, {L_}, {HD}] of e's dtype")
+    if tuple(e.shape) != (B, L_, L_, HD) or not e.is_contiguous():
+        raise ValueError(f"graph_attention_bwd: contiguous e [{B}, {L_}, {L_}, {HD}]")
+    if g.dtype != F32 or tuple(g.shape) != (B, L_, HD) or not g.is_contiguous():
+        raise ValueError(f"graph_attention_bwd: contiguous fp32 g [{B}, {L_}, {HD}]")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (B, L_, L_) or not mask.is_contiguous()):
+        raise ValueError(f"mask must be a contiguous uint8 [{B}, {L_}, {L_}] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    pd_, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+    dev = q.device
+    dq, dk, dv = (torch.empty(B, L_, HD, device=dev, dtype=F32) for _ in range(3))
+    de = torch.empty(B, L_, L_, HD, device=dev, dtype=e.dtype)
+    pmap, smap = (torch.empty(B, H, L_, L_, device=dev, dtype=F32) for _ in range(2))
+    check(lib.rf_graph_attention_bwd(ptr(q), ptr(k), ptr(v), ptr(e), dcode(e.dtype), ptr(mask), ptr(g), ptr(dq), ptr(dk), ptr(dv),
+                                     ptr(de), ptr(pmap), ptr(smap), L_, B, L_, H, d, scale, float(pd_), int(seed), int(off),
+                                     stream()), "rf_graph_attention_bwd")
+    return dq, dk, dv, de, pmap, smap
+
+
+def elu_bwd(g, y, x, out_dtype):
+    """ELU backward from the activation's value (rf_elu_bwd): g, y (and x, or None) contiguous fp32 of one shape, y = x + ELU(z).
+    Returns g * (a > 0 ? 1 : a + 1) with a = y - x, as out_dtype."""
+    _need_cuda(g, y, x)
+    for t_ in (g, y, x):
+        if t_ is not None and (t_.dtype != F32 or t_.shape != g.shape or not t_.is_contiguous()):
+            raise ValueError("elu_bwd: contiguous fp32 g, y and x of one shape")
+    da = torch.empty(g.shape, device=g.device, dtype=out_dtype)
+    check(lib.rf_elu_bwd(ptr(g), ptr(y), ptr(x), ptr(da), dcode(out_dtype), g.numel(), stream()), "rf_elu_bwd")
+    return da
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through
