@@ -240,6 +240,21 @@ int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int6
                          int64_t sym_ld, void* out, const int64_t o_strides[4], int B, int H, int N, int L, int d_head,
                          float* partial_ws, int64_t partial_ws_elems, void* stream);
 
+/* Introspection for tests and measurement tools, like rf_rowops_last_route: the kernel instantiation the calling thread's last
+ * successful rf_favor_attention, rf_tied_logits_softmax, rf_tied_logits(_ld), rf_tied_av(_ld), rf_tied_attention(_ld) or
+ * rf_poswise_collapsed launched (-1 none; after a call that returned an error the value is unspecified).  Host-side only, no
+ * kernel sees it.  rf_tied_attention(_ld) launches two kernels and leaves 1000 * (logits code) + (attention.V code).
+ *   100 .. 111  rf_favor_attention, 4-wave kernel (RF_FAVOR4, and always the softmax features in the 256-row tile):
+ *               100 + 4 * (tile: 0 = 64, 1 = 128, 2 = 256 rows) + 2 * (softmax features) + (tail: seq_len does not fill the tiles)
+ *   112 .. 121  rf_favor_attention, 8-wave kernel: 112 + the same three terms (the softmax features end at the 128-row tile)
+ *   200 .. 215  tied logits, one-pass kernel: 200 + 4 * (tile / 64 - 1) + 2 * (w != NULL) + (tail: L < tile or att_ld != L)
+ *   220 / 221   tied logits, contraction-split, L = 256: w == NULL / w != NULL
+ *   222 / 224 / 226   tied logits, contraction-split, L = 512 / 768 / 1024 (w == NULL)
+ *   240 .. 247  attention . V: 240 + 2 * (tile / 64 - 1) + (tail)
+ *   261 .. 268  rf_poswise_collapsed: 260 + N / 16
+ *   272 / 276   rf_poswise_collapsed, N = 192 / 256 */
+int rf_attn_last_route(void);
+
 /* Feed-forward block with its residual in ONE launch (FeedForward, rf.py:270-281, inside the residual wrappers of the
  * encoder / axial layers rf.py:284-354, 483-560):
  *   out[m,:] = residual[m,:] + W2 relu(W1 x[m,:] + b1) + b2          (fp32; out may alias residual: in place)
@@ -407,7 +422,11 @@ int rf_favor_softmax_features(const void* dash, const void* x, const int64_t xs[
  * key maximum spans the whole sequence; longer: RF_EINVAL, use the unfused chain of rf_gemm + rf_favor_softmax_features +
  * rf_linattn_normalize).  Rows s >= seq_len of an item are neither read nor written: they may belong to another sequence
  * or lie outside the buffers.  softmax_kernel != 0: exp features with the library's
- * stabilisers (per-row max for q, per-(b,o,h) max for k) and eps; else relu(x)+eps. */
+ * stabilisers (per-row max for q, per-(b,o,h) max for k) and eps; else relu(x)+eps.
+ * With softmax_kernel != 0 the kernel exponentiates with exp2, so pc must be dim_head^-1/4 * log2(e) * P (with
+ * softmax_kernel == 0: dim_head^-1/4 * P), and the features are
+ *     phi(x) = exp2(x Pc^T - |x|^2 dim_head^-1/2 log2(e) / 2 - max) + eps,
+ * the maximum of x Pc^T over the 266 features per row for q, over all rows s < seq_len and the 266 features per item for k. */
 int rf_favor_attention(const void* qkv, const void* pc, void* out, const int64_t x_strides[4],
                        const int64_t o_strides[3], int q_off, int k_off, int v_off, int n_b, int n_o, int n_h,
                        int seq_len, int dim_head, int n_features, int softmax_kernel, float eps, void* stream);

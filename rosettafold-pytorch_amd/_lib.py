@@ -124,6 +124,7 @@ PROTOTYPES = {
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],
     "rf_rowops_last_route": [],
+    "rf_attn_last_route": [],
     "rf_version": [],
     "rf_h16_dtype": [],
 }

@@ -971,6 +971,10 @@ extern "C" int rf_favor_phase_cycles(unsigned long long* out7, int reset) {
   return 0;
 }
 
+// rf_attn_last_route (include/rfmi.h has the table of codes; the variable lives in tied.hip): set on the host by the launcher
+// that chose the instantiation, no kernel sees it.
+extern thread_local int g_attn_route;
+
 template <int LS, bool SM, bool TAIL>
 static int launch_favor(const FavorAttnP& p, hipStream_t s) {
   const size_t lds = (size_t)FV_MPAD * 128 + 2 * (size_t)LS * 128 + (size_t)FV_DROWS * FV_CTX_LD + LS * 4 + 64;
@@ -981,6 +985,7 @@ static int launch_favor(const FavorAttnP& p, hipStream_t s) {
   // registers); at 256 rows the softmax variant does not fit and stays on the 4-wave kernel.  RF_FAVOR4 forces the 4-wave kernel.
   static const bool force4 = getenv("RF_FAVOR4") != nullptr;
   constexpr bool only4 = SM && LS > 128;  // (the 8-wave form of this variant does not fit 256 registers: never instantiated)
+  g_attn_route = 100 + (only4 || force4 ? 0 : 12) + (LS == 64 ? 0 : LS == 128 ? 4 : 8) + (SM ? 2 : 0) + (TAIL ? 1 : 0);
   if (only4 || force4) {
     auto k = favor_attention_kernel<LS, SM, TAIL>;
     if (const int e = rf_enable_big_lds<favor_attention_kernel<LS, SM, TAIL>>()) return e;

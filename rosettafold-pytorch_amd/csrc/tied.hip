@@ -20,6 +20,11 @@
 
 static __device__ __attribute__((aligned(16))) unsigned int g_tied_zero16[4];
 
+// rf_attn_last_route (include/rfmi.h has the table of codes): set on the host by every launcher of this file and of favor.hip
+// that chooses an instantiation, so that a test can assert which kernel it measured.  No kernel sees it.
+thread_local int g_attn_route = -1;
+extern "C" int rf_attn_last_route(void) { return g_attn_route; }
+
 union TFrag {
   h16x8 v;
   unsigned u[4];
@@ -419,6 +424,7 @@ static int launch_tied(const TiedP& p, hipStream_t s) {
   if (const int e = rf_enable_big_lds<tied_logits_kernel<L, SCALE, TAIL>>()) return e;
   const int64_t grid = (int64_t)p.B * p.H * (TAIL ? (p.len + 63) / 64 : L / 64);  // (query tiles wholly past len are not launched)
   if (grid > 0x7fffffffLL) return RF_EINVAL;
+  g_attn_route = 200 + 4 * (L / 64 - 1) + (SCALE ? 2 : 0) + (TAIL ? 1 : 0);
   hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, s, p);
   return rf_launch_status();
 }
@@ -446,6 +452,7 @@ static int tied_logits_split(const TiedP& p0, int L, float* ws, int64_t ws_elems
   const int64_t grid64 = (int64_t)p.B * p.H * nrb * nkb * nsplit;
   if (grid64 > 0x7fffffffLL) return RF_EINVAL;
   const unsigned grid = (unsigned)grid64;
+  g_attn_route = 220 + 2 * (nkb - 1) + (p.w ? 1 : 0);
   if (p.w) {
     if (const int e = rf_enable_big_lds<tied_logits_split_kernel<true>>()) return e;
     hipLaunchKernelGGL(tied_logits_split_kernel<true>, dim3(grid), dim3(512), lds, s, p);
@@ -704,6 +711,7 @@ static int launch_tied_av(TiedAvP& p, hipStream_t s) {
   p.units_per_wg = (p.nunits + grid - 1) / grid;
   grid = (p.nunits + p.units_per_wg - 1) / p.units_per_wg;
   if (const int e = rf_enable_big_lds<tied_av_kernel<L, TAIL>>()) return e;
+  g_attn_route = 240 + 2 * (L / 64 - 1) + (TAIL ? 1 : 0);
   hipLaunchKernelGGL((tied_av_kernel<L, TAIL>), dim3((unsigned)grid), dim3(256), 4 * L * 64 + 1024, s, p);
   return rf_launch_status();
 }
@@ -807,7 +815,10 @@ extern "C" int rf_tied_attention_ld(const void* q, const void* k, const void* v,
   const int rc = rf_tied_logits_ld(q, k, qk_strides, w, w_strides, qscale, att, att_ld, att_sym, sym_ld, B, H, N, L, d_head,
                                    partial_ws, partial_ws_elems, stream);
   if (rc != 0) return rc;
-  return rf_tied_av_ld(att, att_ld, v, v_strides, out, o_strides, B, H, N, L, d_head, stream);
+  const int logits_route = g_attn_route;
+  const int rc2 = rf_tied_av_ld(att, att_ld, v, v_strides, out, o_strides, B, H, N, L, d_head, stream);
+  g_attn_route = 1000 * logits_route + g_attn_route;  // both kernels of the composition: 1000 * logits code + attention.V code
+  return rc2;
 }
 
 extern "C" int rf_tied_attention(const void* q, const void* k, const void* v, const int64_t qk_strides[4],
@@ -886,6 +897,7 @@ extern "C" int rf_poswise_collapsed(const void* xn, const void* u, float* w, int
   hipStream_t s = (hipStream_t)stream;
 #define RF_PW(NT_)                                                                                                           \
   if (N == 16 * NT_) {                                                                                                       \
+    g_attn_route = 260 + NT_;                                                                                                \
     hipLaunchKernelGGL(poswise_mfma_kernel<NT_>, dim3(grid), dim3(256), 0, s, (const h16_t*)xn, (const h16_t*)u, w, B, N, \
                        L, D, H, scale);                                                                                      \
     return rf_launch_status();                                                                                               \

@@ -36,7 +36,8 @@ def test_every_declared_symbol_is_exported(lib):
 def test_ctypes_table_matches_header():
     from rosettafold_pytorch_amd import _lib
     assert sorted(set(_lib.PROTOTYPES) | {"rf_build_info"}) == declared()
-    assert _lib.lib.rf_version() >= 1
+    assert _lib.lib.rf_version() >= 14  # 14: rf_attn_last_route
+    assert all(isinstance(h.rf_attn_last_route(), int) for h in _lib.LIBS.values())
     # the two builds say which 16-bit dtype code they take, and the selector routes to the matching one
     assert _lib.LIBS[_lib.RF_BF16].rf_h16_dtype() == _lib.RF_BF16 and _lib.LIBS[_lib.RF_F16].rf_h16_dtype() == _lib.RF_F16
     import torch
