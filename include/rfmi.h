@@ -639,6 +639,36 @@ int rf_graph_attention_bwd(const void* q, const void* k, const void* v, const vo
  * (rf_instnorm_bwd applies the same factor inside its own passes; no stand-alone kernel had it). */
 int rf_elu_bwd(const float* g, const float* y, const float* x, void* da, int dtype, int64_t n, void* stream);
 
+/* ---- backward pass of PositionWiseWeightFactor and of the structure track's node input (csrc/backward.hip; model.py
+ * PositionWiseWeightFactor, _node_input; rf.py:205-217, 715-724) --------------------------------------------------------------
+ * Backward of rf_poswise, with rf_poswise's addressing (rf_version >= 15): q0 [B,L,H*dlen] of q0_dtype (q0_ld between rows), k
+ * rows [B,N,L,*] of dtype (k_ld between rows, head h at column k_col0 + h*k_hstride, dlen columns).  Per (b, l, h), over the MSA
+ * depth n, with keep_n the keep / drop decision of element [b, n, h, l] of rf_dropout's mask (p, seed, offset) over the
+ * contiguous [B,N,H,L] weights (p = 0: no dropout):
+ *   w_n = softmax_n(scale q0_h . k_{n,h}),   wd_n = w_n keep_n / (1 - p)
+ *   dw_n = keep_n / (1 - p) (dw[b,n,h,l] + k_n . ds[b,l,:])        dw fp32 [B,N,H,L] = the gradient of the (dropped) weights
+ *   dlogit_n = w_n (dw_n - sum_m w_m dw_m)
+ *   dq0[b,l,h,:]   = scale sum_n dlogit_n k_{n,h,:}                 fp32 [B,L,H*dlen], contiguous
+ *   dk[b,n,l,h,:]  = scale dlogit_n q0_h + wd_n ds[b,l,:]           of dk_dtype (fp32 or the 16-bit type): rows [B,N,L,*] of
+ *                                                                   dk_ld, head h at column dk_col0 + h*dk_hstride
+ * ds fp32 [B,L,*] (ds_ld between rows) is the gradient of s[b,l,:] = sum_n wd_n k_n, rf_weighted_msa_sum fused behind the
+ * weights: the collapsed one-head form only (H == 1, dlen = the whole row; k_hstride and dk_hstride are not used).  dw or ds
+ * may be NULL (not both); with ds == NULL the second term of dk is absent.  The collapsed form with H > 1 is NOT supported with
+ * ds (RF_EINVAL: dk would be a sum over heads); without ds any H, k_hstride == 0 included, is taken as the addressing says.
+ * Nothing of the forward is saved but its inputs: a block per (b, l) recomputes the logits and w.  to_k's bias is constant over
+ * n, drops out of the softmax, has gradient zero and never reaches this kernel.
+ * k is read twice (the second time from L2), dk written once; 16-byte accesses when dlen % 8 == 0, every leading dimension,
+ * column offset and head stride is a multiple of 8 and the tensors are 16-byte aligned, a scalar path otherwise.
+ * Accumulation: the dot products in fp32; the softmax normaliser, sum_m w_m dw_m (N = 2 or 3 cancels in dw_n - sum) and the sums
+ * over n into dq0 in fp64; each result rounded once.  No atomics: the same bits run to run.  N == 1: dlogit = 0 and dq0 = 0
+ * exactly, dk = wd ds alone.  EVERY element of dq0 and of the addressed columns of dk is written by the call.
+ * RF_EINVAL before any launch: q0, k, dq0 or dk NULL, dw and ds both NULL, ds with H != 1, p outside [0, 1), or
+ * (2*N*H + 512) * 4 bytes of LDS > 64 KB (logits and dlogit, plus the reduction scratch of dq0). */
+int rf_poswise_bwd(const void* q0, int q0_dtype, int64_t q0_ld, const void* k, int dtype, int64_t k_ld, int k_col0, int k_hstride,
+                   int dlen, const float* dw, const float* ds, int64_t ds_ld, float* dq0, void* dk, int dk_dtype, int64_t dk_ld,
+                   int dk_col0, int dk_hstride, int B, int N, int L, int H, float scale, float p, uint64_t seed, uint64_t offset,
+                   void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

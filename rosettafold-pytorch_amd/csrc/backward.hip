@@ -1032,3 +1032,223 @@ extern "C" int rf_elu_bwd(const float* g, const float* y, const float* x, void* 
   hipLaunchKernelGGL(elu_bwd_kernel, dim3(min(cdiv(n, 256), 16384u)), dim3(256), 0, (hipStream_t)stream, g, y, x, da, dtype, n);
   return rf_launch_status();
 }
+
+// ================================================================================================
+// rf_poswise_bwd: backward of PositionWiseWeightFactor's core (ops.hip: poswise_kernel; rf.py:205-217), optionally with the
+// weighted sum over the MSA depth (weighted_msa_sum_kernel; rf.py:723) fused behind it.  Block per (b, l) like the forward; the
+// logits and the weights are recomputed from q0 and k.  A chunk is CH = 8 channels (16-byte accesses) or one channel (the
+// scalar path: any dlen, any alignment; the host chooses).
+//   phase 1  one pass over the block's k rows: logit_{n,h} = scale q0_h . k_{n,h} and, fused form, z_n = k_n . ds.  A group of
+//            G lanes (a power of two, the chunks of one head) owns one (n, h) and meets in a shuffle reduction
+//   phase 2  per head, one wave: w = softmax(logit), dw = keep / (1 - p) (dw + z), dlogit = w (dw - sum w dw),
+//            wd = keep / (1 - p) w
+//   phase 3  second pass over k (L2): thread (rg, cc) owns chunk cc of the H * dlen / CH column chunks and walks the rows
+//            n = rg, rg + R, ...: dk_n = scale dlogit_n q0 + wd_n ds, and its partial dq0 = sum_n dlogit_n k_n; the R partial
+//            sums are added in group order through LDS
+// N == 1: w = 1 and dw - sum w dw = 0 exactly, so dlogit = 0, dq0 = 0, dk = wd ds.
+// ================================================================================================
+template <bool VEC>
+__device__ __forceinline__ void pwb_load(const void* p, int dt, int64_t o, float (&v)[VEC ? 8 : 1]) {
+  if constexpr (VEC) {
+    if (dt == RF_F32) {
+      const float4 a = *(const float4*)((const float*)p + o), b = *(const float4*)((const float*)p + o + 4);
+      v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+      v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+      const h16x8 a = *(const h16x8*)((const h16_t*)p + o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = h2f((h16_t)a[e]);
+    }
+  } else {
+    v[0] = ld(p, dt, o);
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void pwb_store(void* p, int dt, int64_t o, const float (&v)[VEC ? 8 : 1]) {
+  if constexpr (VEC) {
+    if (dt == RF_F32) {
+      *(float4*)((float*)p + o) = make_float4(v[0], v[1], v[2], v[3]);
+      *(float4*)((float*)p + o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+      h16x8 a;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = (short)f2h(v[e]);
+      *(h16x8*)((h16_t*)p + o) = a;
+    }
+  } else {
+    st(p, dt, o, v[0]);
+  }
+}
+
+static inline size_t pwb_lds_bytes(int N, int H) { return ((size_t)2 * N * H + 512) * sizeof(float); }
+
+template <bool VEC, bool DROP>
+__global__ __launch_bounds__(256) void poswise_bwd_kernel(const void* q0, int q0_dt, int64_t q0_ld, const void* k, int dt,
+                                                          int64_t k_ld, int k_col0, int k_hs, int dlen,
+                                                          const float* __restrict__ dw, const float* __restrict__ ds, int64_t ds_ld,
+                                                          float* __restrict__ dq0, void* dk, int dk_dt, int64_t dk_ld, int dk_col0,
+                                                          int dk_hs, int N, int L, int H, float scale, unsigned thresh,
+                                                          float inv_keep, uint64_t seed, uint64_t offset) {
+  constexpr int CH = VEC ? 8 : 1;
+  extern __shared__ __attribute__((aligned(16))) float pwb_sm[];
+  double* red = (double*)pwb_sm;         // [256]: the row groups' partial dq0 of one channel
+  float* sl = pwb_sm + 512;              // [H][N]: logits, then exp, then wd
+  float* sd = sl + (size_t)N * H;        // [H][N]: z, then dw, then dlogit
+  const int bl = blockIdx.x, b = bl / L, l = bl - b * L;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int NH = N * H;
+  const int nch = (dlen + CH - 1) / CH;  // chunks of one head
+  const int64_t qrow = (int64_t)bl * q0_ld, dsrow = (int64_t)bl * ds_ld;
+  // ---- phase 1
+  {
+    int G = 1;
+    while (G < nch && G < 64) G <<= 1;
+    const int ipp = 256 / G, gi = t / G, gj = t & (G - 1);
+    for (int i0 = 0; i0 < NH; i0 += ipp) {  // (block-uniform trip count: the shuffles below run with every lane)
+      const int item = i0 + gi;
+      const bool ok = item < NH;
+      const int n = item / H, h = item - n * H;
+      float a = 0.f, z = 0.f;
+      if (ok) {
+        const int64_t kb = (((int64_t)b * N + n) * L + l) * k_ld + k_col0 + (int64_t)h * k_hs;
+        const int64_t qb = qrow + (int64_t)h * dlen;
+        for (int c = gj; c < nch; c += G) {
+          float kv[CH], qv[CH];
+          pwb_load<VEC>(k, dt, kb + (int64_t)c * CH, kv);
+          pwb_load<VEC>(q0, q0_dt, qb + (int64_t)c * CH, qv);
+#pragma unroll
+          for (int e = 0; e < CH; ++e) a = fmaf(qv[e], kv[e], a);
+          if (ds) {
+            float dv[CH];
+            pwb_load<VEC>(ds, RF_F32, dsrow + (int64_t)c * CH, dv);
+#pragma unroll
+            for (int e = 0; e < CH; ++e) z = fmaf(dv[e], kv[e], z);
+          }
+        }
+      }
+      for (int o = G >> 1; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        z += __shfl_xor(z, o, 64);
+      }
+      if (ok && gj == 0) {
+        sl[h * N + n] = a * scale;
+        sd[h * N + n] = z;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- phase 2 (a lane reads and writes its own entries n = lane + 64 m only)
+  for (int hh = wv; hh < H; hh += 4) {
+    float* ps = sl + hh * N;
+    float* pg = sd + hh * N;
+    float mx = -INFINITY;
+    for (int n = lane; n < N; n += 64) mx = fmaxf(mx, ps[n]);
+    mx = wave_max(mx);
+    double s = 0.0;
+    for (int n = lane; n < N; n += 64) {
+      const float ex = expf(ps[n] - mx);
+      ps[n] = ex;
+      s += (double)ex;
+    }
+    const double inv = 1.0 / wave_sum_f64(s);
+    double dot = 0.0;
+    for (int n = lane; n < N; n += 64) {
+      const int64_t el = (((int64_t)b * N + n) * H + hh) * L + l;  // element [b, n, hh, l] of the weights and their dropout mask
+      float g = pg[n] + (dw ? dw[el] : 0.f);
+      if (DROP) g = dropout_keep(seed, offset, el, thresh) ? g * inv_keep : 0.f;
+      dot = fma((double)ps[n] * inv, (double)g, dot);
+      pg[n] = g;
+    }
+    dot = wave_sum_f64(dot);
+    for (int n = lane; n < N; n += 64) {
+      const double pr = (double)ps[n] * inv;
+      pg[n] = (float)(pr * ((double)pg[n] - dot));
+      float wd = (float)pr;
+      if (DROP) wd = dropout_keep(seed, offset, (((int64_t)b * N + n) * H + hh) * L + l, thresh) ? wd * inv_keep : 0.f;
+      ps[n] = wd;
+    }
+  }
+  __syncthreads();
+  // ---- phase 3
+  const int CC = H * nch;
+  const int CCt = CC < 256 ? CC : 256;
+  const int R = 256 / CCt;
+  const int rg = t / CCt, cl = t - rg * CCt;
+  for (int cc0 = 0; cc0 < CC; cc0 += CCt) {  // (block-uniform trip count: the barriers below are met by every thread)
+    const int cc = cc0 + cl;
+    const bool ok = rg < R && cc < CC;
+    const int h = ok ? cc / nch : 0, c = ok ? cc - h * nch : 0;
+    double acc[CH];
+#pragma unroll
+    for (int e = 0; e < CH; ++e) acc[e] = 0.0;
+    if (ok) {
+      float qv[CH], dv[CH];
+      pwb_load<VEC>(q0, q0_dt, qrow + (int64_t)h * dlen + (int64_t)c * CH, qv);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) dv[e] = 0.f;
+      if (ds) pwb_load<VEC>(ds, RF_F32, dsrow + (int64_t)c * CH, dv);
+      for (int n = rg; n < N; n += R) {
+        const int64_t row = ((int64_t)b * N + n) * L + l;
+        float kv[CH], ov[CH];
+        pwb_load<VEC>(k, dt, row * k_ld + k_col0 + (int64_t)h * k_hs + (int64_t)c * CH, kv);
+        const float dl = sd[h * N + n];
+        const double sdl = (double)scale * (double)dl, wd = (double)sl[h * N + n];
+#pragma unroll
+        for (int e = 0; e < CH; ++e) {
+          acc[e] = fma((double)dl, (double)kv[e], acc[e]);
+          ov[e] = (float)fma(sdl, (double)qv[e], wd * (double)dv[e]);
+        }
+        pwb_store<VEC>(dk, dk_dt, row * dk_ld + dk_col0 + (int64_t)h * dk_hs + (int64_t)c * CH, ov);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < CH; ++e) {
+      red[t] = acc[e];
+      __syncthreads();
+      if (ok && rg == 0) {
+        double s = 0.0;
+        for (int x = 0; x < R; ++x) s += red[x * CCt + cl];
+        dq0[(int64_t)bl * H * dlen + (int64_t)h * dlen + (int64_t)c * CH + e] = (float)((double)scale * s);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// include/rfmi.h: rf_poswise_bwd
+extern "C" int rf_poswise_bwd(const void* q0, int q0_dtype, int64_t q0_ld, const void* k, int dtype, int64_t k_ld, int k_col0,
+                              int k_hstride, int dlen, const float* dw, const float* ds, int64_t ds_ld, float* dq0, void* dk,
+                              int dk_dtype, int64_t dk_ld, int dk_col0, int dk_hstride, int B, int N, int L, int H, float scale,
+                              float p, uint64_t seed, uint64_t offset, void* stream) {
+  RF_CHECK_DT(dtype);
+  RF_CHECK_DT(q0_dtype);
+  RF_CHECK_DT(dk_dtype);
+  if (!q0 || !k || !dq0 || !dk || (!dw && !ds)) return RF_EINVAL;
+  if (B <= 0 || N <= 0 || L <= 0 || H <= 0 || dlen <= 0 || (int64_t)B * L > 0x7fffffff || (int64_t)N * H > 0x7fffffff) return RF_EINVAL;
+  if (k_col0 < 0 || k_hstride < 0 || dk_col0 < 0 || dk_hstride < 0) return RF_EINVAL;
+  if (q0_ld < (int64_t)H * dlen || k_ld < k_col0 + (int64_t)(H - 1) * k_hstride + dlen) return RF_EINVAL;
+  if (dk_ld < dk_col0 + (int64_t)(H - 1) * dk_hstride + dlen || (H > 1 && dk_hstride < dlen)) return RF_EINVAL;
+  if (ds && (H != 1 || ds_ld < dlen)) return RF_EINVAL;
+  if (!(p >= 0.f) || !(p < 1.f)) return RF_EINVAL;
+  if ((int64_t)N * H > 16384) return RF_EINVAL;
+  const size_t lds = pwb_lds_bytes(N, H);
+  if (lds > 64 * 1024) return RF_EINVAL;
+  const int64_t strides = q0_ld | k_ld | k_col0 | (H > 1 ? k_hstride : 0) | dk_ld | dk_col0 | (H > 1 ? dk_hstride : 0) | (ds ? ds_ld : 0);
+  const uintptr_t ptrs = (uintptr_t)q0 | (uintptr_t)k | (uintptr_t)dq0 | (uintptr_t)dk | (uintptr_t)ds;
+  const bool vec = (dlen & 7) == 0 && (strides & 7) == 0 && (ptrs & 15) == 0;
+  const bool drop = p > 0.f;
+  const unsigned thresh = drop ? dropout_threshold(p) : 0u;
+  const float inv_keep = drop ? 1.f / (1.f - p) : 1.f;
+  if (!drop) seed = offset = 0;
+#define PWB_LAUNCH(V_, D_)                                                                                                          \
+  hipLaunchKernelGGL((poswise_bwd_kernel<V_, D_>), dim3(B * L), dim3(256), lds, (hipStream_t)stream, q0, q0_dtype, q0_ld, k, dtype, \
+                     k_ld, k_col0, k_hstride, dlen, dw, ds, ds_ld, dq0, dk, dk_dtype, dk_ld, dk_col0, dk_hstride, N, L, H, scale,   \
+                     thresh, inv_keep, seed, offset)
+  if (vec && drop) PWB_LAUNCH(true, true);
+  else if (vec) PWB_LAUNCH(true, false);
+  else if (drop) PWB_LAUNCH(false, true);
+  else PWB_LAUNCH(false, false);
+#undef PWB_LAUNCH
+  return rf_launch_status();
+}

@@ -555,8 +555,13 @@ class PairEmbedding(RFModule):
 # ================================================================================================
 # MSA row (tied) attention
 # ================================================================================================
-class PositionWiseWeightFactor(RFModule):
-    """rf.py:184-217."""
+class PositionWiseWeightFactor(RecordingModule):
+    """rf.py:184-217.  enable_backward(): with grad mode on, forward(msa_emb) records on the direct form (weights()), and
+    loss.backward() fills the .grad of to_q and to_k and of msa_emb where it requires grad, through rf_poswise_bwd
+    (include/rfmi.h); in train() mode the backward replays the dropout on the softmax weights.  to_k's bias moves every logit of a
+    softmax by the same amount: its gradient is the sum of terms that cancel, zero up to their rounding.  d_msa must be a multiple
+    of 8 while recording.  The attention layers and the structure track call weights() / weights_head_major() /
+    weights_collapsed() without a tape: RoseTTAFold.forward never records here."""
 
     def __init__(self, d_msa=384, n_heads=12, p_dropout=0.1):
         super().__init__()
@@ -569,8 +574,12 @@ class PositionWiseWeightFactor(RFModule):
         self.to_q = nn.Sequential(Linear(d_msa, d_msa), nn.Identity())
         self.to_k = nn.Sequential(Linear(d_msa, d_msa), nn.Identity())
 
-    def drop(self, w):
-        """rf.py:217: dropout on the softmax weights (training mode; they then no longer sum to one, as in the reference)."""
+    def drop(self, w, tape=None):
+        """rf.py:217: dropout on the softmax weights (training mode; they then no longer sum to one, as in the reference).
+        tape: receives the dropout's (p, seed, offset) record as "drop" (None: nothing was dropped)."""
+        if tape is not None:
+            tape["drop"] = _dropout_rec(w, self.p_dropout) if self.training else None
+            return w
         return dropout_(w, self.p_dropout) if self.training else w
 
     def query_proj(self, xn):
@@ -581,14 +590,44 @@ class PositionWiseWeightFactor(RFModule):
                  bias=_f(self.to_q[0].bias))
         return q0
 
-    def weights(self, xn, w_out=None):
-        """xn: T [B,N,L,d] -> w fp32 [B,N,H,L]."""
+    def weights(self, xn, w_out=None, tape=None):
+        """xn: T [B,N,L,d] -> w fp32 [B,N,H,L].  tape: a dict that receives what _backward needs (the input and the dropout
+        record; same kernels, same numbers)."""
         B, N, Lr, D = xn.shape
+        _check_backward_call(self, tape, None, D)
         q0 = self.query_proj(xn)
         k = ops.linear(xn, self.wt("k", self.to_k[0]), _f(self.to_k[0].bias))
         w = torch.empty(B, N, self.n_heads, Lr, device=xn.device, dtype=F32) if w_out is None else w_out
         ops.poswise(q0, D, k, D, 0, self.d_head, self.d_head, w, None, 0, 0, 0, B, N, Lr, self.n_heads, self.scale, 1.0)
-        return self.drop(w)
+        if tape is not None:
+            tape["xn"] = xn
+        return self.drop(w, tape)
+
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, N, H, L] gradient of the weights (read only).  Returns (fp32 d xn [B,N,L,d], {param: grad}).
+        With q0 and k rebuilt from the saved input by the forward's two projections:
+            dq0, dk = rf_poswise_bwd(q0, k, g)                          (the dropout record replayed)
+            dW_k, db_k = dk^T xn, sum dk;   dW_q, db_q = dq0^T xn_0, sum dq0     rf_conv_wgrad
+            d xn = dk W_k;   d xn[:, 0] += dq0 W_q                      rf_gemm"""
+        xn = tape["xn"]
+        B, N, Lr, D = xn.shape
+        H, dh = self.n_heads, self.d_head
+        lq, lk = self.to_q[0], self.to_k[0]
+        q0 = self.query_proj(xn)
+        k = ops.linear(xn, self.wt("k", lk), _f(lk.bias))
+        dq0, dk = ops.poswise_bwd(q0, D, k, D, 0, dh, dh, B, N, Lr, H, self.scale, dw=g, dk_dtype=T(), dropout=tape["drop"])
+        del q0, k
+        dq0_t = ops.cast(dq0.view(B * Lr, D), T())
+        x0 = torch.empty(B, Lr, D, device=xn.device, dtype=T())     # xn[:, 0]
+        ops.copy4d(xn, (0, N * Lr * D, D, 1), x0, (0, Lr * D, D, 1), (1, B, Lr, D))
+        grads = {}
+        grads[lk.weight], grads[lk.bias] = ops.conv_wgrad(dk, xn, 1, bias=True)
+        grads[lq.weight], grads[lq.bias] = ops.conv_wgrad(dq0_t, x0.view(B * Lr, D), 1, bias=True)
+        dx = ops.linear(dk, self.wt_input_grad("k", lk), None, out_dtype=F32, exact=True)
+        dx0 = ops.linear(dq0_t, self.wt_input_grad("q", lq), None, out_dtype=F32, exact=True).view(B, Lr, D)
+        for b in range(B):
+            ops.axpby(dx[b, 0], 1.0, dx0[b], 1.0, dx[b, 0])
+        return dx, grads
 
     def weights_head_major(self, xn):
         """xn: T [B,N,L,d] -> w fp32 [B,H,N,L], without the to_k projection over the N rows: per head
@@ -603,10 +642,12 @@ class PositionWiseWeightFactor(RFModule):
                  b_row=(0, 0, D), c_bs=(D, 0, 0), c_row=(0, 0, H * D))
         return self.drop(ops.poswise_collapsed(xn, u, self.scale))
 
-    def weights_collapsed(self, msa, lnm, m):
+    def weights_collapsed(self, msa, lnm, m, tape=None):
         """1-head weights for the structure track, q side in fp32: w = softmax_n(scale * m[b,n,l,:] . u[b,l,:]) with
         u = to_q(LN(msa[:,0])) W_k  (to_k's bias is constant over n and drops out of the softmax).
-        msa fp32 [B,N,L,D]; lnm = the LayerNorm applied to it; m = lnm(msa) in T."""
+        msa fp32 [B,N,L,D]; lnm = the LayerNorm applied to it; m = lnm(msa) in T.
+        tape: a dict that receives what _node_input_backward needs (row 0 normalised, q0, u and the dropout record; same
+        kernels, same numbers)."""
         assert self.n_heads == 1
         B, N, Lr, D = msa.shape
         row0 = ops.layernorm(msa[:, 0].contiguous(), _f(lnm.weight), _f(lnm.bias), eps=lnm.eps, out_dtype=F32)
@@ -615,11 +656,19 @@ class PositionWiseWeightFactor(RFModule):
         u = ops.linear(q0, wkt, None, out_dtype=F32)
         w = torch.empty(B, N, 1, Lr, device=msa.device, dtype=F32)
         ops.poswise(u, D, m, D, 0, 0, D, w, None, 0, 0, 0, B, N, Lr, 1, self.scale, 1.0)
-        return self.drop(w)
+        if tape is not None:
+            tape.update(row0=row0, q0=q0, u=u)
+        return self.drop(w, tape)
 
-    def forward(self, msa_emb):
-        w = self.weights(ops.cast(msa_emb.contiguous(), T()))
+    def _record(self, msa_emb, tape):
+        w = self.weights(ops.cast(msa_emb.contiguous(), T()), tape=tape)
         return w.unsqueeze(-1)  # b N h l 1
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        B, N, Lr, _ = tape["xn"].shape
+        dx, grads = self._backward(tape, _scaled_copy(gs[0], s).view(B, N, self.n_heads, Lr))
+        _unscale([dx], s)
+        return dx, grads
 
 
 # Shortest chain that fills no tile of the fused tied-attention kernels (ops.TIED_TILES) and still takes them, on their tail
@@ -1830,7 +1879,8 @@ class GraphTransformer(RecordingModule):
     attends uniformly whatever its logits: its query and every key and edge logit receive no gradient from that row, only the
     value path does -- the derivative of what the forward computes; the reference's autograd would differentiate logits that its
     own -1e9 rounds away, and is not followed.  Channel counts (d_node_in, d_edge, n_heads * d_node_out) must be multiples of 8
-    while recording.  InitialCoordGenerationWithMsaAndPair calls run() without a tape: RoseTTAFold.forward never records here."""
+    while recording.  InitialCoordGenerationWithMsaAndPair calls run() with a tape only while it records itself;
+    RoseTTAFold.forward reaches it without one and never records here."""
     _rf_n_inputs = 3   # node_feat, edge_feat, edge_mask (no gradient; may be None)
 
     def __init__(self, d_node_in, d_node_out, d_edge, n_heads, p_dropout=0.15):
@@ -1926,7 +1976,8 @@ class GraphTransformerBlock(RecordingModule):
     """rf.py:667-676.  enable_backward() (switches `attn` along): with grad mode on, forward(node_feat, edge_feat, edge_mask)
     records, and loss.backward() fills the .grad of to_out's Linear, the LayerNorm, every Linear of `attn`, and of node_feat and
     edge_feat where they require grad (see GraphTransformer for the mask, the node with no edge and the channel counts).
-    InitialCoordGenerationWithMsaAndPair calls run() without a tape: RoseTTAFold.forward never records here."""
+    InitialCoordGenerationWithMsaAndPair calls run() with a tape only while it records itself; RoseTTAFold.forward reaches it
+    without one and never records here."""
     _rf_n_inputs = 3
     _rf_scales_own_grads = True   # the tail and the attention each at the fp16 mode's scale of their own gradient: _backward
 
@@ -1991,12 +2042,17 @@ class GraphTransformerBlock(RecordingModule):
         return self._record(node_feat, edge_feat, edge_mask, None)
 
 
-def _node_input(mod, msa, seq_onehot, out_dtype=None):
-    """[sum_n w*LN(msa) | onehot] zero-padded to a multiple of 8 columns, T (rf.py:715-724, 789-798)."""
+def _node_input(mod, msa, seq_onehot, out_dtype=None, tape=None):
+    """[sum_n w*LN(msa) | onehot] zero-padded to a multiple of 8 columns, T (rf.py:715-724, 789-798).
+    tape: a dict that receives what _node_input_backward needs (msa, the type LayerNorm(msa) was kept in, and what
+    weights_collapsed records; same kernels, same numbers)."""
     B, N, Lr, D = msa.shape
     # the fp32 (structure-track) form keeps LayerNorm(msa) in fp32 too: nothing upstream of the SE(3) stack is rounded
-    m = ln(mod.ln_msa, msa, out_dtype=F32 if (out_dtype == F32 and RT.struct_inputs_fp32) else None)
-    w = mod.poswise_weight.weights_collapsed(msa, mod.ln_msa, m)
+    m_dtype = F32 if (out_dtype == F32 and RT.struct_inputs_fp32) else None
+    m = ln(mod.ln_msa, msa, out_dtype=m_dtype)
+    w = mod.poswise_weight.weights_collapsed(msa, mod.ln_msa, m, tape=tape)
+    if tape is not None:
+        tape.update(msa=msa, m_dtype=m_dtype)
     Kp = pad8(D + 21)
     tmp = ops.zeros(B, Lr, Kp, device=msa.device, dtype=F32)
     ops.weighted_msa_sum(m, w, tmp, Kp)
@@ -2004,8 +2060,47 @@ def _node_input(mod, msa, seq_onehot, out_dtype=None):
     return ops.cast(tmp, out_dtype or T()), Kp
 
 
-class InitialCoordGenerationWithMsaAndPair(RFModule):
-    """rf.py:679-749."""
+def _node_input_backward(mod, tape, ds):
+    """Backward of _node_input (the front InitialCoordGenerationWithMsaAndPair and CoordUpdateWithMsaAndPair share) for ds =
+    contiguous fp32 [B, L, D], the gradient of the first D columns of the node input (the one-hot columns carry none).  Returns
+    (fp32 d msa, {param: grad}) over ln_msa and poswise_weight.  All of it runs in fp32, like the forward's q side.  With
+    m = LN(msa) recomputed, q0 = to_q(LN(msa[:, 0])) and u = q0 W_k from the tape:
+        du, dm = rf_poswise_bwd(u, m, ds)           the collapsed form with the weighted sum fused, the dropout record replayed
+        dq0 = du W_k^T;   dW_k = sum_{b,l} q0 du^T;   db_k = 0 exactly (constant over n: it drops out of the softmax)
+        dW_q, db_q = dq0^T row0, sum dq0;   dm[:, 0] += dq0 W_q
+        d msa, dgamma, dbeta = LayerNorm backward of all rows at once        rf_layernorm_bwd"""
+    msa = tape["msa"]
+    B, N, Lr, D = msa.shape
+    pw, lnm = mod.poswise_weight, mod.ln_msa
+    lq, lk = pw.to_q[0], pw.to_k[0]
+    m = ln(lnm, msa, out_dtype=tape["m_dtype"])
+    du, dm = ops.poswise_bwd(tape["u"], D, m, D, 0, 0, D, B, N, Lr, 1, pw.scale, ds=ds, ds_ld=D, dk_dtype=F32,
+                             dropout=tape["drop"])
+    del m
+    du, q0, row0 = du.view(B * Lr, D), tape["q0"].view(B * Lr, D), tape["row0"].view(B * Lr, D)
+    dq0 = ops.linear(du, pw.cached("wk32", lambda: lk.weight.detach().float().contiguous()), None, out_dtype=F32, exact=True)
+    grads = {lk.bias: ops.zeros(D, device=msa.device, dtype=F32)}
+    grads[lk.weight], _ = ops.conv_wgrad(q0, du, 1)
+    grads[lq.weight], grads[lq.bias] = ops.conv_wgrad(dq0, row0, 1, bias=True)
+    wqt = pw.cached("wqt32", lambda: lq.weight.detach().float().t().contiguous())
+    drow0 = ops.linear(dq0, wqt, None, out_dtype=F32, exact=True).view(B, Lr, D)
+    for b in range(B):
+        ops.axpby(dm[b, 0], 1.0, drow0[b], 1.0, dm[b, 0])
+    dmsa, grads[lnm.weight], grads[lnm.bias] = ops.layernorm_bwd(msa, dm, _f(lnm.weight), eps=lnm.eps)
+    return dmsa, grads
+
+
+class InitialCoordGenerationWithMsaAndPair(RecordingModule):
+    """rf.py:679-749.  enable_backward() (switches every block and its `attn` along): with grad mode on,
+    forward(msa, pair, seq_onehot, aa_idx) records, and loss.backward() fills the .grad of every parameter of the module and of
+    msa and pair where they require grad; seq_onehot and aa_idx carry no gradient.  The backward walks the forward in reverse:
+    the output projection, the blocks (GraphTransformerBlock._backward, d edge summed over the blocks in fp32), the two ELU
+    embeddings, the LayerNorm of pair, and the node input (_node_input_backward: rf_poswise_bwd in its fused collapsed form);
+    in train() mode it replays the dropout on the softmax weights and the blocks' attention dropout.  poswise_weight.to_k.bias
+    gets an exact zero.  d_msa, d_pair, d_node and d_edge must be multiples of 8 while recording.  RoseTTAFold.forward calls
+    run() without a tape: it never records here."""
+    _rf_n_inputs = 4   # msa, pair, seq_onehot (no gradient), aa_idx (no gradient)
+    _rf_scales_own_grads = True   # every stage at the fp16 mode's scale of its own gradient: _backward
 
     def __init__(self, d_msa, d_pair, d_node=64, d_edge=64, n_heads=4, n_layers=4, p_dropout=0.1):
         super().__init__()
@@ -2018,23 +2113,113 @@ class InitialCoordGenerationWithMsaAndPair(RFModule):
                                      for _ in range(n_layers)])
         self.to_out = Linear(d_node, 9)
 
-    def run(self, msa, pair, seq_onehot, aa_idx):
+    def run(self, msa, pair, seq_onehot, aa_idx, tape=None):
+        """tape: a dict that receives what _backward needs (the node input's own tape, both embeddings' inputs and outputs, the
+        blocks' tapes, pair; same kernels, same numbers)."""
         B, Lr, _, Dp = pair.shape
+        _check_backward_call(self, tape, None, msa.shape[-1], Dp, self.node_embed[0].out_features, self.edge_embed[0].out_features)
+        rec = tape is not None
+        front = {} if rec else None
         Ke = pad8(Dp + 1)
         ein = ops.zeros(B, Lr, Lr, Ke, device=pair.device, dtype=T())
-        nin, Kp = _node_input(self, msa, seq_onehot)
+        nin, Kp = _node_input(self, msa, seq_onehot, tape=front)
         node = ops.linear(nin, self.wt("n", self.node_embed[0], kpad=Kp), _f(self.node_embed[0].bias), out_dtype=F32,
                           act=L.ACT_ELU)
         ln(self.ln_pair, pair, out=ein, out_ld=Ke)
         ops.seqsep_feature(aa_idx.contiguous(), ein, Ke, Dp)  # clamp(sign(d) log(|d|+1), 0, 5.5), rf.py:746-749
         edge = ops.linear(ein, self.wt("e", self.edge_embed[0], kpad=Ke), _f(self.edge_embed[0].bias), act=L.ACT_ELU)
+        if rec:
+            tape.update(front=front, nin=nin, node0=node, pair=pair, ein=ein, edge=edge, blocks=[])
         for blk in self.blocks:
-            node = blk.run(node, edge)
+            sub = {} if rec else None
+            node = blk.run(node, edge, tape=sub)
+            if rec:
+                tape["blocks"].append(sub)
+        if rec:
+            tape["node"] = node.detach()
         xyz = ops.linear(ops.cast(node, T()), self.wt("o", self.to_out), _f(self.to_out.bias), out_dtype=F32)
         return xyz.view(B, Lr, 3, 3)
 
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, L, 9] gradient of xyz (read only).  Returns (fp32 d msa, fp32 d pair, {param: grad}).
+            d node = g W_o;   dW_o, db_o = g^T node, sum g        g zero-padded from 9 to 16 columns: the 16-bit weight gradient
+                                                                  and rf_gemm take multiples of 8 (wt_input_grad's npad)
+            d node, d edge += block backward, last block first     d edge summed over the blocks in fp32
+            da_e = d edge * ELU'(edge)                             rf_elu_bwd on an fp32 copy of the operand-typed edge embedding,
+                                                                  made here and freed after the call (the tape holds edge once)
+            dW_e, db_e = da_e^T ein, sum da_e;   d pair = LayerNorm backward of (da_e W_e)[..., :d_pair]    (the sequence-separation
+                                                                  column carries no gradient)
+            da_n = d node * ELU'(node0);   dW_n, db_n = da_n^T nin, sum da_n;   ds = (da_n W_n)[..., :d_msa]
+            d msa = _node_input_backward(ds)
+        In the fp16 mode each stage runs on a copy of its incoming gradient at a power-of-two scale of its own."""
+        B, Lr, _ = g.shape
+        lo, ln_, le = self.to_out, self.node_embed[0], self.edge_embed[0]
+        pair, nin, ein = tape["pair"], tape["nin"], tape["ein"]
+        D, Dp = tape["front"]["msa"].shape[-1], pair.shape[-1]
+        dev = g.device
+        # ---- output projection
+        s = _grad_scale([g])
+        gp = ops.zeros(B * Lr, 16, device=dev, dtype=F32)
+        ops.copy4d(_scaled_copy(g, s), (0, 0, 9, 1), gp, (0, 0, 16, 1), (1, 1, B * Lr, 9))
+        gp = ops.cast(gp, T())
+        node_t = ops.cast(tape["node"], T()).view(B * Lr, -1)
+        dw, db = ops.conv_wgrad(gp, node_t, 1, bias=True)
+        grads = {lo.weight: dw[:9], lo.bias: db[:9]}
+        dnode = ops.linear(gp, self.wt_input_grad("o", lo, npad=16), None, out_dtype=F32, exact=True).view(B, Lr, -1)
+        _unscale([dnode] + list(grads.values()), s)
+        # ---- blocks
+        dedge = None
+        for blk, sub in zip(reversed(self.blocks), reversed(tape["blocks"])):
+            dnode, de, gr = blk._backward(sub, dnode)
+            dedge = de if dedge is None else ops.axpby(dedge, 1.0, de, 1.0, dedge)
+            grads.update(gr)
+            del de
+        if dedge is None:   # (no block: the edges reach nothing)
+            dedge = ops.zeros(*tape["edge"].shape, device=dev, dtype=F32)
+        # ---- edge embedding, LayerNorm(pair)
+        s = _grad_scale([dedge])
+        if s != 1.0:
+            ops.axpby(dedge, s, None, 0.0, dedge)
+        da = ops.elu_bwd(dedge, ops.cast(tape["edge"], F32), None, T())
+        del dedge
+        dw, db = ops.conv_wgrad(da, ein, 1, bias=True)
+        we = self.cached("e_input_grad", lambda: le.weight.detach()[:, :Dp].t().to(T()).contiguous())
+        dein = ops.linear(da, we, None, out_dtype=F32, exact=True)
+        del da
+        dpair, dgamma, dbeta = ops.layernorm_bwd(pair, dein, _f(self.ln_pair.weight), eps=self.ln_pair.eps)
+        del dein
+        gr = {le.weight: dw[:, :Dp + 1].contiguous(), le.bias: db, self.ln_pair.weight: dgamma, self.ln_pair.bias: dbeta}
+        _unscale([dpair] + list(gr.values()), s)
+        grads.update(gr)
+        # ---- node embedding
+        s = _grad_scale([dnode])
+        da = ops.elu_bwd(_scaled_copy(dnode, s), tape["node0"], None, T())
+        dw, db = ops.conv_wgrad(da, nin, 1, bias=True)
+        wn = self.cached("n_input_grad", lambda: ln_.weight.detach()[:, :D].t().to(T()).contiguous())
+        ds = ops.linear(da, wn, None, out_dtype=F32, exact=True)
+        gr = {ln_.weight: dw[:, :D + 21].contiguous(), ln_.bias: db}
+        _unscale([ds] + list(gr.values()), s)
+        grads.update(gr)
+        # ---- node input (fp32 throughout: no scale)
+        dmsa, gr = _node_input_backward(self, tape["front"], ds)
+        grads.update(gr)
+        return dmsa, dpair, grads
+
+    def _backward_children(self):
+        return tuple(self.blocks)
+
+    def _record(self, msa, pair, seq_onehot, aa_idx, tape):
+        return self.run(msa.float().contiguous(), pair.float().contiguous(), seq_onehot.float(), aa_idx, tape=tape)
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        B, Lr = gs[0].shape[:2]
+        dmsa, dpair, grads = self._backward(tape, gs[0].float().contiguous().view(B, Lr, 9))
+        return (dmsa, dpair, None, None), grads
+
     def forward(self, msa, pair, seq_onehot, aa_idx):
-        return self.run(msa.float().contiguous(), pair.float().contiguous(), seq_onehot.float(), aa_idx)
+        if _recording(self):
+            return _RecordedFn.apply(self, msa, pair, seq_onehot, aa_idx, *self.parameters())
+        return self._record(msa, pair, seq_onehot, aa_idx, None)
 
 
 # ================================================================================================

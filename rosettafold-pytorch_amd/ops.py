@@ -662,6 +662,58 @@ def elu_bwd(g, y, x, out_dtype):
     return da
 
 
+def poswise_bwd(q0, q0_ld, k, k_ld, k_col0, k_hs, dlen, B, N, L_, H, scale, *, dw=None, ds=None, ds_ld=None, dk=None,
+                dk_dtype=F32, dk_ld=None, dk_col0=0, dk_hs=None, dropout=None):
+    """Backward of poswise in its addressing (rf_poswise_bwd): q0 rows [B*L] of q0_ld, k rows [B*N*L] of k_ld with head h at column
+    k_col0 + h * k_hs (dlen columns); dw contiguous fp32 [B, N, H, L] = the gradient of the weights (after their dropout) or None;
+    ds fp32 rows [B*L] of ds_ld = the gradient of sum_n w_n k_n (weighted_msa_sum fused behind the weights: the collapsed form,
+    H == 1) or None; dropout = the forward's (p, seed, offset) on the weights or None.  Returns (dq0 fp32 [B, L, H * dlen], dk):
+    dk = the given tensor (rows of dk_ld, head h at column dk_col0 + h * dk_hs), or a new contiguous [B, N, L, H * dlen] of
+    dk_dtype."""
+    _need_cuda(q0, k, dw, ds, dk)
+    HD = H * dlen
+    if min(B, N, L_, H, dlen) <= 0 or min(k_col0, k_hs, dk_col0) < 0:
+        raise ValueError("poswise_bwd: sizes must be positive, offsets and strides non-negative")
+    if dk is None:
+        dk = torch.empty(B, N, L_, HD, device=k.device, dtype=dk_dtype)
+        dk_ld, dk_col0, dk_hs = HD, 0, dlen
+    elif dk_ld is None or dk_hs is None:
+        raise ValueError("poswise_bwd: a given dk needs dk_ld and dk_hs")
+    if dw is None and ds is None:
+        raise ValueError("poswise_bwd: dw or ds (or both)")
+    for t_ in (q0, k, dk):
+        if not t_.is_contiguous():
+            raise ValueError("poswise_bwd: contiguous q0, k and dk")
+    if q0_ld < HD or q0.numel() < (B * L_ - 1) * q0_ld + HD:
+        raise ValueError(f"poswise_bwd: q0 holds {q0.numel()} elements, too few for [{B * L_}] rows of {q0_ld} with {HD} columns")
+    rows = B * N * L_
+    if k_ld < k_col0 + (H - 1) * k_hs + dlen or k.numel() < (rows - 1) * k_ld + k_col0 + (H - 1) * k_hs + dlen:
+        raise ValueError(f"poswise_bwd: k holds {k.numel()} elements, too few for [{rows}] rows of {k_ld}")
+    if (dk_ld < dk_col0 + (H - 1) * dk_hs + dlen or (H > 1 and dk_hs < dlen)
+            or dk.numel() < (rows - 1) * dk_ld + dk_col0 + (H - 1) * dk_hs + dlen):
+        raise ValueError(f"poswise_bwd: dk holds {dk.numel()} elements, too few for [{rows}] rows of {dk_ld}")
+    if dw is not None and (dw.dtype != F32 or dw.numel() != B * N * H * L_ or not dw.is_contiguous()):
+        raise ValueError(f"poswise_bwd: contiguous fp32 dw [{B}, {N}, {H}, {L_}]")
+    if ds is not None:
+        ds_ld = dlen if ds_ld is None else ds_ld
+        if H != 1:
+            raise ValueError("poswise_bwd: ds goes with the collapsed one-head form (H == 1)")
+        if ds.dtype != F32 or not ds.is_contiguous() or ds_ld < dlen or ds.numel() < (B * L_ - 1) * ds_ld + dlen:
+            raise ValueError(f"poswise_bwd: contiguous fp32 ds, [{B * L_}] rows of {ds_ld} with {dlen} columns")
+    p, seed, off = dropout if dropout is not None else (0.0, 0, 0)
+    dq0 = torch.empty(B, L_, HD, device=k.device, dtype=F32)
+    if p >= 1.0:   # everything was dropped: the weights, and with them both gradients, are zero
+        fill(dq0, 0.0)
+        if dk_ld == HD and dk_col0 == 0 and (H == 1 or dk_hs == dlen):
+            return dq0, fill(dk, 0.0)
+        raise ValueError("poswise_bwd: p >= 1 with a strided dk")
+    check(lib.rf_poswise_bwd(ptr(q0), dcode(q0.dtype), int(q0_ld), ptr(k), dcode(k.dtype), int(k_ld), int(k_col0), int(k_hs),
+                             int(dlen), ptr(dw), ptr(ds), int(ds_ld or 0), ptr(dq0), ptr(dk), dcode(dk.dtype), int(dk_ld),
+                             int(dk_col0), int(dk_hs), B, N, L_, H, float(scale), float(p), int(seed), int(off), stream()),
+          "rf_poswise_bwd")
+    return dq0, dk
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through
