@@ -669,6 +669,25 @@ int rf_poswise_bwd(const void* q0, int q0_dtype, int64_t q0_ld, const void* k, i
                    int dk_col0, int dk_hstride, int B, int N, int L, int H, float scale, float p, uint64_t seed, uint64_t offset,
                    void* stream);
 
+/* ---- backward pass of MsaUpdateWithPairAndCoord (csrc/backward.hip; structure.py, rf.py:865-920) ---------------------------
+ * Backward of rf_dist_masked_attention (rf_version >= 16).  Per (b, h, i), over the columns j, with the forward's
+ *   logit_j = q_i . k_j + (|CA_i - CA_j| < bins[h] ? 0 : -1e9),   p = softmax_j(logit):
+ *   ds_j = p_j (datt_j - sum_l p_l datt_l)        datt fp32 [B,H,L,L] = the gradient of the probabilities
+ *   dq[b,i,h,:] = sum_j ds_ij k[b,j,h,:]          dk[b,j,h,:] = sum_i ds_ij q[b,i,h,:]
+ * q (pre-scaled, as the forward sees it: the caller multiplies dq by its scale) and k: fp32 [B,L,H*d]; xyz fp32 [B,L,3,3];
+ * bins fp32 [H].  Outputs: dq, dk fp32 [B,L,H*d]; ds_map fp32 [B,H,L,L], the workspace the second kernel sums dk from, which
+ * holds ds on return.  EVERY element of the three is written by the call.  xyz receives no gradient: the mask is piecewise
+ * constant.  Nothing of the forward is saved but its inputs: a block per (b, i) recomputes the row in fp32 (the stored map is
+ * 16-bit and is not read) and takes the distance test with the forward's own fp32 expression, so both masks agree bit for bit.
+ * A masked entry has p = 0 exactly (exp(-1e9 - max) = 0) and so ds = 0 exactly; a residue out of every other residue's range
+ * has p = 1 on itself, and its rows of dq and dk are exactly 0, as are all of dq and dk at L == 1.
+ * Accumulation: the dot products q.k in fp32 in the forward's order; the softmax normaliser, sum_l p_l datt_l and the sums over
+ * j (dq) and over i (dk) in fp64, each result rounded once.  No atomics: the same bits run to run.  datt is read twice per row
+ * (the second time from cache) so that the LDS need stays the forward's.
+ * RF_EINVAL before any launch: a NULL tensor, a size <= 0, or H * L * 4 bytes of LDS > 64 KB (the forward's own limit; any d). */
+int rf_dist_masked_attention_bwd(const float* q, const float* k, const float* xyz, const float* bins, const float* datt,
+                                 float* dq, float* dk, float* ds_map, int B, int L, int H, int d, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

@@ -1252,3 +1252,117 @@ extern "C" int rf_poswise_bwd(const void* q0, int q0_dtype, int64_t q0_ld, const
 #undef PWB_LAUNCH
   return rf_launch_status();
 }
+
+// ================================================================================================
+// rf_dist_masked_attention_bwd: backward of MsaUpdateWithPairAndCoord's attention map (ops.hip: dist_att_kernel; rf.py:899-914).
+// Block per row (b, i) like the forward, with the forward's LDS (H * L floats and nothing more); the row's logits and
+// probabilities are recomputed from q, k and xyz (the stored map is 16-bit and is not read).
+//   phase 1  the forward's own loop: logit_{h,j} = q_i . k_j + dist_mask_bias (common.h: the same fp32 decision as the forward)
+//   phase 2  per head, one wave: p = softmax(logit), ds = p (datt - sum p datt); datt is streamed from memory twice (the second
+//            time from cache) instead of doubling the LDS; ds replaces p in LDS and goes to the fp32 map ds_map [B, H, L, L]
+//   phase 3  dq_i = sum_j ds_j k_j: a wave takes DAB_CW channels at a time, its 64 / DAB_CW lane groups split j (ascending within
+//            a group) and meet in a shuffle butterfly -- no scratch beyond the forward's LDS
+// dist_att_bwd_cols_kernel, block per (b, j), then sums dk_j = sum_i ds_ij q_i from the map the same way: no atomics, a fixed
+// order, the same bits run to run.  A masked entry has exp(-1e9 - max) = 0, so p = 0 and ds = 0 exactly.
+// ================================================================================================
+#define DAB_CW 16  // channels a wave takes at a time (64-byte segments of a k / q row); 64 / DAB_CW lane groups split the sum
+
+__global__ __launch_bounds__(256) void dist_att_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                           const float* __restrict__ xyz, const float* __restrict__ bins,
+                                                           const float* __restrict__ datt, float* __restrict__ dq,
+                                                           float* __restrict__ ds_map, int L, int H, int d) {
+  extern __shared__ float dab_sm[];  // [H][L]: logits, then exp, then ds
+  const int bi = blockIdx.x, b = bi / L, i = bi - b * L;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int HD = H * d;
+  // ---- phase 1
+  const float cx = xyz[((int64_t)bi * 3 + 1) * 3 + 0], cy = xyz[((int64_t)bi * 3 + 1) * 3 + 1],
+              cz = xyz[((int64_t)bi * 3 + 1) * 3 + 2];
+  for (int e = t; e < H * L; e += 256) {
+    const int h = e / L, j = e - h * L;
+    const float* qr = q + ((int64_t)bi * H + h) * d;
+    const float* kr = k + (((int64_t)b * L + j) * H + h) * d;
+    float a = 0.f;
+    for (int c = 0; c < d; ++c) a = fmaf(qr[c], kr[c], a);
+    dab_sm[e] = a + dist_mask_bias(cx, cy, cz, xyz + (((int64_t)b * L + j) * 3 + 1) * 3, bins[h]);
+  }
+  __syncthreads();
+  // ---- phase 2 (a lane reads and writes its own entries j = lane + 64 m only)
+  for (int h = wv; h < H; h += 4) {
+    float* ps = dab_sm + h * L;
+    const int64_t row = (((int64_t)b * H + h) * L + i) * L;  // element [b, h, i, 0] of datt and of the map
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, ps[j]);
+    mx = wave_max(mx);
+    // the normaliser and sum p datt in fp64, as in graph_attention_bwd_kernel: a row with two or three residues in range
+    // cancels in datt - sum p datt
+    double s = 0.0;
+    for (int j = lane; j < L; j += 64) {
+      const float ex = expf(ps[j] - mx);
+      ps[j] = ex;
+      s += (double)ex;
+    }
+    const double inv = 1.0 / wave_sum_f64(s);
+    double dot = 0.0;
+    for (int j = lane; j < L; j += 64) dot = fma((double)ps[j] * inv, (double)datt[row + j], dot);
+    dot = wave_sum_f64(dot);
+    for (int j = lane; j < L; j += 64) {
+      const float dsv = (float)((double)ps[j] * inv * ((double)datt[row + j] - dot));
+      ps[j] = dsv;
+      ds_map[row + j] = dsv;
+    }
+  }
+  __syncthreads();
+  // ---- phase 3
+  const int jg = lane / DAB_CW, cl = lane % DAB_CW;
+  const int nchunk = (HD + DAB_CW - 1) / DAB_CW;
+  for (int ch = wv; ch < nchunk; ch += 4) {  // (wave-uniform trip count: the shuffles below run with every lane)
+    const int c = ch * DAB_CW + cl;
+    const bool ok = c < HD;
+    double a = 0.0;
+    if (ok) {
+      const float* ds = dab_sm + (c / d) * L;
+      const float* kc = k + (int64_t)b * L * HD + c;
+#pragma unroll 4
+      for (int j = jg; j < L; j += 64 / DAB_CW) a = fma((double)ds[j], (double)kc[(int64_t)j * HD], a);
+    }
+    for (int o = DAB_CW; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+    if (ok && jg == 0) dq[(int64_t)bi * HD + c] = (float)a;
+  }
+}
+
+// dk[b, j, c] = sum_i ds[b, h, i, j] q[b, i, c]: block per (b, j); lanes and order as in phase 3 above, over the rows i
+__global__ __launch_bounds__(256) void dist_att_bwd_cols_kernel(const float* __restrict__ ds_map, const float* __restrict__ q,
+                                                                float* __restrict__ dk, int L, int H, int d) {
+  const int bj = blockIdx.x, b = bj / L, j = bj - b * L;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int HD = H * d;
+  const int ig = lane / DAB_CW, cl = lane % DAB_CW;
+  const int nchunk = (HD + DAB_CW - 1) / DAB_CW;
+  for (int ch = wv; ch < nchunk; ch += 4) {
+    const int c = ch * DAB_CW + cl;
+    const bool ok = c < HD;
+    double a = 0.0;
+    if (ok) {
+      const float* col = ds_map + ((int64_t)b * H + c / d) * L * L + j;
+      const float* qc = q + (int64_t)b * L * HD + c;
+#pragma unroll 4
+      for (int i = ig; i < L; i += 64 / DAB_CW) a = fma((double)col[(int64_t)i * L], (double)qc[(int64_t)i * HD], a);
+    }
+    for (int o = DAB_CW; o < 64; o <<= 1) a += __shfl_xor(a, o, 64);
+    if (ok && ig == 0) dk[(int64_t)bj * HD + c] = (float)a;
+  }
+}
+
+// include/rfmi.h: rf_dist_masked_attention_bwd
+extern "C" int rf_dist_masked_attention_bwd(const float* q, const float* k, const float* xyz, const float* bins, const float* datt,
+                                            float* dq, float* dk, float* ds_map, int B, int L, int H, int d, void* stream) {
+  if (!q || !k || !xyz || !bins || !datt || !dq || !dk || !ds_map) return RF_EINVAL;
+  if (B <= 0 || L <= 0 || H <= 0 || d <= 0 || (int64_t)B * L > 0x7fffffff || (int64_t)H * d > 0x7fffffff) return RF_EINVAL;
+  const size_t lds = (size_t)H * L * sizeof(float);  // the forward's
+  if (lds > 64 * 1024) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(dist_att_bwd_kernel, dim3(B * L), dim3(256), lds, s, q, k, xyz, bins, datt, dq, ds_map, L, H, d);
+  hipLaunchKernelGGL(dist_att_bwd_cols_kernel, dim3(B * L), dim3(256), 0, s, ds_map, q, dk, L, H, d);
+  return rf_launch_status();
+}

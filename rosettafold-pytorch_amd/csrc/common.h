@@ -103,6 +103,14 @@ __device__ __forceinline__ float rf_max_nan(float a, float b) { return __builtin
 
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
+// MsaUpdateWithPairAndCoord's additive distance mask (rf.py:906-912): 0 where |c - cj| < bin, else -1e9.  Written once for
+// rf_dist_masked_attention and its backward, so that both take the same fp32 decision at a distance next to a bin.
+__device__ __forceinline__ float dist_mask_bias(float cx, float cy, float cz, const float* cj, float bin) {
+  const float dx = cx - cj[0], dy = cy - cj[1], dz = cz - cj[2];
+  const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
+  return dist < bin ? 0.f : -1e9f;
+}
+
 // Training-mode dropout mask (rf_dropout, csrc/ops.hip; replayed by the backward kernels): Philox4x32-10 keyed by the 64-bit
 // seed, counter = offset + element / 4, word element % 4.
 __device__ __forceinline__ void philox4x32_10(uint64_t ctr, uint64_t key, unsigned (&r)[4]) {

@@ -1412,10 +1412,7 @@ __global__ __launch_bounds__(256) void dist_att_kernel(const float* q, const flo
     const float* kr = k + (((int64_t)b * L + j) * H + h) * dq;
     float a = 0.f;
     for (int c = 0; c < dq; ++c) a = fmaf(qr[c], kr[c], a);
-    const float* cj = xyz + (((int64_t)b * L + j) * 3 + 1) * 3;
-    const float dx = cx - cj[0], dy = cy - cj[1], dz = cz - cj[2];
-    const float dist = sqrtf(dx * dx + dy * dy + dz * dz);
-    sm[e] = a + (dist < bins[h] ? 0.f : -1e9f);
+    sm[e] = a + dist_mask_bias(cx, cy, cz, xyz + (((int64_t)b * L + j) * 3 + 1) * 3, bins[h]);
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -1586,7 +1583,7 @@ extern "C" int rf_add_pos_enc(const float* x, const int64_t* aa_idx, const float
   return rf_launch_status();
 }
 
-extern "C" int rf_version(void) { return 15; }
+extern "C" int rf_version(void) { return 16; }
 #ifdef RF_H16_IS_F16
 extern "C" const char* rf_build_info(void) { return "librfmi_f16 gfx950 (MI355X) round-3: 16-bit operand type = IEEE fp16"; }
 #else

@@ -916,6 +916,29 @@ def dist_masked_attention(q, k, xyz, bins, att, B, L_, H, dq):
                                        stream()), "rf_dist_masked_attention")
 
 
+def dist_masked_attention_bwd(q, k, xyz, bins, datt, B, L_, H, dq):
+    """Backward of dist_masked_attention (rf_dist_masked_attention_bwd): q (scaled, as the forward saw it) and k contiguous fp32
+    [B, L, H*dq], xyz contiguous fp32 [B, L, 3, 3], bins fp32 [H], datt contiguous fp32 [B, H, L, L] = the gradient of the
+    probabilities.  Returns (d q, d k fp32 [B, L, H*dq], ds fp32 [B, H, L, L] = the logits' gradient, exactly 0 at a masked
+    entry).  xyz has no gradient (the mask is piecewise constant)."""
+    _need_cuda(q, k, xyz, bins, datt)
+    HD = H * dq
+    for t_ in (q, k):
+        if t_.dtype != F32 or tuple(t_.shape) != (B, L_, HD) or not t_.is_contiguous():
+            raise ValueError(f"dist_masked_attention_bwd: contiguous fp32 q and k [{B}, {L_}, {HD}]")
+    if xyz.dtype != F32 or tuple(xyz.shape) != (B, L_, 3, 3) or not xyz.is_contiguous():
+        raise ValueError(f"dist_masked_attention_bwd: contiguous fp32 xyz [{B}, {L_}, 3, 3]")
+    if bins.dtype != F32 or bins.numel() != H or not bins.is_contiguous():
+        raise ValueError(f"dist_masked_attention_bwd: contiguous fp32 bins [{H}]")
+    if datt.dtype != F32 or tuple(datt.shape) != (B, H, L_, L_) or not datt.is_contiguous():
+        raise ValueError(f"dist_masked_attention_bwd: contiguous fp32 datt [{B}, {H}, {L_}, {L_}]")
+    d_q, d_k = (torch.empty(B, L_, HD, device=q.device, dtype=F32) for _ in range(2))
+    ds = torch.empty(B, H, L_, L_, device=q.device, dtype=F32)
+    check(lib.rf_dist_masked_attention_bwd(ptr(q), ptr(k), ptr(xyz), ptr(bins), ptr(datt), ptr(d_q), ptr(d_k), ptr(ds), B, L_, H,
+                                           dq, stream()), "rf_dist_masked_attention_bwd")
+    return d_q, d_k, ds
+
+
 # --------------------------------------------------------------------------------------------- SE(3)
 def knn_mask(xyz, aa_idx, k, kmin=9):
     B, L_ = xyz.shape[:2]

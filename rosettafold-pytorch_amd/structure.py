@@ -10,11 +10,12 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .ops import F32
-from .model import (RFModule, Residual, FeedForward, PositionWiseWeightFactor, MsaEmbedding, PairEmbedding,
+from .model import (RFModule, RecordingModule, Residual, FeedForward, PositionWiseWeightFactor, MsaEmbedding, PairEmbedding,
                     MsaUpdateUsingSelfAttention, PairUpdateWithMsa, PairUpdateWithAxialAttention, MsaUpdateWithPair,
                     InitialCoordGenerationWithMsaAndPair, PredictionHead, LayerNorm, Linear, _node_input, _f, ln, T, pad8,
                     CA_IDX, fresh_f32, check_index_range, RT)
-from .backward import _recording
+from .backward import (_recording, _RecordedFn, _check_backward_call, _copy, _grad_scale, _scaled_copy, _unscale,
+                       _pre_norm_residual_bwd)
 
 
 # ================================================================================================
@@ -368,8 +369,23 @@ class CoordUpdateWithMsaAndPair(RFModule):
 # ================================================================================================
 # MSA update with coordinates
 # ================================================================================================
-class MsaUpdateWithPairAndCoord(RFModule):
-    """rf.py:865-920."""
+class MsaUpdateWithPairAndCoord(RecordingModule):
+    """rf.py:865-920.  enable_backward() (switches the FeedForward in `to_out` along): with grad mode on,
+    forward(xyz, state, msa) records, and loss.backward() fills the .grad of every parameter of the module and of state and msa
+    where they require grad.  xyz carries no gradient: it enters through the distance mask only, which is piecewise constant
+    (xyz.grad stays None, as under the reference's autograd).  The backward walks the forward in reverse: the feed-forward
+    (FeedForward._backward, its dropouts replayed in train() mode), ln_out, the attention . V contraction (d att and d v on
+    rf_gemm), the map (rf_dist_masked_attention_bwd, include/rfmi.h), the three projections, and ln_state / ln_msa; LN(state),
+    LN(msa), q, k, v^T and the 16-bit map are rebuilt from the saved inputs with the forward's own launches.  to_k.bias gets an
+    exact zero: q_i . b_k is added to every logit of row i and drops out of the softmax (float64 autograd of the reference
+    returns rounding noise for it, about 1e-15 of to_q.bias's gradient; a relative comparison against that is meaningless).
+    The fp16 mode's power-of-two gradient scale is applied HERE, not by the autograd Function (_rf_scales_own_grads): the
+    feed-forward, ln_out and the value path each run on a copy of their incoming gradient at a scale of their own; the q / k side
+    is fp32 throughout and runs unscaled.  d_msa, d_msa / n_heads, d_state and n_heads * d_trfm_inner must be multiples of 8 while
+    recording.  ThreeTrackBlock.run3, RoseTTAFold.forward and the captured graph call run() without a tape: they never record
+    here."""
+    _rf_n_inputs = 3   # xyz (no gradient), state, msa
+    _rf_scales_own_grads = True
 
     def __init__(self, d_msa, d_state, d_trfm_inner, d_ff, distance_bins=[8, 12, 16, 20], p_dropout=0.1):
         super().__init__()
@@ -385,8 +401,16 @@ class MsaUpdateWithPairAndCoord(RFModule):
         self.ln_out = LayerNorm(d_msa)
         self.to_out = Residual(nn.Sequential(LayerNorm(d_msa), FeedForward(d_msa, d_ff, p_dropout)))
 
-    def run(self, xyz, state, msa):
-        """returns the new fp32 msa [B,N,L,D] (the residual base is LayerNorm(msa), rf.py:893,918)."""
+    @staticmethod
+    def _map_dtype(Lr):
+        """the type of the attention map and of the key-contiguous operands contracted with it over the chain"""
+        return T() if Lr % 8 == 0 else F32
+
+    def _attend(self, xyz, state, msa):
+        """The forward up to the attention . V contraction; the backward rebuilds its operands with the same launches.  Returns
+        (LN(state) fp32, LN(msa) fp32, LN(msa) T, scaled q fp32, k fp32, bins, the map [B,H,L,L], att . V fp32 [B,N,L,D]).  The map
+        and v^T are of the compute type; in the 16-bit modes a chain length that is no multiple of 8, which the 16-bit GEMM cannot
+        contract over (RF_EALIGN), keeps both in fp32 and contracts them on the exact fp32 kernel (_map_dtype)."""
         B, N, Lr, D = msa.shape
         H, dq = self.n_heads, self.d_inner
         dv = D // H
@@ -398,9 +422,9 @@ class MsaUpdateWithPairAndCoord(RFModule):
         ops.axpby(q, self.scale, None, 0.0, q)
         k = ops.linear(st, self.to_k.weight.detach(), _f(self.to_k.bias), out_dtype=F32, exact=True)
         bins = self.cached("bins", lambda: torch.tensor(self.distance_bins, dtype=F32, device=dev))
-        att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
+        att = torch.empty(B, H, Lr, Lr, device=dev, dtype=self._map_dtype(Lr))
         ops.dist_masked_attention(q, k, xyz.contiguous(), bins, att, B, Lr, H, dq)
-        v_t = torch.empty(B, N, D, Lr, device=dev, dtype=T())
+        v_t = torch.empty(B, N, D, Lr, device=dev, dtype=att.dtype)
         ops.gemm(self.wt("v", self.to_v), m_t, v_t, D, Lr, D, batch=(B * N, 1, 1), b_bs=(Lr * D, 0, 0),
                  c_bs=(D * Lr, 0, 0), c_row=(0, 0, Lr), bias=_f(self.to_v.bias), bias_mode=L.BIAS_ROW, exact=False)
         out = torch.empty(B, N, Lr, D, device=dev, dtype=F32)
@@ -408,13 +432,120 @@ class MsaUpdateWithPairAndCoord(RFModule):
                  a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
                  b_bs=(N * D * Lr, dv * Lr, 0), b_row=(dv, D * Lr, Lr),
                  c_bs=(N * Lr * D, dv, 0), c_row=(0, 0, D), c_col=(dv, Lr * D), exact=False)
+        return st, m32, m_t, q, k, bins, att, out
+
+    def run(self, xyz, state, msa, tape=None):
+        """returns the new fp32 msa [B,N,L,D] (the residual base is LayerNorm(msa), rf.py:893,918).
+        tape: a dict that receives what _backward needs (xyz, state, msa, an fp32 copy of the stream in front of the feed-forward
+        and the feed-forward's own tape; same kernels, same numbers)."""
+        D = msa.shape[-1]
+        _check_backward_call(self, tape, None, D, D // self.n_heads, state.shape[-1], self.n_heads * self.d_inner)
+        _, m32, _, _, _, _, _, out = self._attend(xyz, state, msa)
         o = ln(self.ln_out, out, out_dtype=F32)
         ops.axpby(m32, 1.0, o, 1.0, m32)
-        self.to_out.fn[1].apply_residual(ln(self.to_out.fn[0], m32), m32)
+        sub = None
+        if tape is not None:
+            sub = {}
+            tape.update(xyz=xyz, state=state, msa=msa, x1=_copy(m32), ff=sub)
+        self.to_out.fn[1].apply_residual(ln(self.to_out.fn[0], m32), m32, tape=sub)
         return m32
 
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, N, L, D] gradient of the output (overwritten).  Returns (fp32 d state [B, L, d_state], fp32
+        d msa [B, N, L, D], {param: grad}).  With m = LN(msa), s = LN(state), x1 = m + LN_out(out), y = x1 + FF(LN_ff(x1)):
+            g  <- g + d x1 of the feed-forward                           _pre_norm_residual_bwd; g is now d x1 = d m (residual) = d o
+            d out, dgamma_o, dbeta_o = LayerNorm backward                rf_layernorm_bwd on the rebuilt att . V
+            d att[b,h,i,j] = sum_{n,c} d out[b,n,i,h,c] v[b,n,j,h,c]     rf_gemm, K = N * dv in chunks of dv (v = to_v(m) row-major)
+            d v[b,n,j,h,c] = sum_i att[b,h,i,j] d out[b,n,i,h,c]         rf_gemm: the forward's att . V call on the transposed
+                                                                         16-bit map and d out^T
+            dq', dk = rf_dist_masked_attention_bwd(q, k, xyz, d att);   dq = scale dq'
+            dW_q, db_q = dq^T s, sum dq;   dW_k = dk^T s;   db_k = 0 exactly;   dW_v, db_v = dv^T m, sum dv     rf_conv_wgrad
+            d s = dq W_q + dk W_k (exact fp32, like the forward);   d m = dv W_v + g                           rf_gemm
+            d state, d msa and the two affines = LayerNorm backward                                          rf_layernorm_bwd
+        In the fp16 mode the feed-forward, ln_out and the value path each run on a copy of their incoming gradient at a
+        power-of-two scale of their own; d att is brought back to scale 1 in fp32 before the map's backward.  Every contraction of
+        the backward is pinned exact (exact=True, like the sibling modules' input gradients): under the fp32 mode's "high" matmul
+        precision the forward's value path follows it, the gradients stay on the exact fp32 kernel."""
+        xyz, state, msa = tape["xyz"], tape["state"], tape["msa"]
+        B, N, Lr, D = msa.shape
+        H, dq_ = self.n_heads, self.d_inner
+        dv = D // H
+        dev = msa.device
+        grads = {}
+        _pre_norm_residual_bwd(g, self.to_out.fn[1]._backward, tape["ff"], tape["x1"], self.to_out.fn[0], grads)
+        st, _, m_t, q, k, bins, att, out = self._attend(xyz, state, msa)
+        # ---- ln_out
+        s = _grad_scale([g])
+        dout, dgo, dbo = ops.layernorm_bwd(out, _scaled_copy(g, s), _f(self.ln_out.weight), eps=self.ln_out.eps)
+        del out
+        gr = {self.ln_out.weight: dgo, self.ln_out.bias: dbo}
+        _unscale([dout] + list(gr.values()), s)
+        grads.update(gr)
+        # ---- attention . V: d att and d v
+        s = _grad_scale([dout])
+        if s != 1.0:
+            ops.axpby(dout, s, None, 0.0, dout)
+        dout_t = ops.cast(dout, T())
+        v = ops.linear(m_t, self.wt("v", self.to_v), _f(self.to_v.bias), exact=True)   # the values row-major: [B,N,L,D] T
+        datt = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32)
+        ops.gemm(dout_t, v, datt, Lr, Lr, N * dv, batch=(B, H, 1), kc=dv,
+                 a_bs=(N * Lr * D, dv, 0), a_row=(0, 0, D), a_ko=Lr * D,
+                 b_bs=(N * Lr * D, dv, 0), b_row=(0, 0, D), b_ko=Lr * D,
+                 c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr), exact=True)
+        del v
+        _unscale([datt], s)
+        dout_tt = torch.empty(B, N, D, Lr, device=dev, dtype=att.dtype)   # d out key-contiguous, like the forward's v^T
+        ops.copy4d(dout_t, (N * Lr * D, Lr * D, 1, D), dout_tt, (N * D * Lr, D * Lr, Lr, 1), (B, N, D, Lr))
+        att_tr = torch.empty(B, H, Lr, Lr, device=dev, dtype=att.dtype)
+        ops.copy4d(att, (0, Lr * Lr, 1, Lr), att_tr, (0, Lr * Lr, Lr, 1), (1, B * H, Lr, Lr))
+        del att, dout, dout_t
+        dv_t = torch.empty(B, N, Lr, D, device=dev, dtype=att_tr.dtype)   # (fp32 where the map is: _map_dtype)
+        ops.gemm(att_tr, dout_tt, dv_t, Lr, N * dv, Lr, batch=(B, H, 1),
+                 a_bs=(H * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
+                 b_bs=(N * D * Lr, dv * Lr, 0), b_row=(dv, D * Lr, Lr),
+                 c_bs=(N * Lr * D, dv, 0), c_row=(0, 0, D), c_col=(dv, Lr * D), exact=True)
+        del att_tr, dout_tt
+        dv_t = ops.cast(dv_t, T())
+        # ---- value projection, the residual path, ln_msa
+        dwv, dbv = ops.conv_wgrad(dv_t, m_t, 1, bias=True)
+        dm = ops.linear(dv_t, self.wt_input_grad("v", self.to_v), None, out_dtype=F32, exact=True)
+        del dv_t, m_t
+        gr = {self.to_v.weight: dwv, self.to_v.bias: dbv}
+        _unscale([dm] + list(gr.values()), s)
+        grads.update(gr)
+        ops.axpby(dm, 1.0, g, 1.0, dm)
+        dmsa, grads[self.ln_msa.weight], grads[self.ln_msa.bias] = ops.layernorm_bwd(msa, dm, _f(self.ln_msa.weight),
+                                                                                     eps=self.ln_msa.eps)
+        del dm
+        # ---- the map, to_q / to_k, ln_state (fp32 throughout: no scale)
+        dq, dk, _ = ops.dist_masked_attention_bwd(q, k, xyz.contiguous(), bins, datt, B, Lr, H, dq_)
+        del datt
+        ops.axpby(dq, self.scale, None, 0.0, dq)
+        grads[self.to_q.weight], grads[self.to_q.bias] = ops.conv_wgrad(dq, st, 1, bias=True)
+        grads[self.to_k.weight], _ = ops.conv_wgrad(dk, st, 1)
+        grads[self.to_k.bias] = ops.zeros(H * dq_, device=dev, dtype=F32)
+        wqt = self.cached("wqt32", lambda: self.to_q.weight.detach().float().t().contiguous())
+        wkt = self.cached("wkt32", lambda: self.to_k.weight.detach().float().t().contiguous())
+        dst = ops.linear(dq, wqt, None, out_dtype=F32, exact=True)
+        ops.linear(dk, wkt, None, out=dst, residual=dst, exact=True)
+        dstate, grads[self.ln_state.weight], grads[self.ln_state.bias] = ops.layernorm_bwd(
+            state.contiguous(), dst, _f(self.ln_state.weight), eps=self.ln_state.eps)
+        return dstate, dmsa, grads
+
+    def _backward_children(self):
+        return (self.to_out.fn[1],)
+
+    def _record(self, xyz, state, msa, tape):
+        return self.run(xyz.float(), state.float(), msa.float().contiguous(), tape=tape)
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        dstate, dmsa, grads = self._backward(tape, _scaled_copy(gs[0], 1.0))
+        return (None, dstate.view(tape["state"].shape), dmsa), grads
+
     def forward(self, xyz, state, msa):
-        return self.run(xyz.float(), state.float(), msa.float().contiguous())
+        if _recording(self):
+            return _RecordedFn.apply(self, xyz, state, msa, *self.parameters())
+        return self._record(xyz, state, msa, None)
 
 
 # ================================================================================================
