@@ -688,6 +688,35 @@ int rf_poswise_bwd(const void* q0, int q0_dtype, int64_t q0_ld, const void* k, i
 int rf_dist_masked_attention_bwd(const float* q, const float* k, const float* xyz, const float* bins, const float* datt,
                                  float* dq, float* dk, float* ds_map, int B, int L, int H, int d, void* stream);
 
+/* ---- backward pass of SoftTiedAttentionOverResidues (csrc/backward.hip; model.py, rf.py:220-267) ---------------------------
+ * Backward of the tied attention's softmax and of its symmetrised map (rf_version >= 17).  Per (b, h, i), over the columns j:
+ *   p = softmax_j(logits[b,h,i,:]),   dp_j = dp[b,h,i,j] + (g_sym[b,i,j,h] + g_sym[b,j,i,h]) / 2,
+ *   ds[b,h,i,j] = p_j (dp_j - sum_l p_l dp_l)
+ * logits, dp (the value-path part of the probabilities' gradient) and ds: fp32 [B,H,L,L], contiguous; g_sym: fp32 [B,L,L,H],
+ * contiguous, the gradient of sym[b,i,j,h] = (p[b,h,i,j] + p[b,h,j,i]) / 2, or NULL (no second term).  p_h16 and ds_h16, each
+ * may be NULL: copies of p and of ds in the build's 16-bit type, [B,H,L,ld] with ld >= L elements between rows (ld a multiple of
+ * 8, else RF_EALIGN; ld is not read when both are NULL); their columns [L, ld) are written as zeros, the convention of
+ * rf_tied_softmax_ld, so that both are legal 16-bit rf_gemm operands with K = ld at any L.
+ * Nothing of the forward is saved but the fp32 logits: p is recomputed in fp32 with the row maximum subtracted; the normaliser
+ * and sum_l p_l dp_l are fp64 sums, each ds rounded once.  L == 1: ds = 0 exactly.  Any L >= 1 and any H >= 1; EVERY element
+ * of every output handed in is written (the pads included), nothing else is; no atomics: the same bits run to run.
+ * A block takes up to 16 query rows of one sample with all heads and stages the half-sum of g_sym for them in LDS (at most
+ * 64 KB; one row with all heads that does not fit, H * (L | 1) * 4 bytes > 64 KB, reads g_sym from memory instead).
+ * RF_EINVAL before any launch: logits, dp or ds NULL, a size <= 0, L * H >= 2^27, a 16-bit copy with ld < L. */
+int rf_tied_softmax_bwd(const float* logits, const float* dp, const float* g_sym, float* ds, void* p_h16, void* ds_h16, int64_t ld,
+                        int B, int H, int L, void* stream);
+/* Backward of rf_scale_rows with a factor, y[r,:] = alpha w[r] x[r,:] (rf_version >= 17), over rows r = (t, h), t < tokens,
+ * h < H, of D columns.  Row (t, h) of x starts at element t * x_ld + h * x_hs, and likewise for gy (the gradient of y) and dx;
+ * x, gy and dx are fp32 or the build's 16-bit type, each with its own dtype code; w and dw are fp32 [tokens * H], contiguous:
+ *   dx[r,:] = alpha w[r] gy[r,:]          dw[r] = alpha sum_c gy[r,c] x[r,c]      (an fp64 sum, rounded once)
+ * So the q block of a [.., 3 D] projection buffer is walked in place with ld = 3 D, hs = d_head, D = d_head, as rf_poswise does.
+ * dx or dw may be NULL (not both); dx may be gy itself (same dtype and strides).  EVERY addressed element of dx and every
+ * element of dw is written, nothing else is; no atomics: the same bits run to run.
+ * RF_EINVAL before any launch: x, gy or w NULL, dx and dw both NULL, a size <= 0, a negative stride, tokens * H >= 2^34. */
+int rf_scale_rows_bwd(const void* x, int x_dtype, int64_t x_ld, int64_t x_hs, const void* gy, int gy_dtype, int64_t gy_ld,
+                      int64_t gy_hs, const float* w, float alpha, void* dx, int dx_dtype, int64_t dx_ld, int64_t dx_hs, float* dw,
+                      int64_t tokens, int H, int D, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

@@ -123,6 +123,8 @@ PROTOTYPES = {
     "rf_poswise_bwd": [vp, i32, i64, vp, i32, i64, i32, i32, i32, vp, vp, i64, vp, vp, i32, i64, i32, i32, i32, i32, i32, i32, f32,
                        f32, u64, u64, vp],
     "rf_dist_masked_attention_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "rf_tied_softmax_bwd": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "rf_scale_rows_bwd": [vp, i32, i64, i64, vp, i32, i64, i64, vp, f32, vp, i32, i64, i64, vp, i64, i32, i32, vp],
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],

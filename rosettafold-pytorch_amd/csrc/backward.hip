@@ -1366,3 +1366,170 @@ extern "C" int rf_dist_masked_attention_bwd(const float* q, const float* k, cons
   hipLaunchKernelGGL(dist_att_bwd_cols_kernel, dim3(B * L), dim3(256), 0, s, ds_map, q, dk, L, H, d);
   return rf_launch_status();
 }
+
+// ================================================================================================
+// rf_tied_softmax_bwd: backward of the tied attention's softmax and of its symmetrised map (ops.hip: softmax_kernel and
+// att_sym_kernel; rf.py:255, 261-265).  Per (b, h, i), over the columns j:
+//   p = softmax_j(logits),   dp_j = dp[b,h,i,j] + (g_sym[b,i,j,h] + g_sym[b,j,i,h]) / 2,   ds_j = p_j (dp_j - sum_l p_l dp_l)
+// A block takes TI query rows i of one sample and ALL heads.  g_sym[b,i,:,:] is then one contiguous run of L * H floats per row,
+// and the column gather g_sym[b,j,i0:i0+TI,:] is a run of TI * H floats per j (a lone row would read H floats at a stride of
+// L * H): phase A stages the half-sum of both in LDS as [ii][h][j], rows padded to an odd length so that the h-fastest writes
+// and the j-fastest reads are both free of bank conflicts.  TI is the largest of 16, 8, 4, 2, 1 whose stage fits 64 KB; a
+// shape whose single row does not fit (H * L > 16128) reads g_sym from memory in phase B instead (SYM_LDS = false).
+// Phase B, a wave per (ii, h) row: the maximum, then the normaliser and sum p dp in fp64 (as in dist_att_bwd_kernel), then
+// ds; the logits are read three times and dp twice, the repeats from cache.  No atomics, a fixed order: the same bits run to run.
+// ================================================================================================
+static inline int tsb_row_ld(int L) { return L | 1; }
+
+template <bool SYM_LDS>
+__global__ __launch_bounds__(256) void tied_softmax_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ dp,
+                                                               const float* __restrict__ g_sym, float* __restrict__ ds,
+                                                               h16_t* __restrict__ p16, h16_t* __restrict__ ds16, int64_t ld,
+                                                               int H, int L, int TI, int tiles) {
+  extern __shared__ float tsb_sm[];  // [TI][H][L | 1]: the symmetrised map's half-sum (SYM_LDS with g_sym only)
+  const int b = blockIdx.x / tiles, i0 = (blockIdx.x - b * tiles) * TI;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int nrow = min(TI, L - i0);
+  const int Lo = L | 1;
+  const int64_t LH = (int64_t)L * H;
+  const float* gb = g_sym ? g_sym + (int64_t)b * L * LH : nullptr;
+  if (SYM_LDS && gb) {
+    // ---- phase A.  The row term: element e = (j, h) of row i0 + ii, contiguous in memory.
+    for (int ii = 0; ii < nrow; ++ii) {
+      const float* src = gb + (int64_t)(i0 + ii) * LH;
+      float* dst = tsb_sm + (int64_t)ii * H * Lo;
+      for (int e = t; e < L * H; e += 256) {
+        const int j = e / H, h = e - j * H;
+        dst[h * Lo + j] = src[e];
+      }
+    }
+    __syncthreads();
+    // The column term: element e = (j, ii, h), a run of nrow * H floats per j.  Each LDS word is touched by one thread.
+    const int run = nrow * H;
+    for (int e = t; e < L * run; e += 256) {
+      const int j = e / run, r = e - j * run, ii = r / H, h = r - ii * H;
+      float* d = tsb_sm + ((int64_t)ii * H + h) * Lo + j;
+      *d = 0.5f * (*d + gb[(int64_t)j * LH + (int64_t)i0 * H + r]);
+    }
+    __syncthreads();
+  }
+  // ---- phase B (a lane takes the entries j = lane + 64 m)
+  for (int r = wv; r < nrow * H; r += 4) {
+    const int ii = r / H, h = r - ii * H, i = i0 + ii;
+    const int64_t row = (((int64_t)b * H + h) * L + i) * L;  // element [b, h, i, 0] of logits, dp and ds
+    const float* lg = logits + row;
+    const float* dr = dp + row;
+    const float* sy = tsb_sm + (int64_t)r * Lo;
+    auto dp_at = [&](int j) -> float {
+      if (!gb) return dr[j];
+      if (SYM_LDS) return dr[j] + sy[j];
+      return dr[j] + 0.5f * (gb[((int64_t)i * L + j) * H + h] + gb[((int64_t)j * L + i) * H + h]);
+    };
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, lg[j]);
+    mx = wave_max(mx);
+    double s = 0.0, dot = 0.0;
+    for (int j = lane; j < L; j += 64) {
+      const double ex = (double)expf(lg[j] - mx);
+      s += ex;
+      dot = fma(ex, (double)dp_at(j), dot);
+    }
+    const double inv = 1.0 / wave_sum_f64(s);
+    dot = wave_sum_f64(dot) * inv;
+    const int64_t row16 = (((int64_t)b * H + h) * L + i) * ld;
+    for (int j = lane; j < L; j += 64) {
+      const double p = (double)expf(lg[j] - mx) * inv;
+      const float dsv = (float)(p * ((double)dp_at(j) - dot));
+      ds[row + j] = dsv;
+      if (p16) p16[row16 + j] = f2h((float)p);
+      if (ds16) ds16[row16 + j] = f2h(dsv);
+    }
+    for (int64_t j = L + lane; j < ld; j += 64) {  // the pad columns of the 16-bit copies
+      if (p16) p16[row16 + j] = 0;
+      if (ds16) ds16[row16 + j] = 0;
+    }
+  }
+}
+
+// include/rfmi.h: rf_tied_softmax_bwd
+extern "C" int rf_tied_softmax_bwd(const float* logits, const float* dp, const float* g_sym, float* ds, void* p_h16, void* ds_h16,
+                                   int64_t ld, int B, int H, int L, void* stream) {
+  if (!logits || !dp || !ds || B <= 0 || H <= 0 || L <= 0) return RF_EINVAL;
+  if ((int64_t)L * H > 0x7fffffff / 16) return RF_EINVAL;
+  if (p_h16 || ds_h16) {
+    if (ld < L) return RF_EINVAL;
+    if (ld % 8) return RF_EALIGN;
+  }
+  const int64_t row_bytes = (int64_t)H * tsb_row_ld(L) * sizeof(float);
+  int TI = 16;
+  while (TI > 1 && TI * row_bytes > 64 * 1024) TI >>= 1;
+  if (!g_sym) TI = L >= 256 ? 4 : 16;  // nothing is staged: rows per block for the launch shape only
+  const bool stage = g_sym && TI * row_bytes <= 64 * 1024;
+  const int tiles = (L + TI - 1) / TI;
+  if ((int64_t)B * tiles > 0x7fffffff) return RF_EINVAL;
+  const size_t lds = stage ? (size_t)(TI * row_bytes) : 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (stage)
+    hipLaunchKernelGGL(tied_softmax_bwd_kernel<true>, dim3(B * tiles), dim3(256), lds, s, logits, dp, g_sym, ds, (h16_t*)p_h16,
+                       (h16_t*)ds_h16, ld, H, L, TI, tiles);
+  else
+    hipLaunchKernelGGL(tied_softmax_bwd_kernel<false>, dim3(B * tiles), dim3(256), 0, s, logits, dp, g_sym, ds, (h16_t*)p_h16,
+                       (h16_t*)ds_h16, ld, H, L, TI, tiles);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_scale_rows_bwd: backward of rf_scale_rows (y[r, :] = alpha w[r] x[r, :]) over rows r = (t, h) of D columns: row (t, h)
+// of a tensor starts at t * ld + h * hs, w and dw hold one fp32 per row, contiguous.
+//   dx[r, :] = alpha w[r] gy[r, :]      dw[r] = alpha sum_c gy[r, c] x[r, c]
+// G lanes share a row (G = 8, 16 or 32 by D); the sum runs in fp64 and meets in a shuffle butterfly: a fixed order, no atomics.
+// ================================================================================================
+template <int G>
+__global__ __launch_bounds__(256) void scale_rows_bwd_kernel(const void* x, int x_dt, int64_t x_ld, int64_t x_hs, const void* gy,
+                                                             int gy_dt, int64_t gy_ld, int64_t gy_hs, const float* __restrict__ w,
+                                                             float alpha, void* dx, int dx_dt, int64_t dx_ld, int64_t dx_hs,
+                                                             float* __restrict__ dw, int64_t rows, int H, int D) {
+  const int64_t r = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+  const int cl = threadIdx.x % G;
+  const bool ok = r < rows;  // (no early return: the shuffles below run with every lane)
+  double a = 0.0;
+  if (ok) {
+    const int64_t tk = r / H;
+    const int h = (int)(r - tk * H);
+    const int64_t xo = tk * x_ld + h * x_hs, go = tk * gy_ld + h * gy_hs, dxo = tk * dx_ld + h * dx_hs;
+    const double aw = (double)alpha * (double)w[r];
+    for (int c = cl; c < D; c += G) {
+      const float g = ld(gy, gy_dt, go + c);
+      a = fma((double)g, (double)ld(x, x_dt, xo + c), a);
+      if (dx) st(dx, dx_dt, dxo + c, (float)(aw * (double)g));
+    }
+  }
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  if (ok && cl == 0 && dw) dw[r] = (float)((double)alpha * a);
+}
+
+// include/rfmi.h: rf_scale_rows_bwd
+extern "C" int rf_scale_rows_bwd(const void* x, int x_dtype, int64_t x_ld, int64_t x_hs, const void* gy, int gy_dtype, int64_t gy_ld,
+                                 int64_t gy_hs, const float* w, float alpha, void* dx, int dx_dtype, int64_t dx_ld, int64_t dx_hs,
+                                 float* dw, int64_t tokens, int H, int D, void* stream) {
+  RF_CHECK_DT(x_dtype);
+  RF_CHECK_DT(gy_dtype);
+  if (dx) RF_CHECK_DT(dx_dtype);
+  if (!x || !gy || !w || (!dx && !dw) || tokens <= 0 || H <= 0 || D <= 0) return RF_EINVAL;
+  if (x_ld < 0 || x_hs < 0 || gy_ld < 0 || gy_hs < 0 || dx_ld < 0 || dx_hs < 0) return RF_EINVAL;
+  if (tokens > (int64_t)0x7fffffff * 8 / H) return RF_EINVAL;
+  const int64_t rows = tokens * H;
+  hipStream_t s = (hipStream_t)stream;
+#define SRB_LAUNCH(G_)                                                                                                            \
+  hipLaunchKernelGGL(scale_rows_bwd_kernel<G_>, dim3(cdiv(rows, 256 / G_)), dim3(256), 0, s, x, x_dtype, x_ld, x_hs, gy, gy_dtype, \
+                     gy_ld, gy_hs, w, alpha, dx, dx_dtype, dx_ld, dx_hs, dw, rows, H, D)
+  if (D >= 32)
+    SRB_LAUNCH(32);
+  else if (D >= 16)
+    SRB_LAUNCH(16);
+  else
+    SRB_LAUNCH(8);
+#undef SRB_LAUNCH
+  return rf_launch_status();
+}

@@ -561,7 +561,8 @@ class PositionWiseWeightFactor(RecordingModule):
     (include/rfmi.h); in train() mode the backward replays the dropout on the softmax weights.  to_k's bias moves every logit of a
     softmax by the same amount: its gradient is the sum of terms that cancel, zero up to their rounding.  d_msa must be a multiple
     of 8 while recording.  The attention layers and the structure track call weights() / weights_head_major() /
-    weights_collapsed() without a tape: RoseTTAFold.forward never records here."""
+    weights_collapsed() without a tape: RoseTTAFold.forward never records here.  (A recording SoftTiedAttentionOverResidues
+    hands weights_head_major() / drop() a dict for the dropout record alone and composes _backward itself.)"""
 
     def __init__(self, d_msa=384, n_heads=12, p_dropout=0.1):
         super().__init__()
@@ -629,10 +630,11 @@ class PositionWiseWeightFactor(RecordingModule):
             ops.axpby(dx[b, 0], 1.0, dx0[b], 1.0, dx[b, 0])
         return dx, grads
 
-    def weights_head_major(self, xn):
+    def weights_head_major(self, xn, tape=None):
         """xn: T [B,N,L,d] -> w fp32 [B,H,N,L], without the to_k projection over the N rows: per head
         u[b,l,h,:] = W_k[h*dh:(h+1)*dh, :]^T to_q(x_0)[b,l,h*dh:(h+1)*dh], w = softmax_n(scale * xn . u)   (rf.py:205-217,
-        collapsed; to_k's bias is constant over n and drops out of the softmax)."""
+        collapsed; to_k's bias is constant over n and drops out of the softmax).  tape: receives the dropout's record (drop()):
+        the mask was drawn over THIS layout, [B,H,N,L]."""
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
         q0 = self.query_proj(xn)
@@ -640,7 +642,7 @@ class PositionWiseWeightFactor(RecordingModule):
         u = torch.empty(B, Lr, H, D, device=xn.device, dtype=T())
         ops.gemm(q0, wkt, u, B * Lr, D, dh, batch=(H, 1, 1), a_bs=(dh, 0, 0), a_row=(0, 0, D), b_bs=(dh, 0, 0),
                  b_row=(0, 0, D), c_bs=(D, 0, 0), c_row=(0, 0, H * D))
-        return self.drop(ops.poswise_collapsed(xn, u, self.scale))
+        return self.drop(ops.poswise_collapsed(xn, u, self.scale), tape)
 
     def weights_collapsed(self, msa, lnm, m, tape=None):
         """1-head weights for the structure track, q side in fp32: w = softmax_n(scale * m[b,n,l,:] . u[b,l,:]) with
@@ -676,8 +678,14 @@ class PositionWiseWeightFactor(RecordingModule):
 TIED_RAGGED_MIN_L = 40
 
 
-class SoftTiedAttentionOverResidues(RFModule):
-    """rf.py:220-267."""
+class SoftTiedAttentionOverResidues(RecordingModule):
+    """rf.py:220-267.  enable_backward() (switches `poswise_weight` along): with grad mode on, forward(x) records -- on whichever
+    route the shape takes -- and loss.backward() fills the .grad of every parameter and of x where it requires grad; with
+    return_att both outputs take part in autograd and either gradient may be missing.  The backward (_backward) rebuilds its
+    operands from the saved input on the general route and differentiates the unconditioned function: value_conditioning is an
+    identity for any constant.  to_k.bias and poswise_weight.to_k.bias get exact zeros: each adds a constant to every logit of
+    a softmax row.  d_msa and d_msa / n_heads must be multiples of 8 while recording.  EncoderLayer.run and everything above it
+    call attend() without a tape: they never record here."""
 
     def __init__(self, d_msa=384, n_heads=12, p_dropout=0.1, return_att=False):
         super().__init__()
@@ -693,28 +701,36 @@ class SoftTiedAttentionOverResidues(RFModule):
         self.to_v = Linear(d_msa, d_msa)
         self.to_out = Linear(d_msa, d_msa)
 
-    def attend(self, xn, x_res, want_att, next_ln=None, drops=()):
+    def attend(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
         """xn: T [B,N,L,D] (already layer-normed); x_res: fp32 [B,N,L,D] += to_out(attention).  Returns
         (symmetrised attention map fp32 [B,L,L,H] when want_att, next_ln(x_res) when fused else None).
         Training mode: the position weights are dropped out inside (rf.py:217); `drops` = the dropouts on the projected output
-        before the residual add (this module's own, rf.py:265-267, and the wrapping EncoderLayer's, rf.py:346)."""
+        before the residual add (this module's own, rf.py:265-267, and the wrapping EncoderLayer's, rf.py:346).
+        tape: a dict that receives what _backward needs -- xn, the output dropouts' records ("drops"), the position weights'
+        dropout record ("pw") and the layout its mask was drawn over ("w_order": "bhnl" on the head-major and long-row routes,
+        "bnhl" on the general one) -- while the route the shape takes runs unchanged: same kernels, same numbers."""
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
         dev = xn.device
         pw = self.poswise_weight
+        _check_backward_call(self, tape, None, D, dh)
+        if tape is not None:
+            tape.update(xn=xn, drops=[], pw={"drop": None}, w_order="bhnl")
         if (RT.fused_tied and RT.tied_v2 and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256) and H <= 16
                 and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16) and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384
                 and (6 if Lr >= 256 else 8) * (4096 + Lr * 64) + 1024 + N * 256 <= 160 * 1024):
-            return self.attend_head_major(xn, x_res, want_att, next_ln, drops)
+            return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
         if (RT.fused_tied and RT.tied_v2 and Lr not in ops.TIED_TILES and Lr >= TIED_RAGGED_MIN_L
                 and ops.tied_fused_applies(Lr, N, T(), dh, w=not self.folds_weights(B * N * Lr)) and H <= 16
                 and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)):
             # a chain that fills no tile: the same route on the tail instantiations of the kernels (rf_tied_attention_ld)
-            return self.attend_head_major(xn, x_res, want_att, next_ln, drops)
+            return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
         if (RT.fused_tied and RT.tied_v2 and RT.tied_fold_w and ops.is_h16(T()) and dh == 32 and Lr in (512, 768, 1024) and H <= 16
                 and ops.gemm_takes_row_scale(B * N * Lr, 2 * D, D) and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)
                 and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384):
-            return self.attend_long_rows(xn, x_res, want_att, next_ln, drops)
+            return self.attend_long_rows(xn, x_res, want_att, next_ln, drops, tape)
+        if tape is not None:
+            tape["w_order"] = "bnhl"
         # one GEMM for q | k | poswise-k  (N = 3D)
         wcat = self.wcat("qkp", [self.to_q, self.to_k, pw.to_k[0]])
         bcat = self.bcat("qkp", [self.to_q, self.to_k, pw.to_k[0]])
@@ -725,7 +741,7 @@ class SoftTiedAttentionOverResidues(RFModule):
             # training mode: the weights exist as a tensor so that the dropout can sit between the softmax and the scaling
             w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
             ops.poswise(q0, D, qkp, 3 * D, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
-            pw.drop(w)
+            pw.drop(w, tape["pw"] if tape is not None else None)
             wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
                             (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))
             ops.axpby(wl, self.scale, None, 0.0, wl)
@@ -755,7 +771,8 @@ class SoftTiedAttentionOverResidues(RFModule):
                      c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr))
             ops.tied_softmax(logits, att, att_sym, H)
         out = self.attention_values(att, v_t)
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
+                                        recs=tape["drops"] if tape is not None else None)
         return att_sym, xn_next
 
     def folds_weights(self, rows):
@@ -777,7 +794,7 @@ class SoftTiedAttentionOverResidues(RFModule):
                  c_bs=(N * Lr * D, dh, 0), c_row=(0, 0, D), c_col=(dh, Lr * D))
         return out
 
-    def attend_head_major(self, xn, x_res, want_att, next_ln=None, drops=()):
+    def attend_head_major(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
         """The bench path (csrc/tied.hip): one projection GEMM writes q|k|v head-major [B,N,3H,L,32] (every contraction
         step of the attention kernels is then one contiguous tile), the position weights come from the collapsed form
         (no to_k projection over the N rows) and are applied inside the logits kernel, attention.V consumes v with
@@ -787,7 +804,7 @@ class SoftTiedAttentionOverResidues(RFModule):
         dev = xn.device
         G = 3 * H
         lins = [self.to_q, self.to_k, self.to_v]
-        w = self.poswise_weight.weights_head_major(xn)  # fp32 [B,H,N,L]
+        w = self.poswise_weight.weights_head_major(xn, tape["pw"] if tape is not None else None)  # fp32 [B,H,N,L]
         ragged = Lr not in ops.TIED_TILES
         qkv = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
         # q * w * d_head^-0.5 (rf.py:252) in the projection's epilogue, on the fp32 accumulators: q is rounded once, after
@@ -811,10 +828,11 @@ class SoftTiedAttentionOverResidues(RFModule):
         out = torch.empty(B, N, Lr, D, device=dev, dtype=T())
         ops.tied_attention(qkv[:, :, 0:H], qkv[:, :, H:2 * H], qkv[:, :, 2 * H:], out.view(B, N, Lr, H, dh).permute(0, 1, 3, 2, 4),
                            att, w=None if fold else w, qscale=1.0 if fold else self.scale, att_sym=att_sym)
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
+                                        recs=tape["drops"] if tape is not None else None)
         return att_sym, xn_next
 
-    def attend_long_rows(self, xn, x_res, want_att, next_ln=None, drops=()):
+    def attend_long_rows(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
         """L in {512, 768, 1024} (BASELINE.json configs[3]).  Same front as attend_head_major -- collapsed position weights, one
         projection GEMM writing q|k head-major with w * d_head^-0.5 folded into q on the fp32 accumulators -- then the
         contraction-split logits kernel over 128-query x 256-key tiles (csrc/tied.hip: rf_tied_logits).  attention . V at
@@ -824,7 +842,7 @@ class SoftTiedAttentionOverResidues(RFModule):
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
         dev = xn.device
-        w = self.poswise_weight.weights_head_major(xn)  # fp32 [B,H,N,L]
+        w = self.poswise_weight.weights_head_major(xn, tape["pw"] if tape is not None else None)  # fp32 [B,H,N,L]
         G = 2 * H
         lins = [self.to_q, self.to_k]
         qk = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
@@ -837,14 +855,136 @@ class SoftTiedAttentionOverResidues(RFModule):
         if RT.condition and RT.condition_values:
             bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))
         out = self.attention_values(att, self.values_transposed(self.to_v, xn, bv))
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops)
+        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
+                                        recs=tape["drops"] if tape is not None else None)
         return att_sym, xn_next
 
-    def forward(self, x):
+    def _replay_weight_dropout(self, t, tape):
+        """t: fp32 [B,N,H,L], the position weights or their gradient (in place): times the forward's keep / (1 - p).  The Philox
+        mask follows the element offset, so it is replayed over the layout the forward dropped the weights in (tape["w_order"])."""
+        rec = tape["pw"]["drop"]
+        if rec is None:
+            return t
+        if tape["w_order"] == "bnhl":
+            return _replay_dropout(t, rec)
+        B, N, H, Lr = t.shape
+        hm = ops.copy4d(t, (N * H * Lr, Lr, H * Lr, 1), torch.empty(B, H, N, Lr, device=t.device, dtype=F32),
+                        (H * N * Lr, N * Lr, Lr, 1), (B, H, N, Lr))
+        _replay_dropout(hm, rec)
+        return ops.copy4d(hm, (H * N * Lr, N * Lr, Lr, 1), t, (N * H * Lr, Lr, H * Lr, 1), (B, H, N, Lr))
+
+    def _backward(self, tape, g, g_sym=None):
+        """g: contiguous fp32 [B,N,L,D], the gradient of what attend() added to x_res (overwritten); g_sym: contiguous fp32
+        [B,L,L,H], the gradient of the symmetrised map, or None.  Returns (fp32 d xn [B,N,L,D], {param: grad}).  q | k |
+        poswise-k, the (dropped) position weights w, q~ = q w d_head^-0.5, v, v^T and the fp32 logits are rebuilt from the saved
+        xn on the general route, whichever route the forward took, with the plain biases.  Then, with s = d_head^-0.5:
+            dW_o, db_o = g^T o, sum g;   do = g W_o                                rf_conv_wgrad, rf_gemm
+            dp = sum_{n,d} do v                                                     rf_gemm, K = N * d_head in chunks of d_head
+            ds = p (dp + sym(g_sym) - sum p (dp + sym(g_sym)))                      rf_tied_softmax_bwd (p, ds also 16-bit)
+            dv = p^T do;   dq~ = ds k;   dk = ds^T q~                               rf_gemm over the chain (map_ld, zero pads)
+            dq = s w dq~;   dw = s sum_d dq~ q                                      rf_scale_rows_bwd
+            d xn_pw, grads = poswise_weight._backward(dw, the mask replayed)        rf_poswise_bwd
+            dW_{q,k,v}, db_{q,v} = [dq | dk | dv]^T xn;   db_k = 0 exactly          rf_conv_wgrad
+            d xn = [dq | dk | dv] [W_q; W_k; W_v] + d xn_pw                         rf_gemm, exact fp32"""
+        xn = tape["xn"]
+        B, N, Lr, D = xn.shape
+        H, dh = self.n_heads, self.d_head
+        dev = xn.device
+        pw = self.poswise_weight
+        W3, Lp, R = 3 * D, map_ld(Lr), B * N * Lr
+        h16 = ops.is_h16(T())
+        for rec in tape["drops"]:
+            _replay_dropout(g, rec)
+        g_t = ops.cast(g.view(R, D), T())
+
+        # ---- the forward's operands, general route
+        lins = [self.to_q, self.to_k, pw.to_k[0]]
+        qkp = ops.linear(xn, self.wcat("qkp", lins), self.bcat("qkp", lins))   # [B,N,L,3D]: q | k | poswise-k
+        w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
+        ops.poswise(pw.query_proj(xn), D, qkp, W3, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
+        self._replay_weight_dropout(w, tape)
+        wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
+                        (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))                # the weights per (token, head)
+        del w
+        qt = ops.copy4d(qkp, (N * Lr * W3, Lr * W3, W3, 1), torch.empty(B, N, Lr, D, device=dev, dtype=T()),
+                        (N * Lr * D, Lr * D, D, 1), (B, N, Lr, D))
+        ops.scale_rows(qt, ops.axpby(wl, self.scale, None, 0.0, torch.empty_like(wl)), R * H, dh, out=qt)   # q~
+        logits = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32)
+        tied_k = dict(batch=(B, H, 1), kc=dh, c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr))   # a contraction over N * dh
+        rows_d = lambda ld_: dict(bs=(N * Lr * ld_, dh, 0), row=(0, 0, ld_), ko=Lr * ld_)   # noqa: E731  (head h of [B,N,L,ld_])
+        a_d, b_w3 = ({f"a_{k_}": v_ for k_, v_ in rows_d(D).items()}, {f"b_{k_}": v_ for k_, v_ in rows_d(W3).items()})
+        ops.gemm(qt, qkp, logits, Lr, Lr, N * dh, b_off=D, **a_d, **b_w3, **tied_k)
+        v = ops.linear(xn, self.wt("v", self.to_v), _f(self.to_v.bias))          # the values row-major [B,N,L,D]
+
+        def key_contiguous(src, ld_, off=0):
+            """[B,N,L,(h,d)] rows of ld_ -> [B,N,D,Lp]: the B operand of a contraction over the chain (zero pads)"""
+            dst = (torch.empty if Lp == Lr else ops.zeros)(B, N, D, Lp, device=dev, dtype=T())
+            return ops.copy4d(src, (N * Lr * ld_, Lr * ld_, 1, ld_), dst, (N * D * Lp, D * Lp, Lp, 1), (B, N, D, Lr), x_off=off)
+
+        def map_transposed(m):
+            """[B,H,L,Lp] -> the same with rows and columns swapped (zero pads)"""
+            dst = (torch.empty if Lp == Lr else ops.zeros)(B, H, Lr, Lp, device=dev, dtype=m.dtype)
+            return ops.copy4d(m, (0, Lr * Lp, 1, Lp), dst, (0, Lr * Lp, Lp, 1), (1, B * H, Lr, Lr))
+
+        def over_chain(m, bt, out, ld_, off):
+            """out[b,n,i,off + (h,d)] = sum_j m[b,h,i,j] bt[b,n,(h,d),j]: attention_values into rows of ld_"""
+            return ops.gemm(m, bt, out, Lr, N * dh, Lp, batch=(B, H, 1), c_off=off, exact=True,
+                            a_bs=(H * Lr * Lp, Lr * Lp, 0), a_row=(0, 0, Lp),
+                            b_bs=(N * D * Lp, dh * Lp, 0), b_row=(dh, D * Lp, Lp),
+                            c_bs=(N * Lr * ld_, dh, 0), c_row=(0, 0, ld_), c_col=(dh, Lr * ld_))
+
+        # ---- output projection, d p, the softmax and the symmetrised map
+        do = ops.linear(g_t, self.wt_input_grad("o", self.to_out), None, exact=True).view(B, N, Lr, D)
+        dp = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32)
+        ops.gemm(do, v, dp, Lr, Lr, N * dh, exact=True, **a_d, **{f"b_{k_}": v_ for k_, v_ in rows_d(D).items()}, **tied_k)
+        ds, p, ds_t = ops.tied_softmax_bwd(logits, dp, g_sym, h16_copies=h16)
+        if not h16:
+            p, ds_t = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32), ds
+            ops.tied_softmax(logits, p)
+        del logits, dp
+        grads = {}
+        o = over_chain(p, key_contiguous(v, D), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
+        grads[self.to_out.weight], grads[self.to_out.bias] = ops.conv_wgrad(g_t, o.view(R, D), 1, bias=True)
+        del o, v, g_t
+        # ---- dq~, then dq | dk | dv in the layout of a q | k | v projection
+        dqt = over_chain(ds_t, key_contiguous(qkp, W3, D), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
+        dqkv = torch.empty(B, N, Lr, W3, device=dev, dtype=T())
+        over_chain(map_transposed(ds_t), key_contiguous(qt, D), dqkv, W3, D)
+        over_chain(map_transposed(p), key_contiguous(do, D), dqkv, W3, 2 * D)
+        del ds, ds_t, p, do, qt
+        _, dwl = ops.scale_rows_bwd(qkp, W3, dh, dqt, D, dh, wl.view(-1), self.scale, R, H, dh, dx=dqkv, dx_ld=W3, dx_hs=dh)
+        del dqt, qkp, wl
+        # ---- the position weights
+        dw = ops.copy4d(dwl.view(B, N, Lr, H), (N * Lr * H, Lr * H, H, 1), torch.empty(B, N, H, Lr, device=dev, dtype=F32),
+                        (N * H * Lr, H * Lr, 1, Lr), (B, N, Lr, H))
+        self._replay_weight_dropout(dw, tape)
+        dxn, gpw = pw._backward({"xn": xn, "drop": None}, dw)
+        gpw[pw.to_k[0].bias] = ops.zeros(D, device=dev, dtype=F32)
+        grads.update(gpw)
+        # ---- the three projections
+        dwqkv, dbqkv = ops.conv_wgrad(dqkv.view(R, W3), xn.view(R, D), 1, bias=True)
+        for i, lin in enumerate((self.to_q, self.to_k, self.to_v)):
+            grads[lin.weight], grads[lin.bias] = dwqkv[i * D:(i + 1) * D], dbqkv[i * D:(i + 1) * D]
+        grads[self.to_k.bias] = ops.zeros(D, device=dev, dtype=F32)
+        wqkv_t = self.cached(("wqkv_input_grad",), lambda: torch.cat([lin.weight.detach() for lin in (self.to_q, self.to_k, self.to_v)],
+                                                                     0).t().to(T()).contiguous())
+        ops.linear(dqkv.view(R, W3), wqkv_t, None, out=dxn.view(R, D), residual=dxn.view(R, D), exact=True)
+        return dxn, grads
+
+    def _backward_children(self):
+        return (self.poswise_weight,)
+
+    def _record(self, x, tape):
         xn = ops.cast(x.contiguous(), T())
         out = ops.zeros(*x.shape, device=x.device, dtype=F32)
-        att, _ = self.attend(xn, out, self.return_att, drops=(self.p_dropout,) if self.training else ())
+        att, _ = self.attend(xn, out, self.return_att, drops=(self.p_dropout,) if self.training else (), tape=tape)
         return (out, att) if self.return_att else out
+
+    def _backward_from_autograd(self, tape, gs, s, want_dx):
+        g_sym = _scaled_copy(gs[1], s) if len(gs) > 1 and gs[1] is not None else None
+        dx, grads = self._backward(tape, _scaled_copy(gs[0], s), g_sym)
+        _unscale([dx], s)
+        return dx, grads
 
 
 # ================================================================================================

@@ -714,6 +714,56 @@ def poswise_bwd(q0, q0_ld, k, k_ld, k_col0, k_hs, dlen, B, N, L_, H, scale, *, d
     return dq0, dk
 
 
+def tied_softmax_bwd(logits, dp, g_sym=None, h16_copies=False):
+    """Backward of tied_softmax and of its symmetrised map (rf_tied_softmax_bwd): logits and dp (the value-path part of the
+    probabilities' gradient) contiguous fp32 [B, H, L, L]; g_sym contiguous fp32 [B, L, L, H], the gradient of the symmetrised
+    map, or None.  Returns (ds fp32 [B, H, L, L], p, ds16): with h16_copies the probabilities and ds in the active library's
+    16-bit type, [B, H, L, tied_ld(L)] with zeros in the pad columns (16-bit GEMM operands at any L); else (ds, None, None)."""
+    _need_cuda(logits, dp, g_sym)
+    if logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
+        raise ValueError("tied_softmax_bwd: logits [B, H, L, L]")
+    B, H, L_, _ = logits.shape
+    for t_ in (logits, dp):
+        if t_.dtype != F32 or tuple(t_.shape) != (B, H, L_, L_) or not t_.is_contiguous():
+            raise ValueError(f"tied_softmax_bwd: contiguous fp32 logits and dp [{B}, {H}, {L_}, {L_}]")
+    if g_sym is not None and (g_sym.dtype != F32 or tuple(g_sym.shape) != (B, L_, L_, H) or not g_sym.is_contiguous()):
+        raise ValueError(f"tied_softmax_bwd: contiguous fp32 g_sym [{B}, {L_}, {L_}, {H}]")
+    ds = torch.empty(B, H, L_, L_, device=logits.device, dtype=F32)
+    ld_ = tied_ld(L_)
+    p16 = torch.empty(B, H, L_, ld_, device=logits.device, dtype=h16()) if h16_copies else None
+    ds16 = torch.empty(B, H, L_, ld_, device=logits.device, dtype=h16()) if h16_copies else None
+    check(lib.rf_tied_softmax_bwd(ptr(logits), ptr(dp), ptr(g_sym), ptr(ds), ptr(p16), ptr(ds16), ld_, B, H, L_, stream()),
+          "rf_tied_softmax_bwd")
+    return ds, p16, ds16
+
+
+def scale_rows_bwd(x, x_ld, x_hs, gy, gy_ld, gy_hs, w, alpha, tokens, H, D, *, dx=None, dx_ld=None, dx_hs=None, dx_dtype=None,
+                   want_dw=True, x_off=0, gy_off=0, dx_off=0):
+    """Backward of y[r, :] = alpha * w[r] * x[r, :] (rf_scale_rows_bwd) over rows r = (t, h), t < tokens, h < H, of D columns:
+    row (t, h) of x starts at element x_off + t * x_ld + h * x_hs, likewise gy (the gradient of y) and dx; w contiguous fp32
+    [tokens * H].  Returns (dx = alpha * w * gy: the given tensor, or a new contiguous [tokens, H * D] of dx_dtype (default:
+    gy's), fp32 dw [tokens * H] = alpha * sum_c gy * x, or None)."""
+    _need_cuda(x, gy, w, dx)
+    if min(tokens, H, D) <= 0 or min(x_ld, x_hs, gy_ld, gy_hs, x_off, gy_off, dx_off) < 0:
+        raise ValueError("scale_rows_bwd: sizes must be positive, offsets and strides non-negative")
+    if dx is None:
+        dx = torch.empty(tokens, H * D, device=gy.device, dtype=dx_dtype or gy.dtype)
+        dx_ld, dx_hs, dx_off = H * D, D, 0
+    elif dx_ld is None or dx_hs is None or min(dx_ld, dx_hs) < 0:
+        raise ValueError("scale_rows_bwd: a given dx needs dx_ld and dx_hs")
+    for name, t_, off, ld_, hs in (("x", x, x_off, x_ld, x_hs), ("gy", gy, gy_off, gy_ld, gy_hs), ("dx", dx, dx_off, dx_ld, dx_hs)):
+        if not t_.is_contiguous() or t_.numel() < off + (tokens - 1) * ld_ + (H - 1) * hs + D:
+            raise ValueError(f"scale_rows_bwd: {name} holds {t_.numel()} elements, too few for [{tokens}, {H}] rows of {D} "
+                             f"at strides ({ld_}, {hs}) from {off} (or is not contiguous)")
+    if w.dtype != F32 or w.numel() != tokens * H or not w.is_contiguous():
+        raise ValueError(f"scale_rows_bwd: contiguous fp32 w [{tokens * H}]")
+    dw = torch.empty(tokens * H, device=gy.device, dtype=F32) if want_dw else None
+    check(lib.rf_scale_rows_bwd(ptr(x, x_off), dcode(x.dtype), int(x_ld), int(x_hs), ptr(gy, gy_off), dcode(gy.dtype), int(gy_ld),
+                                int(gy_hs), ptr(w), float(alpha), ptr(dx, dx_off), dcode(dx.dtype), int(dx_ld), int(dx_hs),
+                                ptr(dw), int(tokens), int(H), int(D), stream()), "rf_scale_rows_bwd")
+    return dx, dw
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through
