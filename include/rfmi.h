@@ -717,6 +717,34 @@ int rf_scale_rows_bwd(const void* x, int x_dtype, int64_t x_ld, int64_t x_hs, co
                       int64_t gy_hs, const float* w, float alpha, void* dx, int dx_dtype, int64_t dx_ld, int64_t dx_hs, float* dw,
                       int64_t tokens, int H, int D, void* stream);
 
+/* ---- backward pass of MsaUpdateWithPair (csrc/backward.hip; model.py, rf.py:559-610) ----------------------------------------
+ * Backward of the batched per-(layer, head) softmax of the shared front (rf_version >= 18).  logits: fp32 [B,L,L,NZ], what
+ * rf_softmax_batched read (after the logit dropout when there was one), map z = layer * H + head innermost; datt: fp32
+ * [NZ,B,L,datt_ld], the gradient of the maps, datt_ld >= L elements between rows (columns j >= L are neither read nor written);
+ * dz: fp32 [B,L,L,NZ], the logits' gradient:
+ *   p = softmax_j(logits[b,i,:,z]),   dz[b,i,j,z] = p_j (datt[z,b,i,j] - sum_l p_l datt[z,b,i,l])
+ * dz_h16, may be NULL: the same gradient in the build's 16-bit type, [B,L,L,nz_pad] with nz_pad >= NZ a multiple of 8 and exact
+ * zeros in the columns [NZ, nz_pad): the dy operand of rf_conv_wgrad, whose Co must be a multiple of 8 (nz_pad is not read
+ * when dz_h16 is NULL).  p is recomputed in fp32 with the row maximum subtracted; the normaliser and sum_l p_l datt_l are fp64
+ * sums, each dz rounded once.  L == 1: dz = 0 exactly.  A block owns one (b, i), whose NZ rows are one contiguous slab of L * NZ
+ * floats of logits and of dz; it holds the slab in NZ * (L | 1) * 4 bytes of LDS.  EVERY element of dz (and of dz_h16) is
+ * written, nothing else is; no atomics: the same bits run to run.
+ * RF_EINVAL before any launch: logits, datt or dz NULL, a size <= 0, datt_ld < L, with dz_h16 nz_pad < NZ or nz_pad % 8, or a
+ * slab beyond 160 KB of LDS (L * NZ of about 40900). */
+int rf_pair_softmax_bwd(const float* logits, const float* datt, int64_t datt_ld, float* dz, void* dz_h16, int nz_pad, int B, int L,
+                        int NZ, void* stream);
+/* Backward of z = rf_sym_layernorm(pair) . w^T (rf_version >= 18): pair fp32 [B,L,L,D]; w fp32 [NZ,D], the projection with the
+ * LayerNorm's gamma folded in; dz fp32 [B,L,L,NZ]; dpair fp32 [B,L,L,D].  With s = (pair_ij + pair_ji) / 2, xhat and rstd its
+ * LayerNorm statistics (two-pass fp32, as the forward takes them) and g = (dz_ij + dz_ji) . w:
+ *   dpair_ij = dpair_ji = rstd / 2 * (g - mean g - xhat mean(g xhat))
+ * One wave per unordered pair i <= j: both rows of pair and of dz are read once, both rows of dpair are written once (the
+ * diagonal once), bit for bit the same; g lives in registers (NZ fp32 FMAs per element from w in LDS; from memory when w exceeds
+ * 64 KB), the two means are fp64 sums.  EVERY element of dpair is written; no atomics: the same bits run to run.
+ * RF_EINVAL before any launch: a NULL tensor, a size <= 0, D % 4, D > 1024 or NZ > 64; RF_EALIGN: pair, w or dpair not 16-byte
+ * aligned. */
+int rf_sym_layernorm_bwd(const float* pair, const float* dz, const float* w, float* dpair, int B, int L, int D, int NZ, float eps,
+                         void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

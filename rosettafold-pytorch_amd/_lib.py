@@ -125,6 +125,8 @@ PROTOTYPES = {
     "rf_dist_masked_attention_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "rf_tied_softmax_bwd": [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
     "rf_scale_rows_bwd": [vp, i32, i64, i64, vp, i32, i64, i64, vp, f32, vp, i32, i64, i64, vp, i64, i32, i32, vp],
+    "rf_pair_softmax_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp],
+    "rf_sym_layernorm_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],

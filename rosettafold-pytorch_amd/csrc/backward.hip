@@ -1533,3 +1533,224 @@ extern "C" int rf_scale_rows_bwd(const void* x, int x_dtype, int64_t x_ld, int64
 #undef SRB_LAUNCH
   return rf_launch_status();
 }
+
+// ================================================================================================
+// rf_pair_softmax_bwd: backward of the batched per-(layer, head) softmax of MsaUpdateWithPair's shared front (model.py:
+// pair_to_att; ops.hip: softmax_batched_kernel).  The logits live in [B, L, L, NZ], map z = layer * H + head innermost, and the
+// softmax of map z runs over j at a stride of NZ floats.  A block owns one (b, i): the NZ rows of that pair row are ONE contiguous
+// slab of L * NZ floats, on the way in (logits) and on the way out (dz).
+//   phase A  the slab is read with consecutive lanes on consecutive floats and laid down in LDS as [z][j], rows an odd number
+//            of floats apart
+//   phase B  a wave per map z, a lane on the entries j = lane + 64 m: the maximum, then the normaliser and sum_j p datt in fp64 (as
+//            in dist_att_bwd_kernel and tied_softmax_bwd_kernel), then dz = p (datt - sum p datt), which replaces the logit in LDS;
+//            the datt row [z, b, i, :] is read along j, twice (the second time from cache)
+//   phase C  the slab of dz leaves as it came, consecutive lanes on consecutive floats, and so does the 16-bit copy with its
+//            nz_pad columns per (i, j), zeros in the columns [NZ, nz_pad)
+// No atomics and a fixed order: the same bits run to run.  L == 1: p = 1 and dz = datt - datt = 0 exactly.
+// ================================================================================================
+static inline int psb_row_ld(int L) { return L | 1; }
+
+__global__ __launch_bounds__(256) void pair_softmax_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ datt,
+                                                               int64_t datt_ld, float* __restrict__ dz, h16_t* __restrict__ dz16,
+                                                               int nz_pad, int B, int L, int NZ) {
+  extern __shared__ float psb_sm[];  // [NZ][L | 1]: logits, then dz
+  const int bi = blockIdx.x, b = bi / L, i = bi - b * L;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int Lo = L | 1;
+  const int n = L * NZ;
+  const int64_t slab = (int64_t)bi * n;
+  // ---- phase A
+  for (int e = t; e < n; e += 256) {
+    const int j = e / NZ, z = e - j * NZ;
+    psb_sm[z * Lo + j] = logits[slab + e];
+  }
+  __syncthreads();
+  // ---- phase B
+  for (int z = wv; z < NZ; z += 4) {
+    float* ps = psb_sm + z * Lo;
+    const float* dr = datt + (((int64_t)z * B + b) * L + i) * datt_ld;
+    float mx = -INFINITY;
+    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, ps[j]);
+    mx = wave_max(mx);
+    double s = 0.0, dot = 0.0;
+    for (int j = lane; j < L; j += 64) {
+      const double ex = (double)expf(ps[j] - mx);
+      s += ex;
+      dot = fma(ex, (double)dr[j], dot);
+    }
+    const double inv = 1.0 / wave_sum_f64(s);
+    dot = wave_sum_f64(dot) * inv;
+    for (int j = lane; j < L; j += 64) {
+      const double p = (double)expf(ps[j] - mx) * inv;
+      ps[j] = (float)(p * ((double)dr[j] - dot));
+    }
+  }
+  __syncthreads();
+  // ---- phase C
+  for (int e = t; e < n; e += 256) {
+    const int j = e / NZ, z = e - j * NZ;
+    dz[slab + e] = psb_sm[z * Lo + j];
+  }
+  if (dz16) {
+    const int n16 = L * nz_pad;
+    h16_t* out = dz16 + (int64_t)bi * n16;
+    for (int e = t; e < n16; e += 256) {
+      const int j = e / nz_pad, z = e - j * nz_pad;
+      out[e] = z < NZ ? f2h(psb_sm[z * Lo + j]) : (h16_t)0;
+    }
+  }
+}
+
+// include/rfmi.h: rf_pair_softmax_bwd
+extern "C" int rf_pair_softmax_bwd(const float* logits, const float* datt, int64_t datt_ld, float* dz, void* dz_h16, int nz_pad,
+                                   int B, int L, int NZ, void* stream) {
+  if (!logits || !datt || !dz || B <= 0 || L <= 0 || NZ <= 0 || datt_ld < L) return RF_EINVAL;
+  if (dz_h16 && (nz_pad < NZ || nz_pad % 8)) return RF_EINVAL;
+  if ((int64_t)B * L > 0x7fffffff) return RF_EINVAL;
+  const int64_t lds = (int64_t)NZ * psb_row_ld(L) * (int64_t)sizeof(float);
+  if (lds > 160 * 1024 || (dz_h16 && (int64_t)L * nz_pad > 0x7fffffff)) return RF_EINVAL;
+  if (lds > 64 * 1024) {
+    const int rc = rf_enable_big_lds<pair_softmax_bwd_kernel>();
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(pair_softmax_bwd_kernel, dim3(B * L), dim3(256), (size_t)lds, (hipStream_t)stream, logits, datt, datt_ld, dz,
+                     (h16_t*)dz_h16, nz_pad, B, L, NZ);
+  return rf_launch_status();
+}
+
+// ================================================================================================
+// rf_sym_layernorm_bwd: backward of z = rf_sym_layernorm(pair) . w^T, the shared front of MsaUpdateWithPair (symmetrise ->
+// LayerNorm without affine -> the folded projection W * gamma, model.py: pair_to_att).  With s = (pair_ij + pair_ji) / 2 -- the
+// same numbers for (i, j) and (j, i), so one xhat and one rstd serve both -- and g = (dz_ij + dz_ji) . w:
+//   dpair_ij = dpair_ji = rstd / 2 * (g - mean g - xhat * mean(g xhat))          (the diagonal: the same formula)
+// A wave takes one unordered pair i <= j: both pair rows and both dz rows are read once, g is formed in registers from w in LDS
+// (NZ fp32 FMAs per element; lane z holds dz_ij[z] + dz_ji[z] and hands it round by a shuffle), the statistics are recomputed two-pass
+// in fp32 with the forward's expressions, the two means are fp64 sums, and both output rows are written: no [B, L, L, D]
+// intermediate, each element of pair read once and each element of dpair written once, both as 16-byte pieces per lane.
+// The pairs are numbered without a square root: row r and row L - 1 - r of the upper triangle hold L + 1 pairs together, so item
+// (r, c), r < ceil(L / 2), c <= L, is (r, r + c) for c < L - r and (L - 1 - r, c - 1) past it (the middle row of an odd L once).
+// NV = 16-byte pieces per lane (D <= 256 NV); WLDS: w fits 64 KB of LDS, else it is read from memory (cache) in place.
+// ================================================================================================
+template <int NV, bool WLDS>
+__global__ __launch_bounds__(256) void sym_layernorm_bwd_kernel(const float* __restrict__ pair, const float* __restrict__ dz,
+                                                                const float* __restrict__ w, float* __restrict__ dpair, int L,
+                                                                int D, int NZ, float eps, int64_t items, int R) {
+  extern __shared__ float slb_sm[];  // WLDS: w [NZ][D]
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (WLDS) {
+    for (int e = t; e < NZ * D; e += 256) slb_sm[e] = w[e];
+    __syncthreads();
+  }
+  const int nch = D >> 2;
+  int c4[NV];  // this lane's pieces; a lane past the row computes on the row's last piece and writes nothing
+  bool ok[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    ok[v] = lane + 64 * v < nch;
+    c4[v] = ok[v] ? lane + 64 * v : nch - 1;
+  }
+  const float invD = 1.f / (float)D;
+  for (int64_t it = (int64_t)blockIdx.x * 4 + wv; it < items; it += (int64_t)gridDim.x * 4) {  // (wave-uniform)
+    const int64_t br = it / (L + 1);
+    const int c = (int)(it - br * (L + 1));
+    const int b = (int)(br / R), r = (int)(br - (int64_t)b * R);
+    int i, j;
+    if (c < L - r) {
+      i = r;
+      j = r + c;
+    } else {
+      i = L - 1 - r;
+      if (i == r) continue;
+      j = c - 1;
+    }
+    const int64_t rij = ((int64_t)b * L + i) * L + j, rji = ((int64_t)b * L + j) * L + i;
+    const float4* pa = (const float4*)(pair + rij * D);
+    const float4* pb = (const float4*)(pair + rji * D);
+    const float gzl = lane < NZ ? dz[rij * NZ + lane] + dz[rji * NZ + lane] : 0.f;
+    float4 s[NV];
+    float sum = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const float4 a = pa[c4[v]], bb = pb[c4[v]];
+      s[v] = make_float4(0.5f * (a.x + bb.x), 0.5f * (a.y + bb.y), 0.5f * (a.z + bb.z), 0.5f * (a.w + bb.w));
+      if (ok[v]) sum += (s[v].x + s[v].y) + (s[v].z + s[v].w);
+    }
+    const float mean = wave_sum(sum) * invD;
+    float q = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      s[v].x -= mean; s[v].y -= mean; s[v].z -= mean; s[v].w -= mean;
+      if (ok[v]) q += (s[v].x * s[v].x + s[v].y * s[v].y) + (s[v].z * s[v].z + s[v].w * s[v].w);
+    }
+    const float rstd = rsqrtf(wave_sum(q) * invD + eps);
+    float4 g[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) g[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* wp = WLDS ? slb_sm : w;
+#pragma unroll 4
+    for (int z = 0; z < NZ; ++z) {
+      const float gz = __shfl(gzl, z, 64);
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        const float4 w4 = *(const float4*)(wp + (int64_t)z * D + 4 * c4[v]);
+        g[v].x = fmaf(gz, w4.x, g[v].x); g[v].y = fmaf(gz, w4.y, g[v].y);
+        g[v].z = fmaf(gz, w4.z, g[v].z); g[v].w = fmaf(gz, w4.w, g[v].w);
+      }
+    }
+    double m1 = 0.0, m2 = 0.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      s[v].x *= rstd; s[v].y *= rstd; s[v].z *= rstd; s[v].w *= rstd;  // xhat
+      if (ok[v]) {
+        m1 += ((double)g[v].x + (double)g[v].y) + ((double)g[v].z + (double)g[v].w);
+        m2 += ((double)g[v].x * (double)s[v].x + (double)g[v].y * (double)s[v].y) +
+              ((double)g[v].z * (double)s[v].z + (double)g[v].w * (double)s[v].w);
+      }
+    }
+    const float mg = (float)(wave_sum_f64(m1) / (double)D), mgx = (float)(wave_sum_f64(m2) / (double)D);
+    const float hr = 0.5f * rstd;
+    float4* oa = (float4*)(dpair + rij * D);
+    float4* ob = (float4*)(dpair + rji * D);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      if (ok[v]) {
+        const float4 o = make_float4(hr * (g[v].x - mg - s[v].x * mgx), hr * (g[v].y - mg - s[v].y * mgx),
+                                     hr * (g[v].z - mg - s[v].z * mgx), hr * (g[v].w - mg - s[v].w * mgx));
+        oa[c4[v]] = o;
+        if (i != j) ob[c4[v]] = o;
+      }
+    }
+  }
+}
+
+// include/rfmi.h: rf_sym_layernorm_bwd
+extern "C" int rf_sym_layernorm_bwd(const float* pair, const float* dz, const float* w, float* dpair, int B, int L, int D, int NZ,
+                                    float eps, void* stream) {
+  if (!pair || !dz || !w || !dpair || B <= 0 || L <= 0 || D <= 0 || NZ <= 0) return RF_EINVAL;
+  if (D % 4 || D > 1024 || NZ > 64) return RF_EINVAL;
+  if (((uintptr_t)pair % 16) || ((uintptr_t)dpair % 16) || ((uintptr_t)w % 16)) return RF_EALIGN;
+  const int R = (L + 1) / 2;
+  if ((int64_t)B * R > 0x7fffffff) return RF_EINVAL;
+  const int64_t items = (int64_t)B * R * (L + 1);
+  const size_t wbytes = (size_t)NZ * D * sizeof(float);
+  const bool wlds = wbytes <= 64 * 1024;
+  const dim3 grid((unsigned)(items < 4 * 2048 ? cdiv(items, 4) : 2048));
+  hipStream_t s = (hipStream_t)stream;
+#define SLB_LAUNCH(NV_)                                                                                                            \
+  do {                                                                                                                             \
+    if (wlds)                                                                                                                      \
+      hipLaunchKernelGGL((sym_layernorm_bwd_kernel<NV_, true>), grid, dim3(256), wbytes, s, pair, dz, w, dpair, L, D, NZ, eps,     \
+                         items, R);                                                                                                \
+    else                                                                                                                           \
+      hipLaunchKernelGGL((sym_layernorm_bwd_kernel<NV_, false>), grid, dim3(256), 0, s, pair, dz, w, dpair, L, D, NZ, eps, items, \
+                         R);                                                                                                       \
+  } while (0)
+  if (D <= 256)
+    SLB_LAUNCH(1);
+  else if (D <= 512)
+    SLB_LAUNCH(2);
+  else
+    SLB_LAUNCH(4);
+#undef SLB_LAUNCH
+  return rf_launch_status();
+}

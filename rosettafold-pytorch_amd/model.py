@@ -1871,8 +1871,13 @@ class Symmetrization(nn.Module):
         return ops.axpby(x.contiguous(), 0.5, xt, 0.5, torch.empty_like(x))
 
 
-class MsaUpdateWithPairLayer(RFModule):
-    """rf.py:559-595."""
+class MsaUpdateWithPairLayer(RecordingModule):
+    """rf.py:559-595.  enable_backward() (switches the FeedForward in `ff` along): with grad mode on, forward(msa, pair) records,
+    and loss.backward() fills the .grad of every parameter of the layer and of msa and pair where they require grad (the
+    backward: MsaUpdateWithPair._backward, on a stack of this one layer).  MsaUpdateWithPair.run calls run() with the stack's
+    tape or with none; the trunk never hands one in."""
+    _rf_n_inputs = 2
+    _rf_scales_own_grads = True
 
     def __init__(self, d_msa, d_pair, n_heads, p_dropout=0.1):
         super().__init__()
@@ -1890,20 +1895,34 @@ class MsaUpdateWithPairLayer(RFModule):
         b = lin.weight.detach().float() @ lnm.bias.detach().float() + lin.bias.detach().float()
         return w, b
 
-    def run(self, msa, att, xn=None, next_ln=None, row_group=None):
+    def run(self, msa, att, xn=None, next_ln=None, row_group=None, tape=None):
         """msa fp32 [B,N,L,D] in place; att: T [H,B,L,L] (softmax over the last dim); xn = msa2value pre-norm if the
         previous GEMM produced it; returns next_ln(msa) or None.
         row_group: att holds this rank's rows [H,B,h,L] of the maps (pair-track row blocks, shard.shard_range); the values are
         computed from the replicated msa, positions r0..r1 are updated here (attention + feed-forward) and the updated position
-        slices are all-gathered so that msa is whole again on every rank."""
+        slices are all-gathered so that msa is whole again on every rank.
+        tape: a dict that receives what the backward needs (an fp32 copy of msa in front of the attention and in front of the
+        feed-forward -- msa is updated in place --, the attention-output dropout's records and the feed-forward's tape); the
+        kernels and numbers are those of the plain call."""
+        D = msa.shape[-1]
+        _check_backward_call(self, tape, row_group, D, D // self.n_heads)
         if row_group is not None:
             return self._run_rows(msa, att, xn, row_group)
         v_t = self._values(msa, xn)
+        sub = None
+        if tape is not None:
+            sub = {}
+            tape.update(x0=_copy(msa), att_drops=[], ff=sub)
+        drops = ()
         if self.training and self.p_dropout and self.p_dropout > 0:
-            add_dropped(msa, lambda tmp: self._add_attention_values(att, v_t, tmp), (self.p_dropout,))
-            return self._feed_forward(msa, next_ln, drops=(self.ff.p_dropout,))
-        self._add_attention_values(att, v_t, msa)
-        return self._feed_forward(msa, next_ln)
+            add_dropped(msa, lambda tmp: self._add_attention_values(att, v_t, tmp), (self.p_dropout,),
+                        tape["att_drops"] if tape is not None else None)
+            drops = (self.ff.p_dropout,)
+        else:
+            self._add_attention_values(att, v_t, msa)
+        if tape is not None:
+            tape["x1"] = _copy(msa)
+        return self._feed_forward(msa, next_ln, drops=drops, tape=sub)
 
     def _run_rows(self, msa, att, xn, row_group):
         """run() for a block of map rows (see there)."""
@@ -1939,24 +1958,86 @@ class MsaUpdateWithPairLayer(RFModule):
                  b_bs=(dv * Lr, N * D * Lr, 0), b_row=(dv, D * Lr, Lr),
                  c_bs=(dv, N * h * D, 0), c_row=(0, 0, D), c_col=(dv, h * D), residual=dst)
 
-    def _feed_forward(self, x, next_ln, drops=()):
-        return self.ff.fn[1].apply_residual(ln(self.ff.fn[0], x), x, next_ln, drops=drops)
+    def _feed_forward(self, x, next_ln, drops=(), tape=None):
+        return self.ff.fn[1].apply_residual(ln(self.ff.fn[0], x), x, next_ln, drops=drops, tape=tape)
 
-    def forward(self, msa, pair):
+    def _backward_layer(self, tape, g, att, datt):
+        """The layer's part of MsaUpdateWithPair._backward.  g: fp32 [B,N,L,D] gradient of the layer's output, updated in place
+        to the gradient of its msa input; att: the layer's maps T [H,B,L,Lp] as the forward wrote them (Lp = map_ld(L), zero pad
+        columns); datt: fp32 [H,B,L,L], receives the maps' gradient at scale 1.  Returns {param: grad}.
+        LN(msa), the row-major values and g key-contiguous are rebuilt from the saved stream; the attention . V half runs on a
+        copy of g at a power-of-two scale of its own (the fp16 mode), taken off datt, d msa and the parameters in fp32."""
+        x0 = tape["x0"]
+        B, N, Lr, D = x0.shape
+        H, Lp, dev = self.n_heads, att.shape[-1], x0.device
+        dv = D // H
+        lnv, lin = self.msa2value[0], self.msa2value[1]
+        grads = {}
+        _pre_norm_residual_bwd(g, self.ff.fn[1]._backward, tape["ff"], tape["x1"], self.ff.fn[0], grads)
+        s = _grad_scale([g])
+        go = _scaled_copy(g, s)
+        for rec in tape["att_drops"]:
+            _replay_dropout(go, rec)
+        go_t = ops.cast(go, T())
+        xn = ln(lnv, x0)
+        v = ops.linear(xn, self.wt("v", lin), _f(lin.bias), exact=True)   # the values row-major: [B,N,L,D] T
+        ops.gemm(go_t, v, datt, Lr, Lr, N * dv, batch=(H, B, 1), kc=dv,
+                 a_bs=(dv, N * Lr * D, 0), a_row=(0, 0, D), a_ko=Lr * D,
+                 b_bs=(dv, N * Lr * D, 0), b_row=(0, 0, D), b_ko=Lr * D,
+                 c_bs=(B * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr), exact=True)
+        del v
+        _unscale([datt], s)
+        mk = torch.empty if Lp == Lr else ops.zeros
+        go_tt = ops.copy4d(go_t, (N * Lr * D, Lr * D, 1, D), mk(B, N, D, Lp, device=dev, dtype=T()),
+                           (N * D * Lp, D * Lp, Lp, 1), (B, N, D, Lr))        # g key-contiguous, like the forward's v^T
+        att_tr = ops.copy4d(att, (0, Lr * Lp, 1, Lp), mk(H, B, Lr, Lp, device=dev, dtype=att.dtype),
+                            (0, Lr * Lp, Lp, 1), (1, H * B, Lr, Lr))
+        del go, go_t
+        dv_t = torch.empty(B, N, Lr, D, device=dev, dtype=T())
+        ops.gemm(att_tr, go_tt, dv_t, Lr, N * dv, Lp, batch=(H, B, 1),
+                 a_bs=(B * Lr * Lp, Lr * Lp, 0), a_row=(0, 0, Lp),
+                 b_bs=(dv * Lp, N * D * Lp, 0), b_row=(dv, D * Lp, Lp),
+                 c_bs=(dv, N * Lr * D, 0), c_row=(0, 0, D), c_col=(dv, Lr * D), exact=True)
+        del att_tr, go_tt
+        dwv, dbv = ops.conv_wgrad(dv_t, xn, 1, bias=True)
+        dm = ops.linear(dv_t, self.wt_input_grad("v", lin), None, out_dtype=F32, exact=True)
+        del dv_t, xn
+        gr = {lin.weight: dwv, lin.bias: dbv}
+        _unscale([dm] + list(gr.values()), s)
+        dx, gr[lnv.weight], gr[lnv.bias] = ops.layernorm_bwd(x0, dm, _f(lnv.weight), eps=lnv.eps)
+        ops.axpby(g, 1.0, dx, 1.0, g)
+        grads.update(gr)
+        return grads
+
+    def _backward(self, tape, g, want_pair=True):
+        return _msa_update_with_pair_backward([self], tape, g, want_pair)
+
+    def _backward_children(self):
+        return (self.ff.fn[1],)
+
+    def _record(self, msa, pair, tape):
         msa = fresh_f32(msa)
-        self.run(msa, pair_to_att([self], pair.float().contiguous())[0])
+        if tape is not None:
+            tape.update(front={}, layers=[{}])
+        att = pair_to_att([self], pair.float().contiguous(), tape=tape["front"] if tape is not None else None)[0]
+        self.run(msa, att, tape=tape["layers"][0] if tape is not None else None)
         return msa
 
+    def _backward_from_autograd(self, tape, gs, s, want):
+        dmsa, dpair, grads = self._backward(tape, _scaled_copy(gs[0], 1.0), want_pair=want[1])
+        return (dmsa, dpair), grads
 
-def pair_to_att(layers, pair, row_group=None):
-    """Shared front of the MsaUpdateWithPairLayer stack of one block (they all see the same pair):
-    one symmetrise+normalise pass, one GEMM for every layer's head logits, per-(layer,head) softmax.
-    Returns a list of T [H,B,L,Lp] ([H,B,h,Lp] for a block of h pair rows: row_group, the transposed sub-blocks of the
-    symmetrisation come from the other ranks); Lp = map_ld(L), columns L..Lp are zeros."""
-    B, h, Lr, Dp = pair.shape   # (h == L: the whole picture)
+    def forward(self, msa, pair):
+        if _recording(self):
+            return _RecordedFn.apply(self, msa, pair, *self.parameters())
+        return self._record(msa, pair, None)
+
+
+def _pair_logits(layers, pair, row_group=None):
+    """The front of pair_to_att up to the logits: (the symmetrised, normalised pair tensor T [B,h,L,Dp] without the LayerNorm's
+    affine, fp32 logits [B,h,L,nl*H] of every layer's heads from the folded projection)."""
     holder = layers[0]
-    H, nl = holder.n_heads, len(layers)
-    NH = nl * H
+    nl, Dp = len(layers), pair.shape[-1]
     eps = holder.pair2att[1].eps
     if row_group is None:
         xs = ops.sym_layernorm(pair, T(), eps=eps)
@@ -1973,39 +2054,169 @@ def pair_to_att(layers, pair, row_group=None):
         return torch.cat(ws, 0).to(T()).contiguous(), torch.cat(bs, 0).contiguous()
 
     wc, bc = holder.cached(("att_fold", nl), fold)
-    logits = ops.linear(xs, wc, bc, out_dtype=F32)  # [B,h,L,nl*H]
-    if holder.training and row_group is None:   # (the row-sharded forward is the inference path: shard.forward_row_sharded)
-        dropout_(logits, _p(holder.pair2att[3]))   # rf.py:567: Dropout sits between the projection and the softmax
-    # every (layer, head) softmax in one launch: problem z = li*H + h is column z of the logits
-    # (16-bit modes: rows Lp = map_ld(L) apart with zeros in the pad columns, the contraction of _add_attention_values runs over Lp)
+    return xs, ops.linear(xs, wc, bc, out_dtype=F32)
+
+
+def _pair_maps(logits, nl, H):
+    """every (layer, head) softmax in one launch: problem z = li*H + h is column z of the logits [B,h,L,nl*H]
+    (16-bit modes: rows Lp = map_ld(L) apart with zeros in the pad columns, the contraction of _add_attention_values runs over Lp)"""
+    B, h, Lr, NH = logits.shape
     Lp = map_ld(Lr)
-    att_all = (torch.empty if Lp == Lr else ops.zeros)(nl, H, B, h, Lp, device=pair.device, dtype=T())
+    att_all = (torch.empty if Lp == Lr else ops.zeros)(nl, H, B, h, Lp, device=logits.device, dtype=T())
     if h > 0:
         ops.softmax_batched(logits, 1, Lr * NH, NH, att_all, B * h * Lp, Lp, B * h, Lr, NH)
     return [att_all[li] for li in range(nl)]
 
 
-class MsaUpdateWithPair(RFModule):
-    """rf.py:598-610 (the reference hides these layers in a plain list; here they are registered)."""
+def pair_to_att(layers, pair, row_group=None, tape=None):
+    """Shared front of the MsaUpdateWithPairLayer stack of one block (they all see the same pair):
+    one symmetrise+normalise pass, one GEMM for every layer's head logits, per-(layer,head) softmax.
+    Returns a list of T [H,B,L,Lp] ([H,B,h,Lp] for a block of h pair rows: row_group, the transposed sub-blocks of the
+    symmetrisation come from the other ranks); Lp = map_ld(L), columns L..Lp are zeros.
+    tape: a dict that receives pair and the logit dropout's record (same kernels, same numbers)."""
+    holder = layers[0]
+    _check_backward_call(holder, tape, row_group, pair.shape[-1])
+    _, logits = _pair_logits(layers, pair, row_group)  # [B,h,L,nl*H]
+    rec = None
+    if holder.training and row_group is None:   # (the row-sharded forward is the inference path: shard.forward_row_sharded)
+        p = _p(holder.pair2att[3])   # rf.py:567: Dropout sits between the projection and the softmax
+        if tape is None:
+            dropout_(logits, p)
+        else:
+            rec = _dropout_rec(logits, p)
+    if tape is not None:
+        tape.update(pair=pair, drop=rec)
+    return _pair_maps(logits, len(layers), holder.n_heads)
+
+
+def _msa_update_with_pair_backward(layers, tape, g, want_pair=True):
+    """Backward of a stack of MsaUpdateWithPairLayer over one pair tensor (MsaUpdateWithPair._backward; a lone layer is a stack of
+    one).  g: contiguous fp32 [B,N,L,D] gradient of the output (overwritten).  Returns (fp32 d msa, fp32 d pair or None,
+    {param: grad})."""
+    front = tape["front"]
+    pair, rec = front["pair"], front["drop"]
+    B, Lr, _, Dp = pair.shape
+    holder = layers[0]
+    H, nl = holder.n_heads, len(layers)
+    NZ, dev = nl * H, pair.device
+    xs, logits = _pair_logits(layers, pair)
+    _replay_dropout(logits, rec)
+    atts = _pair_maps(logits, nl, H)
+    datt = torch.empty(NZ, B, Lr, Lr, device=dev, dtype=F32)
+    grads = {}
+    for li in reversed(range(nl)):
+        grads.update(layers[li]._backward_layer(tape["layers"][li], g, atts[li], datt[li * H:(li + 1) * H]))
+    del atts
+    # ---- every map's softmax in one launch; the logit dropout; the folded projection; symmetrise -> LayerNorm
+    h16 = ops.is_h16(T())
+    nzp = pad8(NZ)
+    late = h16 and (rec is not None or T() == torch.float16)   # the 16-bit copy follows the replay and the fp16 scale
+    dz, dz16 = ops.pair_softmax_bwd(logits, datt, nz_pad=nzp if h16 and not late else None)
+    del logits, datt
+    _replay_dropout(dz, rec)
+    w32 = holder.cached(("att_fold32", nl), lambda: torch.cat([l.folded_att_proj()[0] for l in layers], 0).contiguous())
+    dpair = ops.sym_layernorm_bwd(pair, dz, w32, eps=holder.pair2att[1].eps) if want_pair else None
+    s = 1.0
+    if late:
+        s = _grad_scale([dz])
+        if s != 1.0:
+            ops.axpby(dz, s, None, 0.0, dz)
+        dz16 = (torch.empty if nzp == NZ else ops.zeros)(B, Lr, Lr, nzp, device=dev, dtype=T())
+        ops.copy4d(dz, (0, 0, NZ, 1), dz16, (0, 0, nzp, 1), (1, 1, B * Lr * Lr, NZ))
+    dwf, dbf = ops.conv_wgrad(dz16 if h16 else dz, xs, 1, bias=True)   # the folded dW' [>= NZ, Dp], db' [>= NZ]
+    del xs, dz, dz16
+    _unscale([dwf, dbf], s)
+    # ---- unfolded per layer ([H, Dp]): dW = dW' gamma (+ db' beta^T), dgamma = sum_h dW' W (both: rf_scale_rows_bwd over the Dp
+    # columns as rows), db = db', dbeta = W^T db'
+    for li, layer in enumerate(layers):
+        lnm, lin = layer.pair2att[1], layer.pair2att[2]
+        wt32 = layer.cached("att_w_t32", lambda: lin.weight.detach().float().t().contiguous())   # W^T [Dp, H]
+        dwf_t = ops.copy4d(dwf, (0, 0, 1, Dp), torch.empty(Dp, H, device=dev, dtype=F32), (0, 0, H, 1), (1, 1, Dp, H),
+                           x_off=li * H * Dp)
+        dw_t, dgamma = ops.scale_rows_bwd(wt32, H, 0, dwf_t, H, 0, _f(lnm.weight), 1.0, Dp, 1, H)
+        grads[lin.weight] = ops.copy4d(dw_t, (0, 0, 1, H), torch.empty(H, Dp, device=dev, dtype=F32), (0, 0, Dp, 1), (1, 1, H, Dp))
+        grads[lnm.weight] = dgamma
+        if rec is None:
+            # both biases add one constant per head to a whole softmax row: exact zeros (float64 autograd returns rounding noise)
+            grads[lin.bias], grads[lnm.bias] = ops.zeros(H, device=dev, dtype=F32), ops.zeros(Dp, device=dev, dtype=F32)
+        else:
+            # (b' = W beta + b no longer drops out of the softmax: W receives db' beta^T through it as well)
+            db = _copy(dbf[li * H:(li + 1) * H])
+            grads[lin.bias] = db
+            grads[lnm.bias] = ops.linear(db.view(1, H), wt32, None, out_dtype=F32, exact=True).view(Dp)
+            dW = grads[lin.weight]
+            ops.linear(db.view(H, 1), _f(lnm.bias).view(Dp, 1), None, out=dW, residual=dW, exact=True)
+    return g, dpair, grads
+
+
+class MsaUpdateWithPair(RecordingModule):
+    """rf.py:598-610 (the reference hides these layers in a plain list; here they are registered).
+    enable_backward() (switches every layer and each layer's FeedForward along): with grad mode on, forward(msa, pair) records,
+    and loss.backward() fills the .grad of every parameter of the stack and of msa and pair where they require grad -- the one
+    way a loss on the MSA track sends gradient into the pair track inside a block.  The backward (_backward) walks the layers in
+    reverse; per layer: the feed-forward (FeedForward._backward through _pre_norm_residual_bwd, its dropouts replayed in train()
+    mode), the attention-output dropout replayed, then with g the gradient of att . V
+        d att[z,b,i,j] = sum_{n,c} g[b,n,i,h,c] v[b,n,j,h,c]          rf_gemm, K = N * dv in chunks of dv
+        d v = att^T g                                                 rf_gemm on the transposed 16-bit map and g key-contiguous,
+                                                                      both padded to map_ld(L) with zero columns
+        dW_v, db_v = dv^T LN(msa), sum dv;   d LN(msa) = dv W_v       rf_conv_wgrad;  rf_gemm, exact fp32
+        d msa += LayerNorm backward of msa2value[0]                   rf_layernorm_bwd
+    LN(msa), the values and the maps are rebuilt from the saved tensors with the forward's own launches.  After the last layer
+    all nl * H map gradients go through ONE rf_pair_softmax_bwd (dz [B,L,L,nl*H]), the logit dropout is replayed on dz,
+    rf_conv_wgrad(dz, xs) with xs = rf_sym_layernorm(pair) gives the folded dW' and db', and rf_sym_layernorm_bwd gives d pair.
+    The 16-bit copy of dz that rf_conv_wgrad reads (nl * H padded to a multiple of 8 with zero columns) is written by
+    rf_pair_softmax_bwd itself in the bf16 mode without logit dropout; with logit dropout, and in the fp16 mode, it is written
+    AFTER the replay and the fp16 scale, from the fp32 dz (the mask follows the element offset of the unpadded layout).
+    The folded gradients are unfolded per layer: dW = dW' gamma, dgamma = sum_h dW' W, db = db', dbeta = W^T db'.  Without logit
+    dropout pair2att.2.bias and pair2att.1.bias add one constant per head to a whole softmax row: their gradients are exact
+    zeros; with it they are computed, and W receives the term db' beta^T through the folded bias b' = W beta + b as well.
+    The fp16 mode's power-of-two gradient scale is applied per stage here (_rf_scales_own_grads), every backward contraction is
+    pinned exact.  While recording, row_group is refused and d_msa, d_msa / n_heads and d_pair must be multiples of 8.
+    TwoTrackBlock.run, ThreeTrackBlock.run3, FinalBlock.run3, RoseTTAFold.forward and the captured graph call run() without a
+    tape: they never record here."""
+    _rf_n_inputs = 2
+    _rf_scales_own_grads = True
 
     def __init__(self, d_msa, d_pair, n_heads, n_encoder_layers=4, p_dropout=0.1):
         super().__init__()
         self.encoder_layers = nn.ModuleList([MsaUpdateWithPairLayer(d_msa, d_pair, n_heads, p_dropout)
                                              for _ in range(n_encoder_layers)])
 
-    def run(self, msa, pair, row_group=None):
-        """msa fp32 [B,N,L,D] in place (replicated on every rank of row_group); pair: the whole tensor, or this rank's rows."""
+    def run(self, msa, pair, row_group=None, tape=None):
+        """msa fp32 [B,N,L,D] in place (replicated on every rank of row_group); pair: the whole tensor, or this rank's rows.
+        tape: a dict that receives the front's and the layers' tapes (pair_to_att, MsaUpdateWithPairLayer.run; same kernels,
+        same numbers)."""
         layers = list(self.encoder_layers)
-        atts = pair_to_att(layers, pair, row_group)
+        D = msa.shape[-1]
+        _check_backward_call(self, tape, row_group, D, D // layers[0].n_heads, pair.shape[-1])
+        if tape is not None:
+            tape.update(front={}, layers=[{} for _ in layers])
+        atts = pair_to_att(layers, pair, row_group, tape=tape["front"] if tape is not None else None)
         xn = None
         for i, (layer, att) in enumerate(zip(layers, atts)):
             nxt = layers[i + 1].msa2value[0] if i + 1 < len(layers) else None
-            xn = layer.run(msa, att, xn=xn, next_ln=nxt, row_group=row_group)
+            xn = layer.run(msa, att, xn=xn, next_ln=nxt, row_group=row_group,
+                           tape=tape["layers"][i] if tape is not None else None)
+
+    def _backward(self, tape, g, want_pair=True):
+        """g: contiguous fp32 [B,N,L,D] gradient of the output (overwritten).  Returns (fp32 d msa [B,N,L,D], fp32 d pair
+        [B,L,L,d_pair] or None, {param: grad}); the class docstring has the steps."""
+        return _msa_update_with_pair_backward(list(self.encoder_layers), tape, g, want_pair)
+
+    def _backward_children(self):
+        return self.encoder_layers
+
+    def _record(self, msa, pair, tape):
+        msa = fresh_f32(msa)
+        self.run(msa, pair.float().contiguous(), tape=tape)
+        return msa
+
+    _backward_from_autograd = MsaUpdateWithPairLayer._backward_from_autograd
 
     def forward(self, msa, pair):
-        msa = fresh_f32(msa)
-        self.run(msa, pair.float().contiguous())
-        return msa
+        if _recording(self):
+            return _RecordedFn.apply(self, msa, pair, *self.parameters())
+        return self._record(msa, pair, None)
 
 
 # ================================================================================================

@@ -764,6 +764,45 @@ def scale_rows_bwd(x, x_ld, x_hs, gy, gy_ld, gy_hs, w, alpha, tokens, H, D, *, d
     return dx, dw
 
 
+def pair_softmax_bwd(logits, datt, nz_pad=None):
+    """Backward of the batched per-(layer, head) softmax of MsaUpdateWithPair's shared front (rf_pair_softmax_bwd): logits
+    contiguous fp32 [B, L, L, NZ] (what softmax_batched read), datt contiguous fp32 [NZ, B, L, ld >= L], the gradient of the
+    maps (columns past L are not read).  Returns (dz fp32 [B, L, L, NZ], dz16): with nz_pad (a multiple of 8, >= NZ) the same
+    gradient in the active library's 16-bit type, [B, L, L, nz_pad] with zeros in the pad columns (rf_conv_wgrad's dy operand);
+    else (dz, None)."""
+    _need_cuda(logits, datt)
+    if logits.dim() != 4 or logits.shape[1] != logits.shape[2] or logits.dtype != F32 or not logits.is_contiguous():
+        raise ValueError("pair_softmax_bwd: contiguous fp32 logits [B, L, L, NZ]")
+    B, L_, _, NZ = logits.shape
+    if datt.dim() != 4 or datt.dtype != F32 or tuple(datt.shape[:3]) != (NZ, B, L_) or datt.shape[3] < L_ or not datt.is_contiguous():
+        raise ValueError(f"pair_softmax_bwd: contiguous fp32 datt [{NZ}, {B}, {L_}, >= {L_}]")
+    if nz_pad is not None and (nz_pad < NZ or nz_pad % 8):
+        raise ValueError(f"pair_softmax_bwd: nz_pad must be a multiple of 8 and at least {NZ}, got {nz_pad}")
+    dz = torch.empty(B, L_, L_, NZ, device=logits.device, dtype=F32)
+    dz16 = torch.empty(B, L_, L_, nz_pad, device=logits.device, dtype=h16()) if nz_pad is not None else None
+    check(lib.rf_pair_softmax_bwd(ptr(logits), ptr(datt), int(datt.shape[3]), ptr(dz), ptr(dz16), int(nz_pad or 0), B, L_, NZ,
+                                  stream()), "rf_pair_softmax_bwd")
+    return dz, dz16
+
+
+def sym_layernorm_bwd(pair, dz, w, eps=1e-5):
+    """Backward of sym_layernorm(pair) @ w^T (rf_sym_layernorm_bwd): pair contiguous fp32 [B, L, L, D], dz contiguous fp32
+    [B, L, L, NZ], w contiguous fp32 [NZ, D] (the projection with the LayerNorm's gamma folded in).  Returns fp32 d pair."""
+    _need_cuda(pair, dz, w)
+    if pair.dim() != 4 or pair.shape[1] != pair.shape[2] or pair.dtype != F32 or not pair.is_contiguous():
+        raise ValueError("sym_layernorm_bwd: contiguous fp32 pair [B, L, L, D]")
+    B, L_, _, D = pair.shape
+    if w.dim() != 2 or w.shape[1] != D or w.dtype != F32 or not w.is_contiguous():
+        raise ValueError(f"sym_layernorm_bwd: contiguous fp32 w [NZ, {D}]")
+    NZ = w.shape[0]
+    if dz.dtype != F32 or tuple(dz.shape) != (B, L_, L_, NZ) or not dz.is_contiguous():
+        raise ValueError(f"sym_layernorm_bwd: contiguous fp32 dz [{B}, {L_}, {L_}, {NZ}]")
+    dpair = torch.empty(pair.shape, device=pair.device, dtype=F32)
+    check(lib.rf_sym_layernorm_bwd(ptr(pair), ptr(dz), ptr(w), ptr(dpair), B, L_, D, NZ, float(eps), stream()),
+          "rf_sym_layernorm_bwd")
+    return dpair
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through
