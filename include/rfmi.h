@@ -287,7 +287,9 @@ int rf_poswise_collapsed(const void* xn, const void* u, float* w, int B, int N, 
  * 128-byte line per output column; s[o] = sum_k wprime[o,k] (fp32, of the 16-bit values);
  * c[o] = sum_k W[o,k] beta[k] + bias[o]; out: fp32 [B, L, L, Dout]:
  *     out = rstd * (sum_k co_k wprime[o,k] - mean * s[o]) + c[o],   mean / rstd over the 1024 features in fp32.
- * Supported: P == 32, Dout == 288, N in {64, 128}, L % 16 == 0 (RF_EINVAL otherwise: rf_gemm with RF_ACT_BLOCK_LN32 + rf_gemm).
+ * Supported: P == 32, Dout == 288, N in {64, 128}, any L >= 1 (RF_EINVAL otherwise: rf_gemm with RF_ACT_BLOCK_LN32 + rf_gemm;
+ * rf_version >= 19: before, L % 16 == 0 was required).  This is rf_outer_product_ln_linear_rect with Li = Lj = L; a picture of
+ * whole tiles (L % 16 == 0) runs the instruction stream it always ran.
  * Optional tail (PairUpdateWithMsa.ln_coevol_feat, rf.py:443,486): with y != NULL the kernel applies a second LayerNorm
  * (ln2_gamma / ln2_beta [Dout], ln2_eps) over the Dout outputs of every pair and writes 16-bit y[(b,i,j) * y_ld + o] INSTEAD of
  * `out` (which may then be NULL): the fp32 result and the separate LayerNorm pass over it disappear as well.  y: 16-byte
@@ -295,6 +297,26 @@ int rf_poswise_collapsed(const void* xn, const void* u, float* w, int B, int N, 
 int rf_outer_product_ln_linear(const void* xt, const void* yt, const void* wprime, const float* s, const float* c, float* out,
                                int B, int L, int N, int P, int Dout, float eps, const float* ln2_gamma, const float* ln2_beta,
                                float ln2_eps, void* y, int64_t y_ld, void* stream);
+
+/* The same kernel on a RECTANGULAR picture of any size (rf_version >= 19): rows i of xt against columns j of yt.
+ *   xt: 16-bit [B, Li, 32, N];  yt: 16-bit [B, Lj, 32, N];  out: fp32 [B, Li, Lj, Dout];  y: 16-bit, y[((b Li + i) Lj + j) y_ld + o];
+ *   wprime / s / c / eps / ln2_* / y_ld as in rf_outer_product_ln_linear.
+ * A block of pair rows (the row-sharded forward: Li = the rank's rows, Lj = L) is one call; so is a chain whose length is no
+ * multiple of the tile.  The kernel walks ceil(Li / 16) x ceil(Lj / 8) tiles of 16 x 8 pairs per sample.  In a tile that hangs
+ * over the picture the residues beyond it are neither read nor written: their operand rows are fetched from the LAST VALID
+ * residue of the same sample instead (no address leaves [b, 0 .. Li - 1] of xt or [b, 0 .. Lj - 1] of yt), the arithmetic of such
+ * a pair runs on that duplicate and stays finite, and every store -- fp32 rows of `out`, 16-byte pieces of the rows of `y` -- is
+ * predicated on (i, j) lying inside the picture.  Every element out[b, i, j, 0 .. Dout - 1] (or y[..., 0 .. Dout - 1]) with
+ * b < B, i < Li, j < Lj is written and nothing else is: columns Dout .. y_ld - 1 of `y` and memory before / behind the addressed
+ * block keep their contents.  A pair's result depends on its own operand rows only (bit-identical whichever picture holds it).
+ * The MSA depth stays N in {64, 128}: a shallower MSA is zero-padded by the caller (zeros add nothing to the sum over n); a
+ * deeper one would need 192 KB of operand buffers in the 160 KB of LDS and stays on the rf_gemm route.
+ * RF_EINVAL: a NULL operand, B / Li / Lj <= 0, P != 32, Dout != 288, N not in {64, 128}, neither `out` nor `y`, more than 2^31 - 1
+ * tiles, or with y != NULL: ln2_gamma / ln2_beta NULL, y_ld < Dout, y_ld % 8 != 0, y / ln2_gamma / ln2_beta not 16-byte aligned.
+ * RF_EALIGN: xt, yt, wprime, s, c or out not 16-byte aligned. */
+int rf_outer_product_ln_linear_rect(const void* xt, const void* yt, const void* wprime, const float* s, const float* c, float* out,
+                                    int B, int Li, int Lj, int N, int P, int Dout, float eps, const float* ln2_gamma,
+                                    const float* ln2_beta, float ln2_eps, void* y, int64_t y_ld, void* stream);
 
 /* PositionWiseWeightFactor core (rf.py:205-217): w[b,n,h,l] = softmax_n( scale * sum_{c<dlen} q0[b,l,h,c]*k[b,n,l,h,c] ).
  * q0: [B,L,H*dlen] (dtype q0_dtype, ld q0_ld); k: T rows [B,N,L,*] of ld k_ld, head h at column k_col0 + h*k_hstride.

@@ -27,13 +27,14 @@
 #include "common.h"
 
 struct OuterP {
-  const h16_t* xt;   // [B, L, 32, N]   x_t[b,i,u,n]  (MSA depth contiguous)
-  const h16_t* yt;   // [B, L, 32, N]
+  const h16_t* xt;   // [B, Li, 32, N]  x_t[b,i,u,n]  (MSA depth contiguous)
+  const h16_t* yt;   // [B, Lj, 32, N]
   const h16_t* wp;   // [16, Dout, 64]  W * gamma, chunk-major: wp[c][o][uu * 8 + vv] = (W gamma)[o][(8 (c / 4) + uu) * 32 + 8 (c % 4) + vv]
   const float* s;    // [Dout]          row sums of wp
   const float* c;    // [Dout]          W beta + bias
-  float* out;        // [B, L, L, Dout] fp32
-  int B, L, Dout;
+  float* out;        // [B, Li, Lj, Dout] fp32
+  int B, Li, Lj, Dout;
+  int nti, ntj;      // tiles per picture: ceil(Li / 16) rows of ceil(Lj / 8)
   float eps;
   // optional second LayerNorm over the Dout outputs of every pair (PairUpdateWithMsa.ln_coevol_feat, rf.py:443,486): when
   // y != NULL the kernel writes y[pair, 0:Dout] = LN2(out[pair, :]) in the 16-bit type (row stride y_ld elements) INSTEAD of `out`
@@ -60,8 +61,14 @@ __device__ __forceinline__ void outer_lds_barrier() {
   __builtin_amdgcn_s_barrier();
 }
 
-// NKS = N / 32 (stage-1 K steps): 4 (N = 128) or 2 (N = 64)
-template <int NKS, bool LN2>
+// NKS = N / 32 (stage-1 K steps): 4 (N = 128) or 2 (N = 64).  (N = 256 would need NKS = 8: 192 KB of operand buffers, more
+// than the 160 KB of LDS -- deeper MSAs stay on the general route.)
+// TAIL: the picture is Li x Lj pairs with Li % 16 or Lj % 8 != 0, so the last row / column of tiles hangs over its edge.  The
+// rule of favor.hip and tied.hip: residues beyond the picture are neither read nor written.  The DMA source row of such a
+// residue is clamped to the last valid residue of the same sample (whole DMA instructions per wave, no address outside the
+// sample), its pairs' arithmetic runs on the duplicate (finite whenever the operands are), and every store is predicated on
+// the pair's (i, j) lying inside the picture.  With TAIL = false none of that code exists: the full-tile instruction stream.
+template <int NKS, bool LN2, bool TAIL>
 __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
   constexpr int TI = 16, TJ = 8, PT = TI * TJ;   // pairs per tile
   constexpr int NB = NKS * 64;                   // bytes per operand row (N 16-bit values)
@@ -135,14 +142,19 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
   const h16_t* xb = nullptr;
   const h16_t* yb = nullptr;
   int b = 0, i0 = 0, j0 = 0;
+  int ilim = TI - 1, jlim = TJ - 1;  // TAIL: last row / column of the tile that lies inside the picture
   auto set_tile = [&](int tile) {
-    const int jt = tile % (p.L / TJ), t2 = tile / (p.L / TJ);
-    const int it = t2 % (p.L / TI);
-    b = t2 / (p.L / TI);
+    const int jt = tile % p.ntj, t2 = tile / p.ntj;
+    const int it = t2 % p.nti;
+    b = t2 / p.nti;
     i0 = it * TI;
     j0 = jt * TJ;
-    xb = p.xt + ((int64_t)b * p.L + i0) * 32 * N;
-    yb = p.yt + ((int64_t)b * p.L + j0) * 32 * N;
+    xb = p.xt + ((int64_t)b * p.Li + i0) * 32 * N;
+    yb = p.yt + ((int64_t)b * p.Lj + j0) * 32 * N;
+    if constexpr (TAIL) {
+      ilim = min(TI - 1, p.Li - 1 - i0);
+      jlim = min(TJ - 1, p.Lj - 1 - j0);
+    }
   };
   auto dma_x = [&](int ug) {  // rows (i_l, u_l): i_l = row >> 3, u = 8 ug + (row & 7)
     const unsigned dst = lds0 + X_OFF + (ug & 1) * XCH;
@@ -152,7 +164,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
     for (int t = 0; t < PDX; ++t) {
       const int q = wave + 8 * t;
       const int row = q * RPI + ln / SPR, sl = ln % SPR;
-      outer_glds16(xb + ((int64_t)(row >> 3) * 32 + ug * 8 + (row & 7)) * N + ((sl ^ (swz(row) & (SPR - 1))) << 3),
+      const int il = TAIL ? min(row >> 3, ilim) : (row >> 3);  // (a residue beyond the picture: the last valid one again)
+      outer_glds16(xb + ((int64_t)il * 32 + ug * 8 + (row & 7)) * N + ((sl ^ (swz(row) & (SPR - 1))) << 3),
                    __builtin_amdgcn_readfirstlane(dst + q * 1024));
     }
   };
@@ -165,7 +178,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
     for (int t = 0; t < PDY; ++t) {
       const int q = wave + 8 * t;
       const int row = q * RPI + ln / SPR, sl = ln % SPR;
-      outer_glds16(yb + ((int64_t)(row >> 3) * 32 + vg * 8 + (row & 7)) * N + ((sl ^ (swz(row) & (SPR - 1))) << 3),
+      const int jl_ = TAIL ? min(row >> 3, jlim) : (row >> 3);
+      outer_glds16(yb + ((int64_t)jl_ * 32 + vg * 8 + (row & 7)) * N + ((sl ^ (swz(row) & (SPR - 1))) << 3),
                    __builtin_amdgcn_readfirstlane(dst + q * 1024));
     }
   };
@@ -300,6 +314,10 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
 
     // ---------------- next tile's first operands (x[0], y[0], wx[0] and register set A are free) ----------------
     const int b_t = b, i0_t = i0, j0_t = j0;
+    const int ilim_t = ilim, jlim_t = jlim;
+    // pair pr = (i_l, j_l) = (pr >> 3, pr & 7) of this tile: its row of the output, and whether the picture holds it
+    auto pair_row = [&](int pr) { return ((int64_t)b_t * p.Li + i0_t + (pr >> 3)) * p.Lj + j0_t + (pr & 7); };
+    auto inside = [&](int pr) { return !TAIL || ((pr >> 3) <= ilim_t && (pr & 7) <= jlim_t); };
     const bool more = tile + t_step < t_end;
     auto prefetch_next = [&]() {
       set_tile(tile + t_step);
@@ -358,9 +376,11 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
         a += __shfl_xor(a, 32, 64); q += __shfl_xor(q, 32, 64);
         if (fq == 0) *(float2*)(part + (8 * PT + pr) * 2) = make_float2(a, q);
       } else {
-        float* orow = p.out + (((int64_t)b_t * p.L + i0_t + (pr >> 3)) * p.L + j0_t + (pr & 7)) * p.Dout + 256 + 4 * fq;
+        float* orow = p.out + pair_row(pr) * p.Dout + 256 + 4 * fq;
+        if (inside(pr)) {
 #pragma unroll
-        for (int cc = 0; cc < 2; ++cc) *(f32x4*)(orow + cc * 16) = accx[cc];
+          for (int cc = 0; cc < 2; ++cc) *(f32x4*)(orow + cc * 16) = accx[cc];
+        }
       }
     }
 #pragma unroll
@@ -385,11 +405,11 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
         a += __shfl_xor(a, 32, 64); q += __shfl_xor(q, 32, 64);
         if (fq == 0) *(float2*)(part + (wave * PT + pr) * 2) = make_float2(a, q);
       } else {
-        float* orow = p.out + (((int64_t)b_t * p.L + i0_t + (pr >> 3)) * p.L + j0_t + (pr & 7)) * p.Dout + o_w + 4 * fq;
+        float* orow = p.out + pair_row(pr) * p.Dout + o_w + 4 * fq;
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
           const f32x4 v = (acc[rt][cc] - mu * s4[cc]) * rstd + c4[cc];
-          *(f32x4*)(orow + cc * 16) = v;
+          if (inside(pr)) *(f32x4*)(orow + cc * 16) = v;
         }
       }
     }
@@ -453,8 +473,8 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
         if (NPC % 512 == 0 || idx < NPC) {
           const int pr = idx / 36, ch = idx % 36;
           const f32x4 v = *(const f32x4*)(img_row(pr) + ch * 16);
-          h16_t* yrow = p.y + (((int64_t)b_t * p.L + i0_t + (pr >> 3)) * p.L + j0_t + (pr & 7)) * p.y_ld + ch * 8;
-          *(f32x4*)yrow = v;
+          h16_t* yrow = p.y + pair_row(pr) * p.y_ld + ch * 8;
+          if (inside(pr)) *(f32x4*)yrow = v;
         }
       }
     }
@@ -465,34 +485,51 @@ __global__ __launch_bounds__(512, 2) void outer_fused_kernel(const OuterP p) {
   }
 }
 
-template <int NKS, bool LN2>
-static int launch_outer(OuterP& p, hipStream_t s) {
+template <int NKS, bool LN2, bool TAIL>
+static int launch_outer_t(OuterP& p, hipStream_t s) {
   constexpr int NB = NKS * 64;
   constexpr int LDS = 2 * (16 * 8 * NB) + 2 * (8 * 8 * NB) + 2 * (128 * 128) + 2 * (32 * 128) + 128 * 8;
   const int ncu = rf_num_cus() > 0 ? rf_num_cus() : 256;
-  p.ntiles = p.B * (p.L / 16) * (p.L / 8);
   const int grid = p.ntiles < ncu ? p.ntiles : ncu;
-  if (const int e = rf_enable_big_lds<outer_fused_kernel<NKS, LN2>>()) return e;
-  hipLaunchKernelGGL((outer_fused_kernel<NKS, LN2>), dim3((unsigned)grid), dim3(512), LDS, s, p);
+  if (const int e = rf_enable_big_lds<outer_fused_kernel<NKS, LN2, TAIL>>()) return e;
+  hipLaunchKernelGGL((outer_fused_kernel<NKS, LN2, TAIL>), dim3((unsigned)grid), dim3(512), LDS, s, p);
   return rf_launch_status();
 }
 
-extern "C" int rf_outer_product_ln_linear(const void* xt, const void* yt, const void* wprime, const float* s, const float* c,
-                                          float* out, int B, int L, int N, int P, int Dout, float eps, const float* ln2_gamma,
-                                          const float* ln2_beta, float ln2_eps, void* y, int64_t y_ld, void* stream) {
-  if (!xt || !yt || !wprime || !s || !c || B <= 0) return RF_EINVAL;
+template <int NKS, bool LN2>
+static int launch_outer(OuterP& p, hipStream_t s) {
+  p.nti = (p.Li + 15) / 16;
+  p.ntj = (p.Lj + 7) / 8;
+  p.ntiles = p.B * p.nti * p.ntj;
+  // the tail variant only where a tile hangs over the picture: whole-tile pictures run the code they always ran
+  return (p.Li % 16 || p.Lj % 8) ? launch_outer_t<NKS, LN2, true>(p, s) : launch_outer_t<NKS, LN2, false>(p, s);
+}
+
+extern "C" int rf_outer_product_ln_linear_rect(const void* xt, const void* yt, const void* wprime, const float* s, const float* c,
+                                               float* out, int B, int Li, int Lj, int N, int P, int Dout, float eps,
+                                               const float* ln2_gamma, const float* ln2_beta, float ln2_eps, void* y, int64_t y_ld,
+                                               void* stream) {
+  if (!xt || !yt || !wprime || !s || !c || B <= 0 || Li <= 0 || Lj <= 0) return RF_EINVAL;
   if (!y && !out) return RF_EINVAL;
   if (y && (!ln2_gamma || !ln2_beta || y_ld < Dout || y_ld % 8 || ((uintptr_t)y % 16) || ((uintptr_t)ln2_gamma % 16) || ((uintptr_t)ln2_beta % 16)))
     return RF_EINVAL;
-  if (P != 32 || Dout != 288 || (N != 128 && N != 64) || L % 16 != 0 || L < 16) return RF_EINVAL;  // (other shapes: rf_gemm + rf_layernorm)
+  if (P != 32 || Dout != 288 || (N != 128 && N != 64)) return RF_EINVAL;  // (other shapes: rf_gemm + rf_layernorm)
+  if ((int64_t)B * ((Li + 15) / 16) * ((Lj + 7) / 8) > 0x7fffffff) return RF_EINVAL;  // (the tile index is an int)
   if (((uintptr_t)xt % 16) || ((uintptr_t)yt % 16) || ((uintptr_t)wprime % 16) || ((uintptr_t)s % 16) || ((uintptr_t)c % 16) ||
       ((uintptr_t)out % 16))
     return RF_EALIGN;
   OuterP p;
   p.xt = (const h16_t*)xt; p.yt = (const h16_t*)yt; p.wp = (const h16_t*)wprime; p.s = s; p.c = c; p.out = out;
-  p.B = B; p.L = L; p.Dout = Dout; p.eps = eps;
+  p.B = B; p.Li = Li; p.Lj = Lj; p.Dout = Dout; p.eps = eps;
   p.g2 = ln2_gamma; p.b2 = ln2_beta; p.eps2 = ln2_eps; p.y = (h16_t*)y; p.y_ld = y_ld;
   hipStream_t st = (hipStream_t)stream;
   if (y) return N == 128 ? launch_outer<4, true>(p, st) : launch_outer<2, true>(p, st);
   return N == 128 ? launch_outer<4, false>(p, st) : launch_outer<2, false>(p, st);
+}
+
+extern "C" int rf_outer_product_ln_linear(const void* xt, const void* yt, const void* wprime, const float* s, const float* c,
+                                          float* out, int B, int L, int N, int P, int Dout, float eps, const float* ln2_gamma,
+                                          const float* ln2_beta, float ln2_eps, void* y, int64_t y_ld, void* stream) {
+  return rf_outer_product_ln_linear_rect(xt, yt, wprime, s, c, out, B, L, L, N, P, Dout, eps, ln2_gamma, ln2_beta, ln2_eps, y,
+                                         y_ld, stream);
 }

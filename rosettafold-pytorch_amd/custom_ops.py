@@ -103,7 +103,8 @@ def _(qkv, proj, heads, softmax_kernel):
 
 @torch.library.custom_op("rfmi::outer_product_ln_linear", mutates_args=(), device_types="cuda")
 def outer_product_ln_linear(x: Tensor, y: Tensor, gamma: Tensor, beta: Tensor, w: Tensor, b: Tensor, eps: float) -> Tensor:
-    """x, y bf16 [B, N, L, 32] -> fp32 [B, L, L, d_out]: Linear(LayerNorm(sum_n x[n,i,:] (x) y[n,j,:])), rf.py:415-427."""
+    """x, y 16-bit [B, N, L, 32], any L >= 1 and N <= 128 (the depth is zero-padded to 64 / 128) -> fp32 [B, L, L, d_out]:
+    Linear(LayerNorm(sum_n x[n,i,:] (x) y[n,j,:])), rf.py:415-427."""
     with _guard(x):
         return ops.outer_product_ln_linear(x, y, gamma, beta, w, b, eps)
 

@@ -1373,8 +1373,19 @@ class OuterProductMean(RecordingModule):
         self.to_out = nn.Sequential(LayerNorm(in_features ** 2), Linear(in_features ** 2, out_features))
 
     def fused_ok(self, P, N, Lr):
-        return (RT.fused_outer and ops.is_h16(T()) and P == 32 and N in (64, 128) and Lr % 16 == 0
+        """the fused kernel (csrc/outer.hip) serves this call: 16-bit modes, P = 32, 288 outputs, any chain length Lr >= 1 and
+        any MSA depth N <= 128 (run at ops.outer_depth(N) = 64 or 128, zero-padded)"""
+        return (RT.fused_outer and ops.is_h16(T()) and P == 32 and 1 <= N <= 128 and Lr >= 1
                 and self.to_out[1].weight.shape[0] == 288)
+
+    def depth_multiple(self, P, N, Lr):
+        """what ops.outer_operands pads the MSA depth to for the route run() takes: the fused kernel's depth, or 8"""
+        return ops.outer_depth(N) if self.fused_ok(P, N, Lr) else 8
+
+    def _fused_operands(self, x_t, y_t):
+        """operands at the fused kernel's depth (callers that built them through depth_multiple hand them over as they are)"""
+        Nk = ops.outer_depth(x_t.shape[-1])
+        return ops.outer_pad_depth(x_t, Nk), ops.outer_pad_depth(y_t, Nk)
 
     def _fold(self):
         """(packed W * gamma, its row sums, W beta + bias) of ops.outer_fold, cached with the weights."""
@@ -1383,9 +1394,11 @@ class OuterProductMean(RecordingModule):
                                                                  lnm.bias.detach(), lin.bias.detach()))
 
     def run_into(self, x_t, y_t, ln2, feat, feat_ld):
-        """Fused form with the consumer's LayerNorm (PairUpdateWithMsa.ln_coevol_feat) in the epilogue: writes bf16
-        feat[..., 0:288] directly; neither the 1024-wide tensor nor the fp32 result exists."""
+        """Fused form with the consumer's LayerNorm (PairUpdateWithMsa.ln_coevol_feat) in the epilogue: writes 16-bit
+        feat[..., 0:288] directly; neither the 1024-wide tensor nor the fp32 result exists.  x_t may be a block of rows
+        [B, h, P, N] against y_t [B, L, P, N] (feat [B, h, L, feat_ld])."""
         wp, s_, c_ = self._fold()
+        x_t, y_t = self._fused_operands(x_t, y_t)
         return ops.outer_fused(x_t, y_t, wp, s_, c_, None, self.to_out[0].eps,
                                ln2=(_f(ln2.weight), _f(ln2.bias), ln2.eps, feat, feat_ld))
 
@@ -1404,6 +1417,7 @@ class OuterProductMean(RecordingModule):
             # tensor never leaves the chip (csrc/outer.hip)
             wp, s_, c_ = self._fold()
             out = torch.empty(B, Lr, Lr, lin.weight.shape[0], device=x_t.device, dtype=F32)
+            x_t, y_t = self._fused_operands(x_t, y_t)
             return ops.outer_fused(x_t, y_t, wp, s_, c_, out, lnm.eps)
         co = torch.empty(B, Lr, Lr, PP, device=x_t.device, dtype=T())
         if ops.is_h16(T()) and P == 32 and (Lr * P) % 256 == 0 and N >= 64 and RT.fused_outer_ln:
@@ -1420,14 +1434,19 @@ class OuterProductMean(RecordingModule):
         return ops.linear(cn, self.wt("w", self.to_out[1]), _f(self.to_out[1].bias), out_dtype=F32)
 
     def run_rows(self, x_rows_t, y_t, N):
-        """x_rows_t: T [B, h, P, N] (a block of rows), y_t: T [B, L, P, N] -> fp32 [B, h, L, out]: the general path of run()
-        on a rectangular block (pair-track row-block sharding)."""
+        """x_rows_t: T [B, h, P, N] (a block of rows), y_t: T [B, L, P, N] -> fp32 [B, h, L, out]: run() on a rectangular
+        block (pair-track row-block sharding), through the fused kernel where run() would take it (the same bits as those
+        rows of run(): a pair's result depends on its own operand rows only), else the general path in slabs."""
         _check_backward_call(self, None, "rows")   # a block of rows IS the row-sharded call: refused while recording
         B, h, P, _ = x_rows_t.shape
         Lr = y_t.shape[1]
         PP = P * P
         lnm = self.to_out[0]
         out = torch.empty(B, h, Lr, self.to_out[1].weight.shape[0], device=x_rows_t.device, dtype=F32)
+        if self.fused_ok(P, N, Lr):
+            wp, s_, c_ = self._fold()
+            x_rows_t, y_t = self._fused_operands(x_rows_t, y_t)
+            return ops.outer_fused(x_rows_t, y_t, wp, s_, c_, out, lnm.eps)
         # in slabs of rows: the P*P-wide intermediate of a slab stays under 2^28 elements (rf_gemm rejects the 512 x 1024 block of a
         # two-rank split at L = 1024 in one piece; the slab also bounds the 0.5 GB-per-256-rows intermediate)
         step = max(1, (1 << 28) // (Lr * PP * B))
@@ -1449,7 +1468,8 @@ class OuterProductMean(RecordingModule):
     def _record(self, x, y, tape):
         if tape is not None:
             tape.update(n=x.shape[1], one=y is None)
-        return self.run(*ops.outer_operands(x, x if y is None else y, T()), tape=tape)
+        B, N, Lr, P = x.shape
+        return self.run(*ops.outer_operands(x, x if y is None else y, T(), self.depth_multiple(P, N, Lr)), tape=tape)
 
     def backward_slab_rows(self, Lr, P):
         """pair rows per slab of _backward: the slab's three P^2-wide tensors stay under RT.outer_bwd_slab_bytes"""
@@ -1595,7 +1615,7 @@ class PairUpdateWithMsa(RFModule):
         ops.copy4d(mp, (N * Lr * P, 0, P, 1), msa1d, (Lr * 2 * P, 0, 2 * P, 1), (B, 1, Lr, P), y_off=P)
         # transposed operands of the outer product: x_t[b,i,u,n] = mp ; y_t = mp * w   (rf.py:472-473)
         mpw = ops.scale_rows(mp, w, B * N * Lr, P)
-        return (msa1d,) + ops.outer_operands(mp, mpw, T())
+        return (msa1d,) + ops.outer_operands(mp, mpw, T(), self.outer_product_mean.depth_multiple(P, N, Lr))
 
     # ---- operand conditioning of the 16-bit modes (csrc/condition.hip; tools/precision_probe.py --pum-sweep) ------------------
     # At random init the 1-D features and the projected feature tensor are a per-sample constant plus a part ~20x smaller that
@@ -1630,11 +1650,14 @@ class PairUpdateWithMsa(RFModule):
         msa1d, xt, yt, Np = self._msa_operands(msa)
         Kf = pad8(self.d_feat)
         feat = ops.zeros(B, h, Lr, Kf, device=dev, dtype=T())
-        # outer product of this block's rows with every column: the general GEMM form (the fused kernel walks square pictures)
+        # outer product of this block's rows with every column: the fused kernel on the rectangle, as run() does on the square
         xr = ops.copy4d(xt, (Lr * P * Np, P * Np, Np, 1), torch.empty(B, h, P, Np, device=dev, dtype=T()),
                         (h * P * Np, P * Np, Np, 1), (B, h, P, Np), x_off=r0 * P * Np)
-        coevol = self.outer_product_mean.run_rows(xr, yt, Np)  # fp32 [B,h,L,Dp]
-        ln(self.ln_coevol_feat, coevol, out=feat, out_ld=Kf, out_off=0)
+        if self.outer_product_mean.fused_ok(P, Np, Lr) and Dp == 288:
+            self.outer_product_mean.run_into(xr, yt, self.ln_coevol_feat, feat, Kf)  # -> feat[..., :Dp]
+        else:
+            coevol = self.outer_product_mean.run_rows(xr, yt, Np)  # fp32 [B,h,L,Dp]
+            ln(self.ln_coevol_feat, coevol, out=feat, out_ld=Kf, out_off=0)
         cond = RT.condition and ops.is_h16(T()) and Dp % 4 == 0   # (rf_center_apply moves 16-byte chunks of a pixel)
         bias = _f(self.resnet[0].bias)
         if cond:   # (the mean over ALL positions: msa is replicated, every rank folds the same constant)

@@ -352,10 +352,16 @@ def tied_row_attention(q, k, v):
 
 
 def outer_fused(xt, yt, wprime, s, c, out, eps, ln2=None):
-    """Fused OuterProductMean core (csrc/outer.hip): xt, yt 16-bit [B, L, 32, N]; wprime chunk-major [16, Dout, 64] from outer_fold;
-    out fp32 [B,L,L,Dout].
+    """Fused OuterProductMean core (csrc/outer.hip): xt 16-bit [B, Li, 32, N] (rows of the picture), yt 16-bit [B, Lj, 32, N] (its
+    columns), any Li, Lj >= 1, N = 64 or 128 (outer_depth); wprime chunk-major [16, Dout, 64] from outer_fold; out fp32 [B,Li,Lj,Dout].
     ln2 = (gamma, beta, eps, y, y_ld): also apply LayerNorm over Dout and write 16-bit y[(b,i,j) * y_ld + o] instead of `out`."""
-    B, L_, P, N = xt.shape
+    B, Li, P, N = xt.shape
+    Lj = yt.shape[1]
+    if yt.dim() != 4 or (yt.shape[0], yt.shape[2], yt.shape[3]) != (B, P, N) or not (xt.is_contiguous() and yt.is_contiguous()):
+        raise ValueError(f"outer_fused: contiguous operands [B, Li, P, N] and [B, Lj, P, N] expected, got {tuple(xt.shape)} and "
+                         f"{tuple(yt.shape)}")
+    if out is not None and (out.dtype != F32 or tuple(out.shape) != (B, Li, Lj, wprime.shape[1]) or not out.is_contiguous()):
+        raise ValueError(f"outer_fused: out must be contiguous fp32 {(B, Li, Lj, wprime.shape[1])}")
     _need_cuda(xt, yt, wprime, s, c, out)
     g2 = b2 = y = None
     eps2, y_ld = 0.0, 0
@@ -364,9 +370,10 @@ def outer_fused(xt, yt, wprime, s, c, out, eps, ln2=None):
         _need_cuda(g2, b2, y)
     if wprime.dim() != 3 or wprime.shape[0] != 16 or wprime.shape[2] != 64:
         raise ValueError("outer_fused: wprime must come from outer_fold (chunk-major [16, Dout, 64])")
-    check(lib.rf_outer_product_ln_linear(ptr(xt), ptr(yt), ptr(wprime), ptr(s), ptr(c), ptr(out), B, L_, N, P, wprime.shape[1],
-                                         float(eps), ptr(g2), ptr(b2), float(eps2), ptr(y), int(y_ld), stream()),
-          "rf_outer_product_ln_linear")
+    check(lib.rf_outer_product_ln_linear_rect(ptr(xt), ptr(yt), ptr(wprime), ptr(s), ptr(c), ptr(out), B, Li, Lj, N, P,
+                                              wprime.shape[1], float(eps), ptr(g2), ptr(b2), float(eps2), ptr(y), int(y_ld),
+                                              stream()),
+          "rf_outer_product_ln_linear_rect")
     return y if ln2 is not None else out
 
 
@@ -382,11 +389,27 @@ def outer_fold(w, gamma, beta, bias, dtype=None):
     return wpc, s, c
 
 
-def outer_operands(x, y, dtype):
+def outer_depth(N):
+    """MSA depth the fused kernel (csrc/outer.hip) runs a depth-N outer product at: 64 or 128, zero-padded (zeros add nothing
+    to the sum over n); None for N > 128 (eight K steps of operands do not fit the LDS: the general route)."""
+    return 64 if N <= 64 else 128 if N <= 128 else None
+
+
+def outer_pad_depth(t, Np):
+    """t [B, L, P, n] -> contiguous [B, L, P, Np], zero-padded along the MSA depth (t itself when n == Np already)."""
+    B, L_, P, n = t.shape
+    if n == Np and t.is_contiguous():
+        return t
+    out = zeros(B, L_, P, Np, device=t.device, dtype=t.dtype)
+    return copy4d(t.contiguous(), (L_ * P * n, P * n, n, 1), out, (L_ * P * Np, P * Np, Np, 1), (B, L_, P, n))
+
+
+def outer_operands(x, y, dtype, multiple=8):
     """Transposed operands of the outer product: x, y [B, N, L, P] -> (xt, yt `dtype` [B, L, P, Np], Np) with the MSA depth
-    contiguous and zero-padded to Np = a multiple of 8 (the contraction length of the GEMM / fused kernel)."""
+    contiguous and zero-padded to Np = a multiple of `multiple`: 8 (the contraction granule of the GEMM route) or the fused
+    kernel's depth outer_depth(N)."""
     B, N, L_, P = x.shape
-    Np = (N + 7) // 8 * 8
+    Np = (N + multiple - 1) // multiple * multiple
     mk = zeros if Np != N else torch.empty  # only the K padding needs zeros
     xt = mk(B, L_, P, Np, device=x.device, dtype=dtype)
     yt = mk(B, L_, P, Np, device=x.device, dtype=dtype)
@@ -396,8 +419,8 @@ def outer_operands(x, y, dtype):
 
 
 def outer_product_ln_linear(x, y, gamma, beta, w, b, eps):
-    """Functional form (dispatcher op): x, y bf16 [B, N, L, 32] -> fp32 [B, L, L, Dout]."""
-    xt, yt, _ = outer_operands(x, y, x.dtype)
+    """Functional form (dispatcher op): x, y 16-bit [B, N, L, 32], any L >= 1 and N <= 128 -> fp32 [B, L, L, Dout]."""
+    xt, yt, _ = outer_operands(x, y, x.dtype, outer_depth(x.shape[1]) or 8)   # (N > 128: the kernel refuses the depth)
     wp, s, c = outer_fold(w, gamma, beta, b, x.dtype)
     out = torch.empty(x.shape[0], x.shape[2], x.shape[2], w.shape[0], device=x.device, dtype=F32)
     return outer_fused(xt, yt, wp, s, c, out, eps)
