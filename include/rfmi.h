@@ -240,8 +240,26 @@ int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int6
                          int64_t sym_ld, void* out, const int64_t o_strides[4], int B, int H, int N, int L, int d_head,
                          float* partial_ws, int64_t partial_ws_elems, void* stream);
 
+/* The contraction-split logits + softmax of the tied attention at ANY chain length 257 <= L <= 1024 (rf_version >= 20):
+ *   att[b,h,i,:] = softmax_j( sum_{n,d} q[b,n,h,i,d] k[b,n,h,j,d] )      (+ att_sym as in rf_tied_softmax)
+ * on 128-query x 256-key tiles, ceil(L / 128) x ceil(L / 256) of them per (b, h) and range of MSA rows.  q carries the position
+ * weights (fold them in with rf_gemm_desc.rs: there is no w; qscale is accepted for symmetry with rf_tied_logits and, as there
+ * with w == NULL, multiplies nothing).  q, k, qk_strides, att, att_ld, att_sym, sym_ld as in rf_tied_logits_ld: att_ld >= L
+ * (RF_EINVAL) and att_ld % 8 == 0 (RF_EALIGN); rows i >= L of att are not touched, columns L <= j < att_ld of every row are exact
+ * zeros, no source row >= L of q or k is addressed.  The split rule of rf_tied_logits holds: N even, split into 1, 2, 4, .. ranges
+ * until a range has <= 64 rows, and a range of 4 .. 64 and an even number of rows (RF_EINVAL otherwise, as for L outside
+ * 257 .. 1024 and d_head != 32).  At a length off 512 / 768 / 1024 the accepted ranges are halved further while fewer than 192
+ * workgroups (B * H * tiles * ranges) would run and a half still has a multiple of 2 and at least 4 rows.  partial_ws: fp32 workspace of at least rf_tied_logits_long_ws_elems(B, H, N, L) elements,
+ * 16-byte aligned (RF_EINVAL when NULL or shorter); that function returns ranges * B * H * L * 256 * ceil(L / 256), or 0 for a
+ * shape the entry point refuses.  L % 256 == 0 with att_ld == L launches the whole-tile instantiations, bit for bit
+ * rf_tied_logits; rf_tied_logits and rf_tied_logits_ld keep their own lengths. */
+int64_t rf_tied_logits_long_ws_elems(int B, int H, int N, int L);
+int rf_tied_logits_long(const void* q, const void* k, const int64_t qk_strides[4], float qscale, void* att, int64_t att_ld,
+                        float* att_sym, int64_t sym_ld, int B, int H, int N, int L, int d_head, float* partial_ws,
+                        int64_t partial_ws_elems, void* stream);
+
 /* Introspection for tests and measurement tools, like rf_rowops_last_route: the kernel instantiation the calling thread's last
- * successful rf_favor_attention, rf_tied_logits_softmax, rf_tied_logits(_ld), rf_tied_av(_ld), rf_tied_attention(_ld) or
+ * successful rf_favor_attention, rf_tied_logits_softmax, rf_tied_logits(_ld), rf_tied_logits_long, rf_tied_av(_ld), rf_tied_attention(_ld) or
  * rf_poswise_collapsed launched (-1 none; after a call that returned an error the value is unspecified).  Host-side only, no
  * kernel sees it.  rf_tied_attention(_ld) launches two kernels and leaves 1000 * (logits code) + (attention.V code).
  *   100 .. 111  rf_favor_attention, 4-wave kernel (RF_FAVOR4, and always the softmax features in the 256-row tile):
@@ -249,10 +267,11 @@ int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int6
  *   112 .. 121  rf_favor_attention, 8-wave kernel: 112 + the same three terms (the softmax features end at the 128-row tile)
  *   200 .. 215  tied logits, one-pass kernel: 200 + 4 * (tile / 64 - 1) + 2 * (w != NULL) + (tail: L < tile or att_ld != L)
  *   220 / 221   tied logits, contraction-split, L = 256: w == NULL / w != NULL
- *   222 / 224 / 226   tied logits, contraction-split, L = 512 / 768 / 1024 (w == NULL)
+ *   222 / 224 / 226   tied logits, contraction-split, L = 512 / 768 / 1024 (w == NULL); rf_tied_logits_long reports the code of
+ *               its key-block count, 220 + 2 * (ceil(L / 256) - 1), at any 257 <= L <= 1024, whole tiles or tail
  *   240 .. 247  attention . V: 240 + 2 * (tile / 64 - 1) + (tail)
- *   261 .. 268  rf_poswise_collapsed: 260 + N / 16
- *   272 / 276   rf_poswise_collapsed, N = 192 / 256 */
+ *   261 .. 268  rf_poswise_collapsed: 260 + NT, NT = ceil(N / 16) row tiles (N < 16 NT: the tail instantiation of that tile count)
+ *   272 / 276   rf_poswise_collapsed, 129 <= N <= 192 / 193 <= N <= 256 (NT = 12 / 16) */
 int rf_attn_last_route(void);
 
 /* Feed-forward block with its residual in ONE launch (FeedForward, rf.py:270-281, inside the residual wrappers of the
@@ -276,7 +295,10 @@ int rf_ffn_fused(const void* x, int64_t ldx, const void* w_packed, const float* 
 /* PositionWiseWeightFactor in collapsed form on the matrix pipe (rf.py:205-217):
  *   w[b,h,n,l] = softmax_n( scale * sum_c xn[b,n,l,c] * u[b,l,h,c] ),   u[b,l,h,:] = W_k[h*dh:(h+1)*dh, :]^T to_q(x_0)[b,l,h,:]
  * (to_k's bias is constant in n and cancels in the softmax, so the to_k projection over all N rows is never formed).
- * xn: bf16 [B,N,L,D]; u: bf16 [B,L,H,D]; w: fp32 [B,H,N,L].  H <= 16, D % 32 == 0, N % 16 == 0, N <= 256. */
+ * xn: bf16 [B,N,L,D]; u: bf16 [B,L,H,D]; w: fp32 [B,H,N,L].  H <= 16, D % 32 == 0, 1 <= N <= 256 (rf_version >= 20: before,
+ * N / 16 in {1..8, 12, 16} was required).  The kernel walks the MSA rows in MFMA tiles of 16, NT = the smallest of 1..8, 12, 16
+ * that holds ceil(N / 16); a depth that does not fill them runs the tail instantiation: no row >= N of xn is addressed, none of w
+ * is written, and N == 16 NT launches what it always did. */
 int rf_poswise_collapsed(const void* xn, const void* u, float* w, int B, int N, int L, int D, int H, float scale,
                          void* stream);
 

@@ -60,6 +60,8 @@ PROTOTYPES = {
     "rf_tied_av_ld": [vp, i64, vp, C.POINTER(I64x4), vp, C.POINTER(I64x4), i32, i32, i32, i32, i32, vp],
     "rf_tied_attention_ld": [vp, vp, vp, C.POINTER(I64x4), C.POINTER(I64x4), vp, C.POINTER(I64x3), f32, vp, i64, vp, i64, vp,
                              C.POINTER(I64x4), i32, i32, i32, i32, i32, vp, i64, vp],
+    "rf_tied_logits_long_ws_elems": [i32, i32, i32, i32],  # returns int64
+    "rf_tied_logits_long": [vp, vp, C.POINTER(I64x4), f32, vp, i64, vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
     "rf_ffn_fused": [vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, f32, i64, i32, i32, vp],
     "rf_outer_product_ln_linear": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, f32, vp, i64, vp],
     "rf_outer_product_ln_linear_rect": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, f32, vp, i64, vp],
@@ -148,6 +150,7 @@ def _load(path):
         _fn.argtypes = _args
         _fn.restype = C.c_int
     handle.rf_instnorm_ws_bytes.restype = C.c_int64
+    handle.rf_tied_logits_long_ws_elems.restype = C.c_int64
     handle.rf_channel_mean_ws_bytes.restype = C.c_int64
     handle.rf_conv_wgrad_ws_bytes.restype = C.c_int64
     handle.rf_layernorm_bwd_ws_bytes.restype = C.c_int64

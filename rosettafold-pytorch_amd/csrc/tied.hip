@@ -248,11 +248,20 @@ struct TiedSplitP {
   int64_t split_stride; // elements between the partial tensors of consecutive splits
   int B, H, N, nsplit, nper;  // nper = MSA rows per split (N = nsplit * nper)
   int L, nrb, nkb;            // L = 128 nrb = 256 nkb: query blocks of 128 rows x key blocks of 256 columns
+                              // (TAIL: any 257 <= L <= 1024, nrb = ceil(L / 128), nkb = ceil(L / 256))
+  int64_t ws_ld;              // TAIL: floats between rows of a partial tensor, 256 nkb (whole key tiles)
   int dbg;                    // RF_TIED_DBG (results WRONG when set): 2 fragments read once, 4 no MFMA, 8 no partial stores
 };
 
-template <bool SCALE>
+// TAIL: the chain has p.L residues, 257 <= L <= 1024, and fills neither its last query block nor its last key block.  The
+// residue row that a lane's DMA piece reads, for q and for k, is clamped to L - 1 of the same (b, n, h) slab (finite copies;
+// clamped, never skipped: every wave still issues PW DMAs per step, which the counted wait relies on), rows >= L of the partial
+// logits are not stored, and a partial tensor is [B][H][L][ws_ld] with ws_ld = 256 nkb, so that the 16-byte stores need no
+// column predicate: columns [L, ws_ld) receive the logits against the clamped key row, which tied_split_softmax_kernel never
+// reads into a result.  Long rows carry their weights in q (no SCALE form).  TAIL = false contains none of this.
+template <bool SCALE, bool TAIL>
 __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP p) {
+  static_assert(!(SCALE && TAIL), "the tail form takes q with the weights folded in");
   constexpr int KB = 256, RB = 128, NSTG = TIED_SPLIT_NSTG;  // a workgroup: 128 query rows x 256 keys (any L = 256 nkb)
   constexpr int Q_BYTES = RB * 64, K_BYTES = KB * 64, STAGE = Q_BYTES + K_BYTES;
   constexpr int QI = RB / 16, PW = 3;        // (QI + KB / 16) DMA pieces of 1 KB per stage = 3 per wave, no padding
@@ -283,6 +292,15 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
   const int lrow = lane >> 2;
   const int c_log = (lane & 3) ^ ((0x78 >> (((lrow >> 2) & 3) * 2)) & 3);
   const int64_t lane_off = (int64_t)lrow * p.l_stride + c_log * 8;
+  int64_t tail_off[PW];  // TAIL: this lane's source offset of piece t inside the (b, h) slab, its row clamped to L - 1
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int t = 0; t < PW; ++t) {
+      const int instr = t * 8 + wave;
+      const int row = (instr < QI ? rb * RB + instr * 16 : kbk * KB + (instr - QI) * 16) + lrow;
+      tail_off[t] = (int64_t)b * p.b_stride + (int64_t)h * p.h_stride + (int64_t)(row < L - 1 ? row : L - 1) * p.l_stride + c_log * 8;
+    }
+  }
   auto stage = [&](int t_) {  // t_: step index inside this split
     char* st = smem + (t_ % NSTG) * STAGE;
     const bool live = t_ < p.nper;
@@ -290,7 +308,12 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
 #pragma unroll
     for (int t = 0; t < PW; ++t) {
       const int instr = t * 8 + wave;
-      if (live && instr < QI)
+      if constexpr (TAIL) {
+        if (live)
+          rf_glds16((instr < QI ? p.q : p.k) + noff + tail_off[t], st + instr * 1024);
+        else
+          rf_glds16(g_tied_zero16, smem + DUMP);
+      } else if (live && instr < QI)
         rf_glds16(qb + noff + (int64_t)(instr * 16) * p.l_stride + lane_off, st + instr * 1024);
       else if (live)
         rf_glds16(kb + noff + (int64_t)((instr - QI) * 16) * p.l_stride + lane_off, st + instr * 1024);
@@ -351,6 +374,17 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
   }
   if (RF_DBG(p.dbg) & 8) return;
   // partial logits: 16-byte pieces, the four lanes of a row group cover 64 contiguous bytes, a wave's four key tiles 256
+  if constexpr (TAIL) {
+    const int row0 = rb * RB + wr * 64 + fr;
+    float* pt = p.part + (int64_t)sp * p.split_stride + (((int64_t)b * p.H + h) * L + row0) * p.ws_ld + kbk * KB + wc * 64 + 4 * fq;
+#pragma unroll
+    for (int qt = 0; qt < 4; ++qt)
+      if (row0 + qt * 16 < L) {
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) *(f32x4*)(pt + (int64_t)(qt * 16) * p.ws_ld + kt * 16) = acc[kt][qt];
+      }
+    return;
+  }
   float* pr = p.part + (int64_t)sp * p.split_stride + (((int64_t)b * p.H + h) * L + rb * RB + wr * 64 + fr) * L + kbk * KB + wc * 64 + 4 * fq;
 #pragma unroll
   for (int qt = 0; qt < 4; ++qt)
@@ -359,13 +393,54 @@ __global__ __launch_bounds__(512) void tied_logits_split_kernel(const TiedSplitP
 }
 
 // att[row, :] = softmax(sum_s part[s][row, :]) for L = 256 NC: one wave per row, 4 NC columns per lane
-template <int NC>
+// TAIL: the row holds `len` <= 256 NC logits at the workspace pitch 256 NC; columns >= len count as -inf (an exact 0 in the
+// sum and in att), the row is written at the pitch att_ld (a multiple of 8, so a lane's 4-column group never straddles it):
+// probabilities in [0, len), exact zeros in [len, att_ld).
+template <int NC, bool TAIL>
 __global__ __launch_bounds__(256) void tied_split_softmax_kernel(const float* part, int64_t split_stride, int nsplit,
-                                                                 h16_t* att, int64_t rows) {
+                                                                 h16_t* att, int64_t rows, int len, int64_t att_ld) {
   constexpr int L = 256 * NC;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  if constexpr (TAIL) {
+    f32x4 v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = *(const f32x4*)(part + row * L + c * 256 + lane * 4);
+    for (int s_ = 1; s_ < nsplit; ++s_)
+#pragma unroll
+      for (int c = 0; c < NC; ++c) v[c] += *(const f32x4*)(part + (int64_t)s_ * split_stride + row * L + c * 256 + lane * 4);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (c * 256 + lane * 4 + e >= len) v[c][e] = -INFINITY;
+        mx = fmaxf(mx, v[c][e]);
+      }
+    mx = wave_max(mx);
+    float sm = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[c][e] = __expf(v[c][e] - mx);
+        sm += v[c][e];
+      }
+    sm = wave_sum(sm);
+    const float inv = 1.f / sm;
+    h16_t* arow = att + row * att_ld;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (c * 256 + lane * 4 < att_ld) {
+        uint2 o;
+        o.x = rf_pack2_h16(v[c][0] * inv, v[c][1] * inv);
+        o.y = rf_pack2_h16(v[c][2] * inv, v[c][3] * inv);
+        *(uint2*)(arow + c * 256 + lane * 4) = o;
+      }
+    for (int64_t col = L + lane * 4; col < att_ld; col += 256) *(uint2*)(arow + col) = make_uint2(0u, 0u);  // (a pitch past the key tiles)
+    return;
+  }
   f32x4 v[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) v[c] = *(const f32x4*)(part + row * L + c * 256 + lane * 4);
@@ -429,16 +504,40 @@ static int launch_tied(const TiedP& p, hipStream_t s) {
   return rf_launch_status();
 }
 
+// MSA-row ranges of the split: 0 when the depth is outside the kernel (N odd, or a range of fewer than 4, more than 64 or an odd
+// number of rows)
+static int tied_split_count(int N, int L) {
+  if (N % 2) return 0;
+  int nsplit = L == 256 ? 2 : 1;  // (at L = 256 two splits keep >= 192 workgroups in flight; longer rows have enough tiles)
+  while (N / nsplit > 64 && N % (nsplit * 2) == 0) nsplit *= 2;
+  const int nper = N / nsplit;
+  return (nper > 64 || nper < 4 || (nper & 1)) ? 0 : nsplit;
+}
+
+// rf_tied_logits_long at a length off 512 / 768 / 1024: the ranges are halved further while fewer than 192 workgroups would be in
+// flight (the reason for the two ranges at L = 256: B = 1, 12 heads at L = 300 are 72 tiles) and a half stays a legal range.  Which
+// depths are accepted does not change, and the whole-tile lengths keep the ranges (and the bits) of rf_tied_logits.
+static int tied_long_split_count(int B, int H, int N, int L) {
+  int nsplit = tied_split_count(N, L);
+  if (!nsplit || L % 256 == 0) return nsplit;
+  const int64_t tiles = (int64_t)B * H * ((L + 127) / 128) * ((L + 255) / 256);
+  while (tiles * nsplit < 192 && (N / nsplit) % 4 == 0 && N / nsplit >= 8) nsplit *= 2;
+  return nsplit;
+}
+
 // contraction-split path: L = 256 .. 1024 in steps of 256, N splits into nsplit ranges of <= 64 rows, workspace of
 // nsplit * B*H*L*L floats
-static int tied_logits_split(const TiedP& p0, int L, float* ws, int64_t ws_elems, hipStream_t s) {
+// `ragged` (rf_tied_logits_long): any 257 <= L <= 1024 and the pitch p0.att_ld; the tail instantiations iff the chain does not
+// fill its key tiles or att is not dense, on a workspace of nsplit * B*H*L * 256 ceil(L / 256) floats
+static int tied_logits_split(const TiedP& p0, int L, float* ws, int64_t ws_elems, hipStream_t s, bool ragged = false) {
   static const bool off = rf_env_flag("RF_NO_TIED_SPLIT");
-  if (off || !ws || L % 256 || L > 1024 || p0.N % 2) return 1;  // 1 = not applicable: the caller falls back to the one-pass kernel
-  const int nrb = L / 128, nkb = L / 256;
-  int nsplit = L == 256 ? 2 : 1;  // (at L = 256 two splits keep >= 192 workgroups in flight; longer rows have enough tiles)
-  while (p0.N / nsplit > 64 && p0.N % (nsplit * 2) == 0) nsplit *= 2;
+  if (off || !ws || (!ragged && L % 256) || L > 1024 || p0.N % 2) return 1;  // 1 = not applicable: the caller falls back to the one-pass kernel
+  const bool tail = ragged && (L % 256 != 0 || p0.att_ld != L);
+  const int nrb = (L + 127) / 128, nkb = (L + 255) / 256;
+  const int nsplit = ragged ? tied_long_split_count(p0.B, p0.H, p0.N, L) : tied_split_count(p0.N, L);
+  if (!nsplit) return 1;
   const int nper = p0.N / nsplit;
-  const int64_t one = (int64_t)p0.B * p0.H * L * L;
+  const int64_t one = (int64_t)p0.B * p0.H * L * (tail ? 256 * nkb : L);
   if (nper > 64 || nper < 4 || (nper & 1) || ws_elems < one * nsplit || ((uintptr_t)ws % 16)) return 1;
   TiedSplitP p;
   p.q = p0.q; p.k = p0.k;
@@ -446,28 +545,38 @@ static int tied_logits_split(const TiedP& p0, int L, float* ws, int64_t ws_elems
   p.w = p0.w; p.w_b = p0.w_b; p.w_h = p0.w_h; p.w_n = p0.w_n; p.qscale = p0.qscale;
   p.part = ws; p.split_stride = one;
   p.B = p0.B; p.H = p0.H; p.N = p0.N; p.nsplit = nsplit; p.nper = nper;
-  p.L = L; p.nrb = nrb; p.nkb = nkb;
+  p.L = L; p.nrb = nrb; p.nkb = nkb; p.ws_ld = 256 * nkb;
   p.dbg = p0.dbg;
   const size_t lds = (size_t)TIED_SPLIT_NSTG * (128 * 64 + 256 * 64) + 1024 + (p.w ? (size_t)nper * 512 : 0);
   const int64_t grid64 = (int64_t)p.B * p.H * nrb * nkb * nsplit;
   if (grid64 > 0x7fffffffLL) return RF_EINVAL;
   const unsigned grid = (unsigned)grid64;
   g_attn_route = 220 + 2 * (nkb - 1) + (p.w ? 1 : 0);
-  if (p.w) {
-    if (const int e = rf_enable_big_lds<tied_logits_split_kernel<true>>()) return e;
-    hipLaunchKernelGGL(tied_logits_split_kernel<true>, dim3(grid), dim3(512), lds, s, p);
+  if (tail) {
+    if (p.w) return RF_EINVAL;
+    if (const int e = rf_enable_big_lds<tied_logits_split_kernel<false, true>>()) return e;
+    hipLaunchKernelGGL((tied_logits_split_kernel<false, true>), dim3(grid), dim3(512), lds, s, p);
+  } else if (p.w) {
+    if (const int e = rf_enable_big_lds<tied_logits_split_kernel<true, false>>()) return e;
+    hipLaunchKernelGGL((tied_logits_split_kernel<true, false>), dim3(grid), dim3(512), lds, s, p);
   } else {
-    if (const int e = rf_enable_big_lds<tied_logits_split_kernel<false>>()) return e;
-    hipLaunchKernelGGL(tied_logits_split_kernel<false>, dim3(grid), dim3(512), lds, s, p);
+    if (const int e = rf_enable_big_lds<tied_logits_split_kernel<false, false>>()) return e;
+    hipLaunchKernelGGL((tied_logits_split_kernel<false, false>), dim3(grid), dim3(512), lds, s, p);
   }
   const int64_t rows = (int64_t)p.B * p.H * L;
   const dim3 sg((unsigned)((rows + 3) / 4));
+#define RF_TIED_SM(NC_)                                                                                                          \
+  if (tail)                                                                                                                      \
+    hipLaunchKernelGGL((tied_split_softmax_kernel<NC_, true>), sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows, L, p0.att_ld); \
+  else                                                                                                                           \
+    hipLaunchKernelGGL((tied_split_softmax_kernel<NC_, false>), sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows, L, (int64_t)L)
   switch (nkb) {
-    case 1: hipLaunchKernelGGL(tied_split_softmax_kernel<1>, sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows); break;
-    case 2: hipLaunchKernelGGL(tied_split_softmax_kernel<2>, sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows); break;
-    case 3: hipLaunchKernelGGL(tied_split_softmax_kernel<3>, sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows); break;
-    default: hipLaunchKernelGGL(tied_split_softmax_kernel<4>, sg, dim3(256), 0, s, ws, one, nsplit, p0.att, rows); break;
+    case 1: RF_TIED_SM(1); break;
+    case 2: RF_TIED_SM(2); break;
+    case 3: RF_TIED_SM(3); break;
+    default: RF_TIED_SM(4); break;
   }
+#undef RF_TIED_SM
   return rf_launch_status();
 }
 
@@ -803,6 +912,42 @@ extern "C" int rf_tied_logits(const void* q, const void* k, const int64_t qk_str
                            partial_ws_elems, stream);
 }
 
+// The contraction-split form at any chain length 257 <= L <= 1024 and any row pitch att_ld >= L (a multiple of 8) of att:
+// att[b,h,i,:] = softmax_j sum_{n,d} q k in [0, L), exact zeros in [L, att_ld); q carries the position weights (no w).  The split
+// rule of rf_tied_logits holds (N even, ranges of 4 .. 64 and an even number of MSA rows), the workspace is required and holds
+// rf_tied_logits_long_ws_elems floats.  L % 256 == 0 with att_ld == L launches the whole-tile instantiations of rf_tied_logits.
+extern "C" int64_t rf_tied_logits_long_ws_elems(int B, int H, int N, int L) {
+  if (B <= 0 || H <= 0 || N <= 0 || L < 257 || L > 1024) return 0;
+  return (int64_t)tied_long_split_count(B, H, N, L) * B * H * L * (256 * ((L + 255) / 256));
+}
+
+extern "C" int rf_tied_logits_long(const void* q, const void* k, const int64_t qk_strides[4], float qscale, void* att,
+                                   int64_t att_ld, float* att_sym, int64_t sym_ld, int B, int H, int N, int L, int d_head,
+                                   float* partial_ws, int64_t partial_ws_elems, void* stream) {
+  if (!q || !k || !att || B <= 0 || H <= 0 || N <= 0) return RF_EINVAL;
+  if (d_head != 32 || L < 257 || L > 1024 || att_ld < L) return RF_EINVAL;
+  if (att_ld % 8) return RF_EALIGN;
+  if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16) || ((uintptr_t)partial_ws % 16)) return RF_EALIGN;
+  for (int i = 0; i < 4; ++i)
+    if (qk_strides[i] % 8) return RF_EALIGN;
+  const int64_t need = rf_tied_logits_long_ws_elems(B, H, N, L);
+  if (need <= 0 || !partial_ws || partial_ws_elems < need) return RF_EINVAL;
+  TiedP p;
+  p.q = (const h16_t*)q; p.k = (const h16_t*)k;
+  p.b_stride = qk_strides[0]; p.n_stride = qk_strides[1]; p.h_stride = qk_strides[2]; p.l_stride = qk_strides[3];
+  p.w = nullptr; p.w_b = p.w_h = p.w_n = 0;
+  p.qscale = qscale;
+  p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
+  p.len = L; p.att_ld = att_ld;
+  p.dbg = tied_dbg();
+  if (p.dbg < 0) return p.dbg;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = tied_logits_split(p, L, partial_ws, partial_ws_elems, s, true);
+  if (rc == 1) rc = RF_EINVAL;  // (RF_NO_TIED_SPLIT: long rows have no other kernel)
+  if (rc != 0) return rc;
+  return att_sym ? tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s) : 0;
+}
+
 // Tied attention core in one call: rf_tied_logits, then attention . V.  q / k / v / out strides: {b, n, h, l} in elements, the
 // 32-wide head slice contiguous.  L in {64, 128, 192, 256} (attention . V keeps whole probability rows in registers).
 extern "C" int rf_tied_attention_ld(const void* q, const void* k, const void* v, const int64_t qk_strides[4],
@@ -835,7 +980,10 @@ extern "C" int rf_tied_attention(const void* q, const void* k, const void* v, co
 //   D[n, h] = sum_c xn[b,n,l,c] u[b,l,h,c]   (N/16 row tiles of MFMA 16x16x32, heads padded to 16),
 //   w[b,h,n,l] = softmax_n(scale * D[n, h]).
 // ------------------------------------------------------------------------------------------------------------------
-template <int NT>  // NT = N / 16 row tiles
+// TAIL: N < 16 NT MSA rows (NT = the smallest instantiated tile count that holds them).  For rows >= N the load address is
+// clamped to row N - 1 (a finite copy), the scaled logit becomes -inf before the maximum (an exact 0 in the sum) and nothing is
+// stored.  TAIL = false contains none of this.
+template <int NT, bool TAIL>  // NT = ceil(N / 16) row tiles
 __global__ __launch_bounds__(256) void poswise_mfma_kernel(const h16_t* xn, const h16_t* u, float* w, int B, int N, int L,
                                                            int D, int H, float scale) {
   const int lane = threadIdx.x & 63;
@@ -852,7 +1000,10 @@ __global__ __launch_bounds__(256) void poswise_mfma_kernel(const h16_t* xn, cons
     const h16x8 uf = *(const h16x8*)(ur + c);
     h16x8 xf[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) xf[t] = *(const h16x8*)(xr + (int64_t)(t * 16 + fr) * L * D + c);
+    for (int t = 0; t < NT; ++t) {
+      const int n = TAIL && t * 16 + fr >= N ? N - 1 : t * 16 + fr;
+      xf[t] = *(const h16x8*)(xr + (int64_t)n * L * D + c);
+    }
 #pragma unroll
     for (int t = 0; t < NT; ++t)
       // MSA rows as MFMA-A, heads as MFMA-B: lane holds D[n = 16 t + 4 fq + r][h = fr]
@@ -864,6 +1015,7 @@ __global__ __launch_bounds__(256) void poswise_mfma_kernel(const h16_t* xn, cons
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       acc[t][r] *= scale;
+      if (TAIL && t * 16 + 4 * fq + r >= N) acc[t][r] = -INFINITY;
       mx = fmaxf(mx, acc[t][r]);
     }
   mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -884,22 +1036,28 @@ __global__ __launch_bounds__(256) void poswise_mfma_kernel(const h16_t* xn, cons
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) wo[(int64_t)(t * 16 + 4 * fq + r) * L] = acc[t][r] * inv;
+      for (int r = 0; r < 4; ++r)
+        if (!TAIL || t * 16 + 4 * fq + r < N) wo[(int64_t)(t * 16 + 4 * fq + r) * L] = acc[t][r] * inv;
   }
 }
 
 extern "C" int rf_poswise_collapsed(const void* xn, const void* u, float* w, int B, int N, int L, int D, int H, float scale,
                                     void* stream) {
   if (!xn || !u || !w || B <= 0 || L <= 0) return RF_EINVAL;
-  if (H < 1 || H > 16 || D % 32 || N % 16 || N < 16 || N > 256) return RF_EINVAL;
+  if (H < 1 || H > 16 || D % 32 || N < 1 || N > 256) return RF_EINVAL;
   if (((uintptr_t)xn % 16) || ((uintptr_t)u % 16)) return RF_EALIGN;
   const unsigned grid = (unsigned)(((int64_t)B * L + 3) / 4);
   hipStream_t s = (hipStream_t)stream;
+  // the smallest instantiated tile count that holds the N rows; the tail instantiation iff they do not fill it
 #define RF_PW(NT_)                                                                                                           \
-  if (N == 16 * NT_) {                                                                                                       \
+  if (N <= 16 * NT_) {                                                                                                       \
     g_attn_route = 260 + NT_;                                                                                                \
-    hipLaunchKernelGGL(poswise_mfma_kernel<NT_>, dim3(grid), dim3(256), 0, s, (const h16_t*)xn, (const h16_t*)u, w, B, N, \
-                       L, D, H, scale);                                                                                      \
+    if (N == 16 * NT_)                                                                                                       \
+      hipLaunchKernelGGL((poswise_mfma_kernel<NT_, false>), dim3(grid), dim3(256), 0, s, (const h16_t*)xn, (const h16_t*)u, \
+                         w, B, N, L, D, H, scale);                                                                           \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((poswise_mfma_kernel<NT_, true>), dim3(grid), dim3(256), 0, s, (const h16_t*)xn, (const h16_t*)u,  \
+                         w, B, N, L, D, H, scale);                                                                           \
     return rf_launch_status();                                                                                               \
   }
   RF_PW(1) RF_PW(2) RF_PW(3) RF_PW(4) RF_PW(5) RF_PW(6) RF_PW(7) RF_PW(8) RF_PW(12) RF_PW(16)

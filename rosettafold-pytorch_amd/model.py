@@ -716,18 +716,23 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         _check_backward_call(self, tape, None, D, dh)
         if tape is not None:
             tape.update(xn=xn, drops=[], pw={"drop": None}, w_order="bhnl")
+        # (any MSA depth 1 <= N <= 256: rf_poswise_collapsed pads its last tile of 16 rows inside the kernel; weights applied in
+        # the logits kernel are staged four MSA rows at a time, so a depth off a multiple of 4 needs them folded into q)
         if (RT.fused_tied and RT.tied_v2 and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256) and H <= 16
-                and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16) and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384
+                and 1 <= N <= 256 and (N % 4 == 0 or self.folds_weights(B * N * Lr))
+                and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384
                 and (6 if Lr >= 256 else 8) * (4096 + Lr * 64) + 1024 + N * 256 <= 160 * 1024):
             return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
         if (RT.fused_tied and RT.tied_v2 and Lr not in ops.TIED_TILES and Lr >= TIED_RAGGED_MIN_L
                 and ops.tied_fused_applies(Lr, N, T(), dh, w=not self.folds_weights(B * N * Lr)) and H <= 16
-                and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)):
+                and 1 <= N <= 256):
             # a chain that fills no tile: the same route on the tail instantiations of the kernels (rf_tied_attention_ld)
             return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
-        if (RT.fused_tied and RT.tied_v2 and RT.tied_fold_w and ops.is_h16(T()) and dh == 32 and Lr in (512, 768, 1024) and H <= 16
-                and ops.gemm_takes_row_scale(B * N * Lr, 2 * D, D) and N % 16 == 0 and N // 16 in (1, 2, 3, 4, 5, 6, 7, 8, 12, 16)
-                and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384):
+        if (RT.fused_tied and RT.tied_v2 and RT.tied_fold_w and 256 < Lr <= 1024 and H <= 16 and 1 <= N <= 256
+                and (Lr in (512, 768, 1024) or RT.tied_long_ragged) and ops.tied_long_applies(Lr, N, T(), dh)
+                and ops.gemm_takes_row_scale(B * N * Lr, 2 * D, D)):
+            # (the projection is the only kernel on this route with a condition on the row count, B * N * Lr % 64 == 0 and
+            # >= 16384, and gemm_takes_row_scale states it)
             return self.attend_long_rows(xn, x_res, want_att, next_ln, drops, tape)
         if tape is not None:
             tape["w_order"] = "bnhl"
@@ -833,9 +838,11 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         return att_sym, xn_next
 
     def attend_long_rows(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
-        """L in {512, 768, 1024} (BASELINE.json configs[3]).  Same front as attend_head_major -- collapsed position weights, one
-        projection GEMM writing q|k head-major with w * d_head^-0.5 folded into q on the fp32 accumulators -- then the
-        contraction-split logits kernel over 128-query x 256-key tiles (csrc/tied.hip: rf_tied_logits).  attention . V at
+        """Any 256 < L <= 1024 (L in {512, 768, 1024}: BASELINE.json configs[3]; every other length runs the tail instantiations
+        of the same kernel through ops.tied_logits_long, with the map's row pitch map_ld(L)).  Same front as
+        attend_head_major -- collapsed position weights, one projection GEMM writing q|k head-major with w * d_head^-0.5
+        folded into q on the fp32 accumulators -- then the contraction-split logits kernel over 128-query x 256-key tiles
+        (csrc/tied.hip: rf_tied_logits, rf_tied_logits_long).  attention . V at
         these lengths is a plain large GEMM per (b, head) (M = L queries, K = L keys, N = n_seq * 32): it goes to rf_gemm with
         v written key-contiguous by its projection (keeping whole probability rows in registers, as the L <= 256 kernel
         does, would need 128 VGPRs per 16 query rows)."""
@@ -848,9 +855,9 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         qk = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
         ops.gemm(xn, self.wcat("qk", lins), qk, B * N * Lr, 2 * D, D, bias=self.bcat("qk", lins),
                  c_row=(Lr, G * Lr * dh, dh), c_col=(dh, Lr * dh), rs=(w, H * N * Lr, N * Lr, dh, D, self.scale))
-        att = torch.empty(B, H, Lr, Lr, device=dev, dtype=T())
+        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by the logits kernel)
         att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
-        ops.tied_logits(qk[:, :, 0:H], qk[:, :, H:], att, att_sym)
+        (ops.tied_logits if Lr in (512, 768, 1024) else ops.tied_logits_long)(qk[:, :, 0:H], qk[:, :, H:], att, att_sym)
         bv, bo = _f(self.to_v.bias), _f(self.to_out.bias)
         if RT.condition and RT.condition_values:
             bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))

@@ -339,6 +339,48 @@ def tied_logits(q, k, att, att_sym=None, qscale=1.0):
     return att
 
 
+def _tied_long_splits(N, B=1, H=1, L_=512):
+    """MSA-row ranges of the contraction-split logits kernel above L = 256 (csrc/tied.hip: tied_split_count, and at a length off
+    512 / 768 / 1024 tied_long_split_count: halved further while fewer than 192 workgroups would run); 0: N is outside it"""
+    if N < 1 or N % 2:
+        return 0
+    nsplit = 1
+    while N // nsplit > 64 and N % (2 * nsplit) == 0:
+        nsplit *= 2
+    nper = N // nsplit
+    if not (4 <= nper <= 64 and nper % 2 == 0):
+        return 0
+    if L_ % 256:
+        tiles = B * H * ((L_ + 127) // 128) * ((L_ + 255) // 256)
+        while tiles * nsplit < 192 and (N // nsplit) % 4 == 0 and N // nsplit >= 8:
+            nsplit *= 2
+    return nsplit
+
+
+def tied_long_applies(L_, N, dtype, dh=32):
+    """Python mirror of what rf_tied_logits_long accepts: 16-bit operands, d_head 32, 257 <= L <= 1024, N even and split into
+    ranges of 4 .. 64 and an even number of MSA rows."""
+    return bool(is_h16(dtype) and dh == 32 and 257 <= L_ <= 1024 and _tied_long_splits(N))
+
+
+def tied_logits_long(q, k, att, att_sym=None, qscale=1.0):
+    """tied_logits at any chain length 257 <= L <= 1024 (rf_tied_logits_long: the tail instantiations of the contraction-split
+    kernel): att 16-bit [B, H, L, att_ld], att_ld >= L a multiple of 8, zeros written past column L."""
+    B, N, H, L_, dh = q.shape
+    att_ld = _att_ld(att, L_)
+    # (rf_tied_logits_long_ws_elems: MSA-row ranges x rows x whole key tiles of 256 columns; a refused shape gets 4 floats and the
+    # library's answer)
+    ws = torch.empty(max(_tied_long_splits(N, B, H, L_) * B * H * L_ * 256 * ((L_ + 255) // 256), 4), device=q.device, dtype=F32)
+    _need_cuda(q, k, att, att_sym, ws)
+    if q.stride() != k.stride():
+        raise ValueError("q and k must share their strides")
+    check(lib.rf_tied_logits_long(ptr(q), ptr(k), C.byref(_hstrides(q)), float(qscale), ptr(att), att_ld, ptr(att_sym),
+                                  att_sym.shape[-1] if att_sym is not None else 0, B, H, N, L_, dh, ptr(ws), ws.numel(), stream()),
+          "rf_tied_logits_long")
+    COUNTERS["tied_logits_long"] += 1
+    return att
+
+
 def tied_row_attention(q, k, v):
     """Functional form for the dispatcher op: q, k, v h16 [B, N, L, H, 32] -> (out [B, N, L, H*32], att_sym [B, L, L, H]).
     L in TIED_TILES, or any 1 <= L <= 256 (the attention map then has the leading dimension tied_ld(L): rf_tied_attention_ld)."""

@@ -40,6 +40,9 @@ class _Runtime:
     outer_bwd_fused = not bool(int(__import__("os").environ.get("RF_NO_FUSED_OUTER_BWD", "0")))
     tied_v2 = not bool(int(__import__("os").environ.get("RF_TIED_V1", "0")))  # head-major q|k|v + collapsed weights + A.V kernel
     tied_fold_w = not bool(int(__import__("os").environ.get("RF_TIED_NO_FOLD", "0")))  # position weights folded into q by the projection's epilogue
+    # long rows off 512 / 768 / 1024 (any 257 <= L <= 1024) on the tail instantiations of the contraction-split logits kernel;
+    # RF_NO_TIED_LONG_RAGGED=1 restores the general route at these lengths, for A/B timing (tools/tied_long_ragged_bench.py)
+    tied_long_ragged = not bool(int(__import__("os").environ.get("RF_NO_TIED_LONG_RAGGED", "0")))
     # pair-track row blocks (shard.forward_row_sharded): how the attention direction that crosses the blocks is computed --
     # "transpose" (two transposing exchanges, fused kernel) or "contexts" (all-reduce of the Performer contexts, GEMM chain)
     rowshard_attention = __import__("os").environ.get("RF_ROWSHARD_ATTENTION", "transpose")
