@@ -609,25 +609,41 @@ static int tied_sym(const void* att, int64_t att_ld, float* att_sym, int64_t sym
   return rf_launch_status();
 }
 
+// the logits entry points: q / k / att on 16 bytes, the q | k strides {b, n, h, l} on 8 elements
+static int tied_qk_align(const void* q, const void* k, const void* att, const int64_t qk_strides[4]) {
+  if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16)) return RF_EALIGN;
+  for (int i = 0; i < 4; ++i)
+    if (qk_strides[i] % 8) return RF_EALIGN;
+  return 0;
+}
+
+// ... and their arguments as a TiedP (w null: q is used as it is; p.dbg < 0: the caller returns it)
+static TiedP tied_params(const void* q, const void* k, const int64_t qk_strides[4], const float* w, const int64_t w_strides[3],
+                         float qscale, void* att, int64_t att_ld, int B, int H, int N, int L) {
+  TiedP p;
+  p.q = (const h16_t*)q; p.k = (const h16_t*)k;
+  p.b_stride = qk_strides[0]; p.n_stride = qk_strides[1]; p.h_stride = qk_strides[2]; p.l_stride = qk_strides[3];
+  p.w = w;
+  p.w_b = w ? w_strides[0] : 0; p.w_h = w ? w_strides[1] : 0; p.w_n = w ? w_strides[2] : 0;
+  p.qscale = qscale;
+  p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
+  p.len = L; p.att_ld = att_ld;
+  p.dbg = tied_dbg();
+  return p;
+}
+
 extern "C" int rf_tied_logits_softmax(const void* q, const void* k, int64_t b_stride, int64_t n_stride, int64_t l_stride,
                                       void* att, float* att_sym, int64_t sym_ld, int B, int H, int N, int L, int d_head,
                                       void* stream) {
   if (!q || !k || !att || B <= 0 || H <= 0 || N <= 0) return RF_EINVAL;
   if (d_head != 32 || (L != 64 && L != 128 && L != 192 && L != 256)) return RF_EINVAL;  // (the caller falls back to rf_gemm + rf_tied_softmax)
-  if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16) || b_stride % 8 || n_stride % 8 || l_stride % 8)
-    return RF_EALIGN;
-  TiedP p;
-  p.q = (const h16_t*)q; p.k = (const h16_t*)k;
-  p.b_stride = b_stride; p.n_stride = n_stride; p.l_stride = l_stride; p.h_stride = d_head;
-  p.w = nullptr; p.w_b = p.w_h = p.w_n = 0; p.qscale = 1.f;
-  p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
-  p.len = L; p.att_ld = L;
-  p.dbg = tied_dbg();
+  const int64_t qk_strides[4] = {b_stride, n_stride, d_head, l_stride};  // (head h: the columns h * d_head .. of a row)
+  if (const int e = tied_qk_align(q, k, att, qk_strides)) return e;
+  const TiedP p = tied_params(q, k, qk_strides, nullptr, nullptr, 1.f, att, L, B, H, N, L);
   if (p.dbg < 0) return p.dbg;
   hipStream_t s = (hipStream_t)stream;
   const int rc = tied_logits_dispatch(p, s);
-  if (rc != 0 || !att_sym) return rc;
-  return tied_sym(att, L, att_sym, sym_ld, B, H, L, s);
+  return rc == 0 && att_sym ? tied_sym(att, L, att_sym, sym_ld, B, H, L, s) : rc;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -880,28 +896,16 @@ extern "C" int rf_tied_logits_ld(const void* q, const void* k, const int64_t qk_
   const bool dense = att_ld == L;
   if (d_head != 32 || att_ld < L || !(small || (dense && L > 0 && L % 256 == 0 && L <= 1024))) return RF_EINVAL;
   if (att_ld % 8) return RF_EALIGN;
-  if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16)) return RF_EALIGN;
-  for (int i = 0; i < 4; ++i)
-    if (qk_strides[i] % 8) return RF_EALIGN;
+  if (const int e = tied_qk_align(q, k, att, qk_strides)) return e;
   if (w && (((uintptr_t)w % 16) || w_strides[0] % 4 || w_strides[1] % 4 || w_strides[2] % 4)) return RF_EALIGN;
   if (w && N % 4) return RF_EINVAL;  // the weight tile is staged four MSA rows per DMA instruction
   if (w && !small) return RF_EINVAL; // long rows: fold the weights into q (rf_gemm_desc.rs)
-  TiedP p;
-  p.q = (const h16_t*)q; p.k = (const h16_t*)k;
-  p.b_stride = qk_strides[0]; p.n_stride = qk_strides[1]; p.h_stride = qk_strides[2]; p.l_stride = qk_strides[3];
-  p.w = w;
-  p.w_b = w ? w_strides[0] : 0; p.w_h = w ? w_strides[1] : 0; p.w_n = w ? w_strides[2] : 0;
-  p.qscale = qscale;
-  p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
-  p.len = L; p.att_ld = att_ld;
-  p.dbg = tied_dbg();
+  const TiedP p = tied_params(q, k, qk_strides, w, w_strides, qscale, att, att_ld, B, H, N, L);
   if (p.dbg < 0) return p.dbg;
   hipStream_t s = (hipStream_t)stream;
   int rc = dense ? tied_logits_split(p, L, partial_ws, partial_ws_elems, s) : 1;
   if (rc == 1) rc = small ? tied_logits_dispatch(p, s) : RF_EINVAL;  // (long rows have no one-pass kernel: the workspace is required)
-  if (rc != 0) return rc;
-  if (att_sym && (rc = tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s)) != 0) return rc;
-  return 0;
+  return rc == 0 && att_sym ? tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s) : rc;
 }
 
 extern "C" int rf_tied_logits(const void* q, const void* k, const int64_t qk_strides[4], const float* w,
@@ -926,26 +930,16 @@ extern "C" int rf_tied_logits_long(const void* q, const void* k, const int64_t q
                                    float* partial_ws, int64_t partial_ws_elems, void* stream) {
   if (!q || !k || !att || B <= 0 || H <= 0 || N <= 0) return RF_EINVAL;
   if (d_head != 32 || L < 257 || L > 1024 || att_ld < L) return RF_EINVAL;
-  if (att_ld % 8) return RF_EALIGN;
-  if (((uintptr_t)q % 16) || ((uintptr_t)k % 16) || ((uintptr_t)att % 16) || ((uintptr_t)partial_ws % 16)) return RF_EALIGN;
-  for (int i = 0; i < 4; ++i)
-    if (qk_strides[i] % 8) return RF_EALIGN;
+  if (att_ld % 8 || ((uintptr_t)partial_ws % 16)) return RF_EALIGN;
+  if (const int e = tied_qk_align(q, k, att, qk_strides)) return e;
   const int64_t need = rf_tied_logits_long_ws_elems(B, H, N, L);
   if (need <= 0 || !partial_ws || partial_ws_elems < need) return RF_EINVAL;
-  TiedP p;
-  p.q = (const h16_t*)q; p.k = (const h16_t*)k;
-  p.b_stride = qk_strides[0]; p.n_stride = qk_strides[1]; p.h_stride = qk_strides[2]; p.l_stride = qk_strides[3];
-  p.w = nullptr; p.w_b = p.w_h = p.w_n = 0;
-  p.qscale = qscale;
-  p.att = (h16_t*)att; p.B = B; p.H = H; p.N = N;
-  p.len = L; p.att_ld = att_ld;
-  p.dbg = tied_dbg();
+  const TiedP p = tied_params(q, k, qk_strides, nullptr, nullptr, qscale, att, att_ld, B, H, N, L);
   if (p.dbg < 0) return p.dbg;
   hipStream_t s = (hipStream_t)stream;
   int rc = tied_logits_split(p, L, partial_ws, partial_ws_elems, s, true);
   if (rc == 1) rc = RF_EINVAL;  // (RF_NO_TIED_SPLIT: long rows have no other kernel)
-  if (rc != 0) return rc;
-  return att_sym ? tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s) : 0;
+  return rc == 0 && att_sym ? tied_sym(att, att_ld, att_sym, sym_ld, B, H, L, s) : rc;
 }
 
 // Tied attention core in one call: rf_tied_logits, then attention . V.  q / k / v / out strides: {b, n, h, l} in elements, the

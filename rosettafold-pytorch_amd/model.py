@@ -685,7 +685,11 @@ class SoftTiedAttentionOverResidues(RecordingModule):
     operands from the saved input on the general route and differentiates the unconditioned function: value_conditioning is an
     identity for any constant.  to_k.bias and poswise_weight.to_k.bias get exact zeros: each adds a constant to every logit of
     a softmax row.  d_msa and d_msa / n_heads must be multiples of 8 while recording.  EncoderLayer.run and everything above it
-    call attend() without a tape: they never record here."""
+    call attend() without a tape: they never record here.
+
+    attend() runs the route that route(B, N, L) names (ROUTES).  The stages the routes share are written once: maps,
+    value_biases, head_major_front, into_residual, and general_operands for the training-mode forward and _backward."""
+    ROUTES = ("head_major", "long_rows", "general_fused_logits", "general")
 
     def __init__(self, d_msa=384, n_heads=12, p_dropout=0.1, return_att=False):
         super().__init__()
@@ -710,75 +714,130 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         dropout record ("pw") and the layout its mask was drawn over ("w_order": "bhnl" on the head-major and long-row routes,
         "bnhl" on the general one) -- while the route the shape takes runs unchanged: same kernels, same numbers."""
         B, N, Lr, D = xn.shape
-        H, dh = self.n_heads, self.d_head
-        dev = xn.device
-        pw = self.poswise_weight
-        _check_backward_call(self, tape, None, D, dh)
+        _check_backward_call(self, tape, None, D, self.d_head)
+        route = self.route(B, N, Lr)
         if tape is not None:
-            tape.update(xn=xn, drops=[], pw={"drop": None}, w_order="bhnl")
+            tape.update(xn=xn, drops=[], pw={"drop": None}, w_order="bnhl" if route.startswith("general") else "bhnl")
+        if route.startswith("general"):
+            return self.attend_general(xn, x_res, want_att, next_ln, drops, tape, fused_logits=route == "general_fused_logits")
+        return (self.attend_head_major if route == "head_major" else self.attend_long_rows)(xn, x_res, want_att, next_ln, drops, tape)
+
+    def route(self, B, N, Lr):
+        """The one of ROUTES that attend() takes at xn [B,N,L,D] ("general_fused_logits": the general route with
+        rf_tied_logits_softmax), from the shape, T(), the RT switches and the ops.*_applies predicates: no tensor, no launch.
+        tests/golden/tied_routes.json holds its answers over a grid, quirks included: a whole tile counts the position-weight
+        tile in LDS even when the weights are folded into q, and has floors on the row count that other chains lack."""
+        H, dh, rows, h16, tile = self.n_heads, self.d_head, B * N * Lr, ops.is_h16(T()), Lr in ops.TIED_TILES
+        D = H * dh
         # (any MSA depth 1 <= N <= 256: rf_poswise_collapsed pads its last tile of 16 rows inside the kernel; weights applied in
         # the logits kernel are staged four MSA rows at a time, so a depth off a multiple of 4 needs them folded into q)
-        if (RT.fused_tied and RT.tied_v2 and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256) and H <= 16
-                and 1 <= N <= 256 and (N % 4 == 0 or self.folds_weights(B * N * Lr))
-                and (B * N * Lr) % 256 == 0 and B * N * Lr >= 16384
-                and (6 if Lr >= 256 else 8) * (4096 + Lr * 64) + 1024 + N * 256 <= 160 * 1024):
-            return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
-        if (RT.fused_tied and RT.tied_v2 and Lr not in ops.TIED_TILES and Lr >= TIED_RAGGED_MIN_L
-                and ops.tied_fused_applies(Lr, N, T(), dh, w=not self.folds_weights(B * N * Lr)) and H <= 16
-                and 1 <= N <= 256):
-            # a chain that fills no tile: the same route on the tail instantiations of the kernels (rf_tied_attention_ld)
-            return self.attend_head_major(xn, x_res, want_att, next_ln, drops, tape)
-        if (RT.fused_tied and RT.tied_v2 and RT.tied_fold_w and 256 < Lr <= 1024 and H <= 16 and 1 <= N <= 256
-                and (Lr in (512, 768, 1024) or RT.tied_long_ragged) and ops.tied_long_applies(Lr, N, T(), dh)
-                and ops.gemm_takes_row_scale(B * N * Lr, 2 * D, D)):
-            # (the projection is the only kernel on this route with a condition on the row count, B * N * Lr % 64 == 0 and
-            # >= 16384, and gemm_takes_row_scale states it)
-            return self.attend_long_rows(xn, x_res, want_att, next_ln, drops, tape)
-        if tape is not None:
-            tape["w_order"] = "bnhl"
-        # one GEMM for q | k | poswise-k  (N = 3D)
-        wcat = self.wcat("qkp", [self.to_q, self.to_k, pw.to_k[0]])
-        bcat = self.bcat("qkp", [self.to_q, self.to_k, pw.to_k[0]])
-        qkp = ops.linear(xn, wcat, bcat)  # [B,N,L,3D]
+        if RT.fused_tied and RT.tied_v2 and H <= 16 and 1 <= N <= 256:
+            fold = self.folds_weights(rows)
+            if tile:
+                if (h16 and dh == 32 and (N % 4 == 0 or fold) and rows % 256 == 0 and rows >= 16384
+                        and ops.tied_lds_fits(Lr, N)):
+                    return "head_major"
+            elif Lr >= TIED_RAGGED_MIN_L and ops.tied_fused_applies(Lr, N, T(), dh, w=not fold):
+                # a chain that fills no tile: the same route on the tail instantiations of the kernels (rf_tied_attention_ld)
+                return "head_major"
+            # (the projection is the only kernel on the long-row route with a condition on the row count, B * N * Lr % 64 == 0
+            # and >= 16384, and gemm_takes_row_scale states it)
+            if (RT.tied_fold_w and 256 < Lr <= 1024 and (Lr in (512, 768, 1024) or RT.tied_long_ragged)
+                    and ops.tied_long_applies(Lr, N, T(), dh) and ops.gemm_takes_row_scale(rows, 2 * D, D)):
+                return "long_rows"
+        return "general_fused_logits" if RT.fused_tied and h16 and dh == 32 and tile else "general"
+
+    # the stages every route shares ---------------------------------------------------------------------------------------------
+    def maps(self, B, Lr, dev, want_att):
+        """(att T [B,H,L,map_ld(L)]: the kernel that fills it writes zeros in the pad columns; fp32 [B,L,L,H] for the symmetrised
+        map when wanted, else None)"""
+        return (torch.empty(B, self.n_heads, Lr, map_ld(Lr), device=dev, dtype=T()),
+                torch.empty(B, Lr, Lr, self.n_heads, device=dev, dtype=F32) if want_att else None)
+
+    def value_biases(self, xn, lead=(), h16_only=False):
+        """(bias of the projection whose output columns are [lead..., v], bias of to_out): value_conditioning's where it is switched
+        on, else the plain ones.  h16_only: the general route also runs in float32 and conditions in the 16-bit modes only."""
+        if RT.condition and RT.condition_values and (ops.is_h16(T()) or not h16_only):
+            return tuple(t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out, lead=lead))
+        return (self.bcat("qkv", [*lead, self.to_v]) if lead else _f(self.to_v.bias)), _f(self.to_out.bias)
+
+    def into_residual(self, out, bo, x_res, next_ln, drops, tape):
+        """x_res += to_out(out) with the output dropouts (their records onto the tape) -> next_ln(x_res) when fused, else None"""
+        return project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
+                                     recs=tape["drops"] if tape is not None else None)
+
+    def head_major_front(self, xn, key, lins, fold, tape):
+        """Both head-major routes: the position weights w fp32 [B,H,N,L] from the collapsed form (no to_k projection over the N
+        rows) and one GEMM projecting `lins` (q | k | v or q | k) head-major, [B,N,G,L,32] with G = len(lins) * H: every
+        contraction step of the attention kernels is then one contiguous tile.  fold: q * w * d_head^-0.5 (rf.py:252) in that
+        GEMM's epilogue, on the fp32 accumulators, so q is rounded once and the logits kernel sees no weights.
+        -> (w, the projection, to_out's bias from value_biases when v is projected here, else None)"""
+        B, N, Lr, D = xn.shape
+        H, dh, G = self.n_heads, self.d_head, len(lins) * self.n_heads
+        w = self.poswise_weight.weights_head_major(xn, tape["pw"] if tape is not None else None)
+        proj = torch.empty(B, N, G, Lr, dh, device=xn.device, dtype=T())
+        if not fold and Lr % 4:
+            # the logits kernel stages w by 16-byte pieces: rows padded to a multiple of 4 floats (the pad is read, its values
+            # scale query rows past the chain only, which are never stored)
+            Lw = (Lr + 3) // 4 * 4
+            w = ops.copy4d(w, (H * N * Lr, N * Lr, Lr, 1), ops.zeros(B, H, N, Lw, device=xn.device, dtype=F32),
+                           (H * N * Lw, N * Lw, Lw, 1), (B, H, N, Lr))
+        bias, bo = self.value_biases(xn, lead=lins[:-1]) if lins[-1] is self.to_v else (self.bcat(key, lins), None)
+        ops.gemm(xn, self.wcat(key, lins), proj, B * N * Lr, len(lins) * D, D, bias=bias, c_row=(Lr, G * Lr * dh, dh),
+                 c_col=(dh, Lr * dh), rs=(w, H * N * Lr, N * Lr, dh, D, self.scale) if fold else None)
+        return w, proj, bo
+
+    def general_operands(self, xn, drop=None):
+        """The general route's operands: one GEMM for q | k | poswise-k [B,N,L,3D], w = softmax_n(q0 . k_pw * scale) and q~ = q w
+        d_head^-0.5 (rf.py:252).  drop None: the poswise kernel writes q~ over the q block and w never exists as a tensor;
+        returns (qkp, None, None).  Else drop(w) drops w fp32 [B,N,H,L] in place between the softmax and the scaling; returns
+        (qkp with q as projected, the dropped weights per (token, head) fp32 [B,N,L,H], q~ T [B,N,L,D])."""
+        B, N, Lr, D = xn.shape
+        H, dh, dev, W3 = self.n_heads, self.d_head, xn.device, 3 * D
+        pw = self.poswise_weight
+        lins = [self.to_q, self.to_k, pw.to_k[0]]
+        qkp = ops.linear(xn, self.wcat("qkp", lins), self.bcat("qkp", lins))
         q0 = pw.query_proj(xn)
-        # w = softmax_n(q0.k_pw * scale);  q <- q * w * scale   (rf.py:252)
-        if pw.training and pw.p_dropout and pw.p_dropout > 0:
-            # training mode: the weights exist as a tensor so that the dropout can sit between the softmax and the scaling
-            w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
-            ops.poswise(q0, D, qkp, 3 * D, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
-            pw.drop(w, tape["pw"] if tape is not None else None)
-            wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
-                            (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))
-            ops.axpby(wl, self.scale, None, 0.0, wl)
-            qc = ops.copy4d(qkp, (N * Lr * 3 * D, Lr * 3 * D, 3 * D, 1), torch.empty(B, N, Lr, D, device=dev, dtype=T()),
-                            (N * Lr * D, Lr * D, D, 1), (B, N, Lr, D))
-            ops.scale_rows(qc, wl, B * N * Lr * H, dh, out=qc)
-            ops.copy4d(qc, (N * Lr * D, Lr * D, D, 1), qkp, (N * Lr * 3 * D, Lr * 3 * D, 3 * D, 1), (B, N, Lr, D))
-        else:
-            ops.poswise(q0, D, qkp, 3 * D, 2 * D, dh, dh, None, qkp, 3 * D, 0, dh, B, N, Lr, H, pw.scale, self.scale)
-        # v transposed: v_t[b,n,(h,d),l]
-        bv, bo = _f(self.to_v.bias), _f(self.to_out.bias)
-        if RT.condition and RT.condition_values and ops.is_h16(T()):
-            bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))
+        if drop is None:
+            ops.poswise(q0, D, qkp, W3, 2 * D, dh, dh, None, qkp, W3, 0, dh, B, N, Lr, H, pw.scale, self.scale)
+            return qkp, None, None
+        w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
+        ops.poswise(q0, D, qkp, W3, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
+        drop(w)
+        wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
+                        (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))
+        del w
+        qt = ops.copy4d(qkp, (N * Lr * W3, Lr * W3, W3, 1), torch.empty(B, N, Lr, D, device=dev, dtype=T()),
+                        (N * Lr * D, Lr * D, D, 1), (B, N, Lr, D))
+        ops.scale_rows(qt, ops.axpby(wl, self.scale, None, 0.0, torch.empty_like(wl)), B * N * Lr * H, dh, out=qt)
+        return qkp, wl, qt
+
+    def attend_general(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None, fused_logits=False):
+        """Any shape and compute dtype: q | k | poswise-k row-major, v key-contiguous, the logits from rf_tied_logits_softmax
+        (fused_logits) or rf_gemm + rf_tied_softmax, attention . V on rf_gemm."""
+        B, N, Lr, D = xn.shape
+        H, dh, W3 = self.n_heads, self.d_head, 3 * D
+        pw = self.poswise_weight
+        # training mode: the weights exist as a tensor so that the dropout can sit between the softmax and the scaling
+        dropping = pw.training and pw.p_dropout and pw.p_dropout > 0
+        qkp, _, qt = self.general_operands(xn, (lambda w: pw.drop(w, tape["pw"] if tape is not None else None)) if dropping else None)
+        if dropping:
+            ops.copy4d(qt, (N * Lr * D, Lr * D, D, 1), qkp, (N * Lr * W3, Lr * W3, W3, 1), (B, N, Lr, D))
+        bv, bo = self.value_biases(xn, h16_only=True)
         v_t = self.values_transposed(self.to_v, xn, bv)
         # logits[b,h,i,j] = sum_{n,d} q k   (contraction over N*dh, rf.py:254), softmax over j (rf.py:255)
-        W3 = 3 * D
-        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by tied_softmax)
-        att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
-        if RT.fused_tied and ops.is_h16(T()) and dh == 32 and Lr in (64, 128, 192, 256):
+        att, att_sym = self.maps(B, Lr, xn.device, want_att)
+        if fused_logits:
             # one launch: 6-8-stage DMA ring over the N steps, logits in registers, wave-local softmax (csrc/tied.hip)
             ops.tied_logits_softmax(qkp, qkp[..., D:], N * Lr * W3, Lr * W3, W3, att, att_sym, B, H, N, Lr, dh)
         else:
-            logits = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32)
+            logits = torch.empty(B, H, Lr, Lr, device=xn.device, dtype=F32)
             ops.gemm(qkp, qkp, logits, Lr, Lr, N * dh, batch=(B, H, 1), b_off=D,
                      a_bs=(N * Lr * W3, dh, 0), a_row=(0, 0, W3), a_ko=Lr * W3,
                      b_bs=(N * Lr * W3, dh, 0), b_row=(0, 0, W3), b_ko=Lr * W3, kc=dh,
                      c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr))
             ops.tied_softmax(logits, att, att_sym, H)
-        out = self.attention_values(att, v_t)
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
-                                        recs=tape["drops"] if tape is not None else None)
-        return att_sym, xn_next
+        return att_sym, self.into_residual(self.attention_values(att, v_t), bo, x_res, next_ln, drops, tape)
 
     def folds_weights(self, rows):
         """the head-major q|k|v projection of `rows` MSA positions folds w * d_head^-0.5 into q (attend_head_major)"""
@@ -800,71 +859,35 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         return out
 
     def attend_head_major(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
-        """The bench path (csrc/tied.hip): one projection GEMM writes q|k|v head-major [B,N,3H,L,32] (every contraction
-        step of the attention kernels is then one contiguous tile), the position weights come from the collapsed form
-        (no to_k projection over the N rows) and are applied inside the logits kernel, attention.V consumes v with
-        transposed LDS reads: no v^T GEMM, no pass over q, no fp32 logits."""
+        """The bench path (csrc/tied.hip), any L <= 256: head_major_front with q | k | v, the position weights folded into q or
+        applied inside the logits kernel, attention . V consuming v with transposed LDS reads: no v^T GEMM, no pass over q, no
+        fp32 logits."""
         B, N, Lr, D = xn.shape
         H, dh = self.n_heads, self.d_head
-        dev = xn.device
-        G = 3 * H
-        lins = [self.to_q, self.to_k, self.to_v]
-        w = self.poswise_weight.weights_head_major(xn, tape["pw"] if tape is not None else None)  # fp32 [B,H,N,L]
-        ragged = Lr not in ops.TIED_TILES
-        qkv = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
-        # q * w * d_head^-0.5 (rf.py:252) in the projection's epilogue, on the fp32 accumulators: q is rounded once, after
-        # the scaling, and the logits kernel neither stages the weights nor rescales its fragments (round 2: 15-20 us of VALU)
-        # ... when the projection runs on the kernel whose epilogue knows the row-group scale (d_msa = 288: N = 864 does not)
+        # (folded where the projection runs on the kernel whose epilogue knows the row-group scale; d_msa = 288, N = 864: not)
         fold = self.folds_weights(B * N * Lr)
-        if ragged and not fold and Lr % 4:
-            # the logits kernel stages w by 16-byte pieces: rows padded to a multiple of 4 floats (the pad is read, its values
-            # scale query rows past the chain only, which are never stored)
-            Lw = (Lr + 3) // 4 * 4
-            w = ops.copy4d(w, (H * N * Lr, N * Lr, Lr, 1), ops.zeros(B, H, N, Lw, device=dev, dtype=F32),
-                           (H * N * Lw, N * Lw, Lw, 1), (B, H, N, Lr))
-        bqkv, bo = self.bcat("qkv", lins), _f(self.to_out.bias)
-        if RT.condition and RT.condition_values:
-            bqkv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out, lead=(self.to_q, self.to_k)))
-        ops.gemm(xn, self.wcat("qkv", lins), qkv, B * N * Lr, 3 * D, D, bias=bqkv,
-                 c_row=(Lr, G * Lr * dh, dh), c_col=(dh, Lr * dh),
-                 rs=(w, H * N * Lr, N * Lr, dh, D, self.scale) if fold else None)
-        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by the logits kernel)
-        att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
-        out = torch.empty(B, N, Lr, D, device=dev, dtype=T())
+        w, qkv, bo = self.head_major_front(xn, "qkv", [self.to_q, self.to_k, self.to_v], fold, tape)
+        att, att_sym = self.maps(B, Lr, xn.device, want_att)
+        out = torch.empty(B, N, Lr, D, device=xn.device, dtype=T())
         ops.tied_attention(qkv[:, :, 0:H], qkv[:, :, H:2 * H], qkv[:, :, 2 * H:], out.view(B, N, Lr, H, dh).permute(0, 1, 3, 2, 4),
                            att, w=None if fold else w, qscale=1.0 if fold else self.scale, att_sym=att_sym)
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
-                                        recs=tape["drops"] if tape is not None else None)
-        return att_sym, xn_next
+        return att_sym, self.into_residual(out, bo, x_res, next_ln, drops, tape)
 
     def attend_long_rows(self, xn, x_res, want_att, next_ln=None, drops=(), tape=None):
         """Any 256 < L <= 1024 (L in {512, 768, 1024}: BASELINE.json configs[3]; every other length runs the tail instantiations
-        of the same kernel through ops.tied_logits_long, with the map's row pitch map_ld(L)).  Same front as
-        attend_head_major -- collapsed position weights, one projection GEMM writing q|k head-major with w * d_head^-0.5
-        folded into q on the fp32 accumulators -- then the contraction-split logits kernel over 128-query x 256-key tiles
-        (csrc/tied.hip: rf_tied_logits, rf_tied_logits_long).  attention . V at
-        these lengths is a plain large GEMM per (b, head) (M = L queries, K = L keys, N = n_seq * 32): it goes to rf_gemm with
-        v written key-contiguous by its projection (keeping whole probability rows in registers, as the L <= 256 kernel
-        does, would need 128 VGPRs per 16 query rows)."""
+        of the same kernel through ops.tied_logits_long, with the map's row pitch map_ld(L)): head_major_front with q | k and the
+        weights folded into q, then the contraction-split logits kernel over 128-query x 256-key tiles (csrc/tied.hip:
+        rf_tied_logits, rf_tied_logits_long).  attention . V at these lengths is a plain large GEMM per (b, head) (M = L queries,
+        K = L keys, N = n_seq * 32): it goes to rf_gemm with v written key-contiguous by its projection (whole probability
+        rows in registers, as in the L <= 256 kernel, would need 128 VGPRs per 16 query rows)."""
         B, N, Lr, D = xn.shape
-        H, dh = self.n_heads, self.d_head
-        dev = xn.device
-        w = self.poswise_weight.weights_head_major(xn, tape["pw"] if tape is not None else None)  # fp32 [B,H,N,L]
-        G = 2 * H
-        lins = [self.to_q, self.to_k]
-        qk = torch.empty(B, N, G, Lr, dh, device=dev, dtype=T())
-        ops.gemm(xn, self.wcat("qk", lins), qk, B * N * Lr, 2 * D, D, bias=self.bcat("qk", lins),
-                 c_row=(Lr, G * Lr * dh, dh), c_col=(dh, Lr * dh), rs=(w, H * N * Lr, N * Lr, dh, D, self.scale))
-        att = torch.empty(B, H, Lr, map_ld(Lr), device=dev, dtype=T())  # (pad columns: zeros written by the logits kernel)
-        att_sym = torch.empty(B, Lr, Lr, H, device=dev, dtype=F32) if want_att else None
+        H = self.n_heads
+        _, qk, _ = self.head_major_front(xn, "qk", [self.to_q, self.to_k], True, tape)
+        att, att_sym = self.maps(B, Lr, xn.device, want_att)
         (ops.tied_logits if Lr in (512, 768, 1024) else ops.tied_logits_long)(qk[:, :, 0:H], qk[:, :, H:], att, att_sym)
-        bv, bo = _f(self.to_v.bias), _f(self.to_out.bias)
-        if RT.condition and RT.condition_values:
-            bv, bo = (t_[0] for t_ in self.value_conditioning(xn, self.to_v, self.to_out))
+        bv, bo = self.value_biases(xn)
         out = self.attention_values(att, self.values_transposed(self.to_v, xn, bv))
-        xn_next = project_into_residual(out, self.wt("o", self.to_out), bo, x_res, next_ln, drops,
-                                        recs=tape["drops"] if tape is not None else None)
-        return att_sym, xn_next
+        return att_sym, self.into_residual(out, bo, x_res, next_ln, drops, tape)
 
     def _replay_weight_dropout(self, t, tape):
         """t: fp32 [B,N,H,L], the position weights or their gradient (in place): times the forward's keep / (1 - p).  The Philox
@@ -905,17 +928,7 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         g_t = ops.cast(g.view(R, D), T())
 
         # ---- the forward's operands, general route
-        lins = [self.to_q, self.to_k, pw.to_k[0]]
-        qkp = ops.linear(xn, self.wcat("qkp", lins), self.bcat("qkp", lins))   # [B,N,L,3D]: q | k | poswise-k
-        w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
-        ops.poswise(pw.query_proj(xn), D, qkp, W3, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
-        self._replay_weight_dropout(w, tape)
-        wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
-                        (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))                # the weights per (token, head)
-        del w
-        qt = ops.copy4d(qkp, (N * Lr * W3, Lr * W3, W3, 1), torch.empty(B, N, Lr, D, device=dev, dtype=T()),
-                        (N * Lr * D, Lr * D, D, 1), (B, N, Lr, D))
-        ops.scale_rows(qt, ops.axpby(wl, self.scale, None, 0.0, torch.empty_like(wl)), R * H, dh, out=qt)   # q~
+        qkp, wl, qt = self.general_operands(xn, lambda w: self._replay_weight_dropout(w, tape))
         logits = torch.empty(B, H, Lr, Lr, device=dev, dtype=F32)
         tied_k = dict(batch=(B, H, 1), kc=dh, c_bs=(H * Lr * Lr, Lr * Lr, 0), c_row=(0, 0, Lr))   # a contraction over N * dh
         rows_d = lambda ld_: dict(bs=(N * Lr * ld_, dh, 0), row=(0, 0, ld_), ko=Lr * ld_)   # noqa: E731  (head h of [B,N,L,ld_])

@@ -234,16 +234,23 @@ def tied_ld(L_):
     return (L_ + 7) // 8 * 8
 
 
+def tied_lds_fits(L_, w_rows):
+    """The one-pass logits kernel's LDS at a chain of 1 <= L <= 256 residues fits the 160 KB of a workgroup (csrc/tied.hip:
+    launch_tied): a ring of 6 (tile 256) or 8 stages of a 64-query and a key tile, 1 KB, and 256 bytes per MSA row of a
+    position-weight tile of w_rows rows."""
+    tile = (L_ + 63) // 64 * 64
+    return (6 if tile >= 256 else 8) * (4096 + tile * 64) + 1024 + w_rows * 256 <= 160 * 1024
+
+
 def tied_fused_applies(L_, N, dtype, dh=32, w=True):
     """Python mirror of what rf_tied_attention_ld accepts (the one-pass logits + softmax kernel, then attention . V): 16-bit
-    operands, d_head 32, 1 <= L <= 256, and a ring + position-weight tile that fit the 160 KB of LDS (w: the weights are
-    applied in the kernel, which stages them four MSA rows per DMA instruction)."""
+    operands, d_head 32, 1 <= L <= 256, and a ring + position-weight tile that fit the LDS (w: the weights are applied in the
+    kernel, which stages them four MSA rows per DMA instruction)."""
     if not (is_h16(dtype) and dh == 32 and 1 <= L_ <= 256 and N >= 1):
         return False
     if w and N % 4:
         return False
-    tile = (L_ + 63) // 64 * 64
-    return (6 if tile >= 256 else 8) * (4096 + tile * 64) + 1024 + (N * 256 if w else 0) <= 160 * 1024
+    return tied_lds_fits(L_, N if w else 0)
 
 
 def _att_ld(att, L_):
@@ -261,6 +268,13 @@ def _w_strides(w, B, H, N, L_):
     return I64x3(w.stride(0), w.stride(1), w.stride(2))
 
 
+def _qk_sym(q, k, att_sym):
+    """(strides shared by the head-major q and k views, row pitch of att_sym or 0) as the logits entry points take them"""
+    if q.stride() != k.stride():
+        raise ValueError("q and k must share their strides")
+    return C.byref(_hstrides(q)), att_sym.shape[-1] if att_sym is not None else 0
+
+
 def tied_attention(q, k, v, out, att, w=None, qscale=1.0, att_sym=None, partial_ws=None):
     """Tied MSA-row attention core (csrc/tied.hip).  q, k, v, out: bf16 views indexed [B, N, H, L, 32] (any strides with
     a contiguous head slice); att: bf16 [B, H, L, att_ld] (workspace + result; att_ld = L, or any multiple of 8 >= L: the
@@ -275,20 +289,17 @@ def tied_attention(q, k, v, out, att, w=None, qscale=1.0, att_sym=None, partial_
     if partial_ws is False:
         partial_ws = None
     _need_cuda(q, k, v, out, att, w, att_sym, partial_ws)
-    if q.stride() != k.stride():
-        raise ValueError("q and k must share their strides")
+    qks, sym_ld = _qk_sym(q, k, att_sym)
     ws = _w_strides(w, B, H, N, L_)
+    ws_elems = partial_ws.numel() if partial_ws is not None else 0
     if not (L_ in TIED_TILES and att_ld == L_):
-        check(lib.rf_tied_attention_ld(ptr(q), ptr(k), ptr(v), C.byref(_hstrides(q)), C.byref(_hstrides(v)), ptr(w), C.byref(ws),
-                                       float(qscale), ptr(att), att_ld, ptr(att_sym),
-                                       att_sym.shape[-1] if att_sym is not None else 0, ptr(out), C.byref(_hstrides(out)), B, H,
-                                       N, L_, dh, ptr(partial_ws), partial_ws.numel() if partial_ws is not None else 0,
-                                       stream()), "rf_tied_attention_ld")
+        check(lib.rf_tied_attention_ld(ptr(q), ptr(k), ptr(v), qks, C.byref(_hstrides(v)), ptr(w), C.byref(ws), float(qscale),
+                                       ptr(att), att_ld, ptr(att_sym), sym_ld, ptr(out), C.byref(_hstrides(out)), B, H, N, L_, dh,
+                                       ptr(partial_ws), ws_elems, stream()), "rf_tied_attention_ld")
         return out
-    check(lib.rf_tied_attention(ptr(q), ptr(k), ptr(v), C.byref(_hstrides(q)), C.byref(_hstrides(v)), ptr(w), C.byref(ws),
-                                float(qscale), ptr(att), ptr(att_sym), att_sym.shape[-1] if att_sym is not None else 0,
-                                ptr(out), C.byref(_hstrides(out)), B, H, N, L_, dh, ptr(partial_ws),
-                                partial_ws.numel() if partial_ws is not None else 0, stream()), "rf_tied_attention")
+    check(lib.rf_tied_attention(ptr(q), ptr(k), ptr(v), qks, C.byref(_hstrides(v)), ptr(w), C.byref(ws), float(qscale), ptr(att),
+                                ptr(att_sym), sym_ld, ptr(out), C.byref(_hstrides(out)), B, H, N, L_, dh, ptr(partial_ws),
+                                ws_elems, stream()), "rf_tied_attention")
     return out
 
 
@@ -301,11 +312,9 @@ def tied_logits_ld(q, k, att, w=None, qscale=1.0, att_sym=None):
     B, N, H, L_, dh = q.shape
     att_ld = _att_ld(att, L_)
     _need_cuda(q, k, att, w, att_sym)
-    if q.stride() != k.stride():
-        raise ValueError("q and k must share their strides")
-    check(lib.rf_tied_logits_ld(ptr(q), ptr(k), C.byref(_hstrides(q)), ptr(w), C.byref(_w_strides(w, B, H, N, L_)), float(qscale),
-                                ptr(att), att_ld, ptr(att_sym), att_sym.shape[-1] if att_sym is not None else 0, B, H, N, L_, dh,
-                                None, 0, stream()), "rf_tied_logits_ld")
+    qks, sym_ld = _qk_sym(q, k, att_sym)
+    check(lib.rf_tied_logits_ld(ptr(q), ptr(k), qks, ptr(w), C.byref(_w_strides(w, B, H, N, L_)), float(qscale), ptr(att), att_ld,
+                                ptr(att_sym), sym_ld, B, H, N, L_, dh, None, 0, stream()), "rf_tied_logits_ld")
     return att
 
 
@@ -329,38 +338,23 @@ def tied_logits(q, k, att, att_sym=None, qscale=1.0):
         nsplit *= 2
     ws = torch.empty(max(nsplit, 2 if L_ == 256 else 1) * B * H * L_ * L_, device=q.device, dtype=F32)
     _need_cuda(q, k, att, att_sym, ws)
-    if q.stride() != k.stride():
-        raise ValueError("q and k must share their strides")
-    check(lib.rf_tied_logits(ptr(q), ptr(k), C.byref(_hstrides(q)), None, C.byref(I64x3(0, 0, 0)), float(qscale), ptr(att),
-                             ptr(att_sym), att_sym.shape[-1] if att_sym is not None else 0, B, H, N, L_, dh, ptr(ws), ws.numel(),
-                             stream()), "rf_tied_logits")
+    qks, sym_ld = _qk_sym(q, k, att_sym)
+    check(lib.rf_tied_logits(ptr(q), ptr(k), qks, None, C.byref(I64x3(0, 0, 0)), float(qscale), ptr(att), ptr(att_sym), sym_ld,
+                             B, H, N, L_, dh, ptr(ws), ws.numel(), stream()), "rf_tied_logits")
     if L_ > 256:
         COUNTERS["tied_logits_long"] += 1
     return att
 
 
 def _tied_long_splits(N, B=1, H=1, L_=512):
-    """MSA-row ranges of the contraction-split logits kernel above L = 256 (csrc/tied.hip: tied_split_count, and at a length off
-    512 / 768 / 1024 tied_long_split_count: halved further while fewer than 192 workgroups would run); 0: N is outside it"""
-    if N < 1 or N % 2:
-        return 0
-    nsplit = 1
-    while N // nsplit > 64 and N % (2 * nsplit) == 0:
-        nsplit *= 2
-    nper = N // nsplit
-    if not (4 <= nper <= 64 and nper % 2 == 0):
-        return 0
-    if L_ % 256:
-        tiles = B * H * ((L_ + 127) // 128) * ((L_ + 255) // 256)
-        while tiles * nsplit < 192 and (N // nsplit) % 4 == 0 and N // nsplit >= 8:
-            nsplit *= 2
-    return nsplit
+    """MSA-row ranges of the contraction-split logits kernel above L = 256, from the library's workspace size; 0: N is outside it"""
+    return lib.rf_tied_logits_long_ws_elems(B, H, N, L_) // (B * H * L_ * 256 * ((L_ + 255) // 256))
 
 
 def tied_long_applies(L_, N, dtype, dh=32):
-    """Python mirror of what rf_tied_logits_long accepts: 16-bit operands, d_head 32, 257 <= L <= 1024, N even and split into
-    ranges of 4 .. 64 and an even number of MSA rows."""
-    return bool(is_h16(dtype) and dh == 32 and 257 <= L_ <= 1024 and _tied_long_splits(N))
+    """What rf_tied_logits_long accepts: 16-bit operands, d_head 32, 257 <= L <= 1024 and an MSA depth its split rule takes (N
+    even, ranges of 4 .. 64 and an even number of MSA rows), asked of the library's host-only rf_tied_logits_long_ws_elems."""
+    return bool(is_h16(dtype) and dh == 32 and 257 <= L_ <= 1024 and _tied_long_splits(N, L_=L_))
 
 
 def tied_logits_long(q, k, att, att_sym=None, qscale=1.0):
@@ -368,15 +362,12 @@ def tied_logits_long(q, k, att, att_sym=None, qscale=1.0):
     kernel): att 16-bit [B, H, L, att_ld], att_ld >= L a multiple of 8, zeros written past column L."""
     B, N, H, L_, dh = q.shape
     att_ld = _att_ld(att, L_)
-    # (rf_tied_logits_long_ws_elems: MSA-row ranges x rows x whole key tiles of 256 columns; a refused shape gets 4 floats and the
-    # library's answer)
-    ws = torch.empty(max(_tied_long_splits(N, B, H, L_) * B * H * L_ * 256 * ((L_ + 255) // 256), 4), device=q.device, dtype=F32)
+    # (a refused shape gets 4 floats and the library's answer)
+    ws = torch.empty(max(lib.rf_tied_logits_long_ws_elems(B, H, N, L_), 4), device=q.device, dtype=F32)
     _need_cuda(q, k, att, att_sym, ws)
-    if q.stride() != k.stride():
-        raise ValueError("q and k must share their strides")
-    check(lib.rf_tied_logits_long(ptr(q), ptr(k), C.byref(_hstrides(q)), float(qscale), ptr(att), att_ld, ptr(att_sym),
-                                  att_sym.shape[-1] if att_sym is not None else 0, B, H, N, L_, dh, ptr(ws), ws.numel(), stream()),
-          "rf_tied_logits_long")
+    qks, sym_ld = _qk_sym(q, k, att_sym)
+    check(lib.rf_tied_logits_long(ptr(q), ptr(k), qks, float(qscale), ptr(att), att_ld, ptr(att_sym), sym_ld, B, H, N, L_, dh,
+                                  ptr(ws), ws.numel(), stream()), "rf_tied_logits_long")
     COUNTERS["tied_logits_long"] += 1
     return att
 
