@@ -84,7 +84,8 @@ def _conv_weight_grad(dw, w):
     """fp32 [Co, 9 * Ci] gradient in the forward's [co][tap][ci] layout -> a contiguous [Co, Ci, 3, 3] like the weight"""
     Co, Ci = w.shape[0], w.shape[1]
     out = torch.empty(Co, Ci, 3, 3, device=dw.device, dtype=F32)
-    return ops.copy4d(dw, (9 * Ci, 1, Ci, 1), out, (9 * Ci, 9, 1, 1), (Co, Ci, 9, 1))
+    ops.copy(dw.view(Co, 9, Ci).transpose(1, 2), out.view(Co, Ci, 9))
+    return out
 
 
 def _param_grads(mod, grads, s):

@@ -199,7 +199,7 @@ def pair_bias_attention(logits: Tensor, v: Tensor, msa: Tensor) -> Tensor:
         att = torch.empty(H, B, Lr, Lr, device=v.device, dtype=v.dtype)
         ops.softmax_batched(logits.contiguous(), 1, Lr * H, H, att, B * Lr * Lr, Lr, B * Lr, Lr, H)
         v_t = torch.empty(B, N, D, Lr, device=v.device, dtype=v.dtype)
-        ops.copy4d(v.contiguous(), (N * Lr * D, Lr * D, D, 1), v_t, (N * D * Lr, D * Lr, 1, Lr), (B, N, Lr, D))
+        ops.copy(v, v_t.transpose(2, 3))
         out = msa.contiguous().clone()
         ops.gemm(att, v_t, out, Lr, N * dv, Lr, batch=(H, B, 1), a_bs=(B * Lr * Lr, Lr * Lr, 0), a_row=(0, 0, Lr),
                  b_bs=(dv * Lr, N * D * Lr, 0), b_row=(dv, D * Lr, Lr), c_bs=(dv, N * Lr * D, 0), c_row=(0, 0, D),

@@ -350,11 +350,11 @@ class RowWise(nn.Module):
             self.fn.attend(ops.cast(x.contiguous(), T()), out, axis=1)
             return out
         xt = torch.empty(b, l, n, d, device=x.device, dtype=x.dtype)
-        ops.copy4d(x.contiguous(), (n * l * d, d, l * d, 1), xt, (l * n * d, n * d, d, 1), (b, l, n, d))
+        ops.copy(x.transpose(1, 2), xt)
         y = self.fn(xt.view(b * l, n, d)).contiguous()
         do = y.shape[-1]
         out = torch.empty(b, n, l, do, device=x.device, dtype=y.dtype)
-        ops.copy4d(y, (l * n * do, n * do, do, 1), out, (n * l * do, do, l * do, 1), (b, l, n, do))
+        ops.copy(y.view(b, l, n, do), out.transpose(1, 2))
         return out
 
 
@@ -620,7 +620,7 @@ class PositionWiseWeightFactor(RecordingModule):
         del q0, k
         dq0_t = ops.cast(dq0.view(B * Lr, D), T())
         x0 = torch.empty(B, Lr, D, device=xn.device, dtype=T())     # xn[:, 0]
-        ops.copy4d(xn, (0, N * Lr * D, D, 1), x0, (0, Lr * D, D, 1), (1, B, Lr, D))
+        ops.copy(xn[:, 0], x0)
         grads = {}
         grads[lk.weight], grads[lk.bias] = ops.conv_wgrad(dk, xn, 1, bias=True)
         grads[lq.weight], grads[lq.bias] = ops.conv_wgrad(dq0_t, x0.view(B * Lr, D), 1, bias=True)
@@ -780,8 +780,9 @@ class SoftTiedAttentionOverResidues(RecordingModule):
             # the logits kernel stages w by 16-byte pieces: rows padded to a multiple of 4 floats (the pad is read, its values
             # scale query rows past the chain only, which are never stored)
             Lw = (Lr + 3) // 4 * 4
-            w = ops.copy4d(w, (H * N * Lr, N * Lr, Lr, 1), ops.zeros(B, H, N, Lw, device=xn.device, dtype=F32),
-                           (H * N * Lw, N * Lw, Lw, 1), (B, H, N, Lr))
+            w_pad = ops.zeros(B, H, N, Lw, device=xn.device, dtype=F32)
+            ops.copy(w, w_pad[..., :Lr])
+            w = w_pad
         bias, bo = self.value_biases(xn, lead=lins[:-1]) if lins[-1] is self.to_v else (self.bcat(key, lins), None)
         ops.gemm(xn, self.wcat(key, lins), proj, B * N * Lr, len(lins) * D, D, bias=bias, c_row=(Lr, G * Lr * dh, dh),
                  c_col=(dh, Lr * dh), rs=(w, H * N * Lr, N * Lr, dh, D, self.scale) if fold else None)
@@ -804,11 +805,9 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         w = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
         ops.poswise(q0, D, qkp, W3, 2 * D, dh, dh, w, None, 0, 0, 0, B, N, Lr, H, pw.scale, 1.0)
         drop(w)
-        wl = ops.copy4d(w, (N * H * Lr, H * Lr, 1, Lr), torch.empty(B, N, Lr, H, device=dev, dtype=F32),
-                        (N * Lr * H, Lr * H, H, 1), (B, N, Lr, H))
+        wl = ops.copy(w.transpose(2, 3), torch.empty(B, N, Lr, H, device=dev, dtype=F32))
         del w
-        qt = ops.copy4d(qkp, (N * Lr * W3, Lr * W3, W3, 1), torch.empty(B, N, Lr, D, device=dev, dtype=T()),
-                        (N * Lr * D, Lr * D, D, 1), (B, N, Lr, D))
+        qt = ops.copy(qkp[..., :D], torch.empty(B, N, Lr, D, device=dev, dtype=T()))
         ops.scale_rows(qt, ops.axpby(wl, self.scale, None, 0.0, torch.empty_like(wl)), B * N * Lr * H, dh, out=qt)
         return qkp, wl, qt
 
@@ -822,7 +821,7 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         dropping = pw.training and pw.p_dropout and pw.p_dropout > 0
         qkp, _, qt = self.general_operands(xn, (lambda w: pw.drop(w, tape["pw"] if tape is not None else None)) if dropping else None)
         if dropping:
-            ops.copy4d(qt, (N * Lr * D, Lr * D, D, 1), qkp, (N * Lr * W3, Lr * W3, W3, 1), (B, N, Lr, D))
+            ops.copy(qt, qkp[..., :D])
         bv, bo = self.value_biases(xn, h16_only=True)
         v_t = self.values_transposed(self.to_v, xn, bv)
         # logits[b,h,i,j] = sum_{n,d} q k   (contraction over N*dh, rf.py:254), softmax over j (rf.py:255)
@@ -898,10 +897,10 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         if tape["w_order"] == "bnhl":
             return _replay_dropout(t, rec)
         B, N, H, Lr = t.shape
-        hm = ops.copy4d(t, (N * H * Lr, Lr, H * Lr, 1), torch.empty(B, H, N, Lr, device=t.device, dtype=F32),
-                        (H * N * Lr, N * Lr, Lr, 1), (B, H, N, Lr))
+        hm = ops.copy(t.transpose(1, 2), torch.empty(B, H, N, Lr, device=t.device, dtype=F32))
         _replay_dropout(hm, rec)
-        return ops.copy4d(hm, (H * N * Lr, N * Lr, Lr, 1), t, (N * H * Lr, Lr, H * Lr, 1), (B, H, N, Lr))
+        ops.copy(hm, t.transpose(1, 2))
+        return t
 
     def _backward(self, tape, g, g_sym=None):
         """g: contiguous fp32 [B,N,L,D], the gradient of what attend() added to x_res (overwritten); g_sym: contiguous fp32
@@ -936,15 +935,17 @@ class SoftTiedAttentionOverResidues(RecordingModule):
         ops.gemm(qt, qkp, logits, Lr, Lr, N * dh, b_off=D, **a_d, **b_w3, **tied_k)
         v = ops.linear(xn, self.wt("v", self.to_v), _f(self.to_v.bias))          # the values row-major [B,N,L,D]
 
-        def key_contiguous(src, ld_, off=0):
-            """[B,N,L,(h,d)] rows of ld_ -> [B,N,D,Lp]: the B operand of a contraction over the chain (zero pads)"""
+        def key_contiguous(src, off=0):
+            """columns off.. of [B,N,L,(h,d)] rows -> [B,N,D,Lp]: the B operand of a contraction over the chain (zero pads)"""
             dst = (torch.empty if Lp == Lr else ops.zeros)(B, N, D, Lp, device=dev, dtype=T())
-            return ops.copy4d(src, (N * Lr * ld_, Lr * ld_, 1, ld_), dst, (N * D * Lp, D * Lp, Lp, 1), (B, N, D, Lr), x_off=off)
+            ops.copy(src[..., off:off + D].transpose(2, 3), dst[..., :Lr])
+            return dst
 
         def map_transposed(m):
             """[B,H,L,Lp] -> the same with rows and columns swapped (zero pads)"""
             dst = (torch.empty if Lp == Lr else ops.zeros)(B, H, Lr, Lp, device=dev, dtype=m.dtype)
-            return ops.copy4d(m, (0, Lr * Lp, 1, Lp), dst, (0, Lr * Lp, Lp, 1), (1, B * H, Lr, Lr))
+            ops.copy(m[..., :Lr].transpose(2, 3), dst[..., :Lr])
+            return dst
 
         def over_chain(m, bt, out, ld_, off):
             """out[b,n,i,off + (h,d)] = sum_j m[b,h,i,j] bt[b,n,(h,d),j]: attention_values into rows of ld_"""
@@ -963,20 +964,20 @@ class SoftTiedAttentionOverResidues(RecordingModule):
             ops.tied_softmax(logits, p)
         del logits, dp
         grads = {}
-        o = over_chain(p, key_contiguous(v, D), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
+        o = over_chain(p, key_contiguous(v), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
         grads[self.to_out.weight], grads[self.to_out.bias] = ops.conv_wgrad(g_t, o.view(R, D), 1, bias=True)
         del o, v, g_t
         # ---- dq~, then dq | dk | dv in the layout of a q | k | v projection
-        dqt = over_chain(ds_t, key_contiguous(qkp, W3, D), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
+        dqt = over_chain(ds_t, key_contiguous(qkp, D), torch.empty(B, N, Lr, D, device=dev, dtype=T()), D, 0)
         dqkv = torch.empty(B, N, Lr, W3, device=dev, dtype=T())
-        over_chain(map_transposed(ds_t), key_contiguous(qt, D), dqkv, W3, D)
-        over_chain(map_transposed(p), key_contiguous(do, D), dqkv, W3, 2 * D)
+        over_chain(map_transposed(ds_t), key_contiguous(qt), dqkv, W3, D)
+        over_chain(map_transposed(p), key_contiguous(do), dqkv, W3, 2 * D)
         del ds, ds_t, p, do, qt
         _, dwl = ops.scale_rows_bwd(qkp, W3, dh, dqt, D, dh, wl.view(-1), self.scale, R, H, dh, dx=dqkv, dx_ld=W3, dx_hs=dh)
         del dqt, qkp, wl
         # ---- the position weights
-        dw = ops.copy4d(dwl.view(B, N, Lr, H), (N * Lr * H, Lr * H, H, 1), torch.empty(B, N, H, Lr, device=dev, dtype=F32),
-                        (N * H * Lr, H * Lr, 1, Lr), (B, N, Lr, H))
+        dw = torch.empty(B, N, H, Lr, device=dev, dtype=F32)
+        ops.copy(dwl.view(B, N, Lr, H), dw.transpose(2, 3))
         self._replay_weight_dropout(dw, tape)
         dxn, gpw = pw._backward({"xn": xn, "drop": None}, dw)
         gpw[pw.to_k[0].bias] = ops.zeros(D, device=dev, dtype=F32)
@@ -1158,8 +1159,8 @@ class PerformerSelfAttention(RecordingModule):
             ops.favor_softmax_features(kt, qk, inner, xs, Lo, H, S, Ls, m, M_PAD, dh, 0, 1)
         # v^T [B,Lo,H,80,Ls] with a ones row at index 64 (-> k' column sums ride along in the context GEMM)
         vt = ops.zeros(B, Lo, H, VT_ROWS, Ls, device=dev, dtype=T())
-        ones_row = ops.fill(torch.empty(B * Lo * H, Ls, device=dev, dtype=T()), 1.0)
-        ops.copy4d(ones_row, (0, 0, Ls, 1), vt, (0, 0, VT_ROWS * Ls, 1), (1, 1, B * Lo * H, Ls), y_off=dh * Ls)
+        ones_row = ops.fill(torch.empty(B, Lo, H, Ls, device=dev, dtype=T()), 1.0)
+        ops.copy(ones_row, vt[:, :, :, dh])
         ops.gemm(self.wt("v", self.to_v), xn, vt, inner, Ls, D, batch=(B, Lo, 1),
                  b_bs=(RB * D, so * D, 0), b_row=(0, 0, ss * D),
                  c_bs=(Lo * H * VT_ROWS * Ls, H * VT_ROWS * Ls, 0), c_row=(dh, VT_ROWS * Ls, Ls),
@@ -1257,16 +1258,16 @@ class PerformerSelfAttention(RecordingModule):
 
     def _seq_transpose(self, seq_major, rows, geo, to_rows):
         """[B, Lo, H, 80, Ls] (sequence index innermost) <-> [B, L1, L2, H, 80] (the numerator's rows), one copy per sample."""
-        B, Ls, Lo, ss, so = geo[:5]
+        B, Ls, Lo, ss = geo[:4]
         H, V = self.heads, VT_ROWS
-        rs = (so * H * V, ss * H * V, V, 1)          # (o, n, h, e) in the row layout, past the sample offset
-        ts = (H * V * Ls, 1, V * Ls, Ls)              # (o, n, h, e) in the sequence-major layout
+        # both as (b, o, n, h, e): the rows hold (n, o) in that order when the sequences run along axis 1
+        r = rows.view(B, Lo, Ls, H, V) if ss == 1 else rows.view(B, Ls, Lo, H, V).transpose(1, 2)
+        t = seq_major.permute(0, 1, 4, 2, 3)
         for b in range(B):
-            ro, to = b * Lo * Ls * H * V, b * Lo * H * V * Ls
             if to_rows:
-                ops.copy4d(seq_major, ts, rows, rs, (Lo, Ls, H, V), x_off=to, y_off=ro)
+                ops.copy(t[b], r[b])
             else:
-                ops.copy4d(rows, rs, seq_major, ts, (Lo, Ls, H, V), x_off=ro, y_off=to)
+                ops.copy(r[b], t[b])
 
     def enable_backward(self, mode=True):
         """Opt in to autograd (generalized ReLU feature map only: the softmax-kernel Performer of the MSA track raises
@@ -1476,8 +1477,7 @@ class OuterProductMean(RecordingModule):
             for b in range(B):
                 ops.gemm(x_rows_t[b, i0:i0 + hs], y_t[b], co[b], hs * P, Lr * P, N, c_row=(P, Lr * PP, P), c_col=(P, PP))
             y = ops.linear(ln(lnm, co), self.wt("w", self.to_out[1]), _f(self.to_out[1].bias), out_dtype=F32)
-            ops.copy4d(y, (hs * Lr * y.shape[-1], Lr * y.shape[-1], y.shape[-1], 1), out,
-                       (h * Lr * y.shape[-1], Lr * y.shape[-1], y.shape[-1], 1), (B, hs, Lr, y.shape[-1]), y_off=i0 * Lr * y.shape[-1])
+            ops.copy(y, out[:, i0:i0 + hs])
         return out
 
     def forward(self, x, y=None):
@@ -1499,7 +1499,7 @@ class OuterProductMean(RecordingModule):
         g = gs[0] if gs[0].dtype == F32 and gs[0].is_contiguous() else gs[0].float().contiguous()
         one = tape["one"]
         (dx, dy), grads = self._backward(tape, g, s, want_x=want[0], want_y=want[1] or (one and want[0]))
-        B, Lr, P, Np = tape["x_t"].shape
+        B, Lr, P, _ = tape["x_t"].shape
         N = tape["n"]
         if one and dx is not None:
             ops.axpby(dx, 1.0, dy, 1.0, dx)
@@ -1510,8 +1510,9 @@ class OuterProductMean(RecordingModule):
                 out.append(None)
                 continue
             _unscale([d], s)
-            out.append(ops.copy4d(d, (Lr * P * Np, P * Np, Np, 1), torch.empty(B, N, Lr, P, device=d.device, dtype=F32),
-                                  (N * Lr * P, P, 1, Lr * P), (B, Lr, P, N)))
+            dn = torch.empty(B, N, Lr, P, device=d.device, dtype=F32)
+            ops.copy(d[..., :N], dn.permute(0, 2, 3, 1))
+            out.append(dn)
         return tuple(out), grads
 
     def _backward(self, tape, g, s=1.0, want_x=True, want_y=True):
@@ -1548,7 +1549,7 @@ class OuterProductMean(RecordingModule):
         for b in range(B):
             if want_x:   # y as [Np, (j, v)]: the B operand of dx
                 y_n = (ops.zeros if Kx != Lr * P else torch.empty)(Np, Kx, device=dev, dtype=t)
-                ops.copy4d(y_t[b], (0, P * Np, Np, 1), y_n, (0, P, 1, Kx), (1, Lr, P, Np))
+                ops.copy(y_t[b], y_n[:, :Lr * P].unflatten(1, (Lr, P)).permute(1, 2, 0))
             for i0 in range(0, Lr, h):
                 hs = min(h, Lr - i0)
                 o_s, d_s, g_s = co[:hs], dz[:hs], gt[:hs]
@@ -1578,14 +1579,14 @@ class OuterProductMean(RecordingModule):
                                  exact=True)
                     else:
                         a = ops.zeros(hs * P, Kx, device=dev, dtype=t)
-                        ops.copy4d(d_s, (Lr * PP, PP, P, 1), a, (P * Kx, P, Kx, 1), (hs, Lr, P, P))
+                        ops.copy(d_s.view(hs, Lr, P, P), a.view(hs, P, Kx)[..., :Lr * P].unflatten(2, (Lr, P)).permute(0, 2, 1, 3))
                         ops.gemm(a, y_n, c, hs * P, Np, Kx, exact=True)
                 if want_y:   # do^T [(j, v), (i, u)] and x[i] as [Np, (i, u)]
                     Ky = pad8(hs * P)
                     mk = ops.zeros if Ky != hs * P else torch.empty
                     a, x_n = mk(Lr * P, Ky, device=dev, dtype=t), mk(Np, Ky, device=dev, dtype=t)
-                    ops.copy4d(d_s, (Lr * PP, PP, P, 1), a, (P, P * Ky, 1, Ky), (hs, Lr, P, P))
-                    ops.copy4d(x_t[b, i0:i0 + hs], (0, P * Np, Np, 1), x_n, (0, P, 1, Ky), (1, hs, P, Np))
+                    ops.copy(d_s.view(hs, Lr, P, P), a.view(Lr, P, Ky)[..., :hs * P].unflatten(2, (hs, P)).permute(2, 0, 3, 1))
+                    ops.copy(x_t[b, i0:i0 + hs], x_n[:, :hs * P].unflatten(1, (hs, P)).permute(1, 2, 0))
                     ops.gemm(a, x_n, dy_t[b], Lr * P, Np, Ky, residual=dy_t[b] if i0 else None, exact=True)
         return (dx_t, dy_t), {lin.weight: dW, lin.bias: db, lnm.weight: dgamma, lnm.bias: dbeta}
 
@@ -1632,7 +1633,7 @@ class PairUpdateWithMsa(RFModule):
         msa1d = torch.empty(B, Lr, 2 * P, device=dev, dtype=F32)
         ones = ops.fill(torch.empty(B, N, 1, Lr, device=dev, dtype=F32), 1.0)
         ops.weighted_msa_sum(mp, ones, msa1d, 2 * P)
-        ops.copy4d(mp, (N * Lr * P, 0, P, 1), msa1d, (Lr * 2 * P, 0, 2 * P, 1), (B, 1, Lr, P), y_off=P)
+        ops.copy(mp[:, 0], msa1d[..., P:])
         # transposed operands of the outer product: x_t[b,i,u,n] = mp ; y_t = mp * w   (rf.py:472-473)
         mpw = ops.scale_rows(mp, w, B * N * Lr, P)
         return (msa1d,) + ops.outer_operands(mp, mpw, T(), self.outer_product_mean.depth_multiple(P, N, Lr))
@@ -1671,8 +1672,7 @@ class PairUpdateWithMsa(RFModule):
         Kf = pad8(self.d_feat)
         feat = ops.zeros(B, h, Lr, Kf, device=dev, dtype=T())
         # outer product of this block's rows with every column: the fused kernel on the rectangle, as run() does on the square
-        xr = ops.copy4d(xt, (Lr * P * Np, P * Np, Np, 1), torch.empty(B, h, P, Np, device=dev, dtype=T()),
-                        (h * P * Np, P * Np, Np, 1), (B, h, P, Np), x_off=r0 * P * Np)
+        xr = ops.copy(xt[:, r0:r1], torch.empty(B, h, P, Np, device=dev, dtype=T()))
         if self.outer_product_mean.fused_ok(P, Np, Lr) and Dp == 288:
             self.outer_product_mean.run_into(xr, yt, self.ln_coevol_feat, feat, Kf)  # -> feat[..., :Dp]
         else:
@@ -1683,12 +1683,11 @@ class PairUpdateWithMsa(RFModule):
         if cond:   # (the mean over ALL positions: msa is replicated, every rank folds the same constant)
             bias_b = self._center_1d(msa1d, bias)
         # feat[b,i,j, Dp + c] = msa1d[b, r0 + i, c] ; feat[b,i,j, Dp + 2P + c] = msa1d[b, j, c]   (rf_tile_1d_feats on a block)
-        fs = (h * Lr * Kf, Lr * Kf, Kf, 1)
-        ops.copy4d(msa1d, (Lr * 2 * P, 2 * P, 0, 1), feat, fs, (B, h, Lr, 2 * P), x_off=r0 * 2 * P, y_off=Dp)
-        ops.copy4d(msa1d, (Lr * 2 * P, 0, 2 * P, 1), feat, fs, (B, h, Lr, 2 * P), y_off=Dp + 2 * P)
+        ops.copy(msa1d[:, r0:r1, None, :].expand(B, h, Lr, 2 * P), feat[..., Dp:Dp + 2 * P])
+        ops.copy(msa1d[:, None, :, :].expand(B, h, Lr, 2 * P), feat[..., Dp + 2 * P:Dp + 4 * P])
         ln(self.ln_pair, pair_rows, out=feat, out_ld=Kf, out_off=Dp + 4 * P)
         H = att.shape[-1]
-        ops.copy4d(att.contiguous(), (Lr * Lr * H, Lr * H, H, 1), feat, fs, (B, h, Lr, H), x_off=r0 * Lr * H, y_off=2 * Dp + 4 * P)
+        ops.copy(att[:, r0:r1], feat[..., 2 * Dp + 4 * P:2 * Dp + 4 * P + H])
         blk = self.resnet[1].fn
         kw = {"row_group": row_group, "rows_global": Lr}
         if cond:
@@ -1740,9 +1739,7 @@ class PairUpdateWithMsa(RFModule):
         Kf = pad8(self.d_feat)
         feat = torch.empty(B, Lr, Lr, Kf, device=dev, dtype=T())  # every feature column is written below; only the K padding
         if Kf > self.d_feat:                                       # needs zeros (a full memset of this tensor is 0.38 GB)
-            zpad = ops.zeros(B * Lr * Lr, Kf - self.d_feat, device=dev, dtype=T())
-            ops.copy4d(zpad, (0, 0, Kf - self.d_feat, 1), feat, (0, 0, Kf, 1), (1, 1, B * Lr * Lr, Kf - self.d_feat),
-                       y_off=self.d_feat)
+            ops.copy(ops.zeros(B, Lr, Lr, Kf - self.d_feat, device=dev, dtype=T()), feat[..., self.d_feat:])
         if self.outer_product_mean.fused_ok(P, Np, Lr) and Dp == 288:
             self.outer_product_mean.run_into(xt, yt, self.ln_coevol_feat, feat, Kf)  # outer -> LN -> Linear -> LN -> feat[..., :Dp]
         else:
@@ -1756,7 +1753,7 @@ class PairUpdateWithMsa(RFModule):
             bias_b = self._center_1d(msa1d, bias)   # msa1d -= its mean over the positions; [B, Dp] bias that carries W * mean
         ops.tile_1d_feats(msa1d, feat, Kf, Dp, B, Lr, 2 * P)
         ln(self.ln_pair, pair, out=feat, out_ld=Kf, out_off=Dp + 4 * P)
-        ops.copy4d(att.contiguous(), (0, 0, H, 1), feat, (0, 0, Kf, 1), (1, 1, B * Lr * Lr, H), y_off=2 * Dp + 4 * P)
+        ops.copy(att, feat[..., 2 * Dp + 4 * P:2 * Dp + 4 * P + H])
         if cond:
             x = torch.empty(B, Lr, Lr, Dp, device=dev, dtype=F32)
             for b in range(B):
@@ -1909,8 +1906,7 @@ class Symmetrization(nn.Module):
 
     def forward(self, x):
         xt = torch.empty_like(x)
-        B, Lr, _, D = x.shape
-        ops.copy4d(x.contiguous(), (Lr * Lr * D, D, Lr * D, 1), xt, (Lr * Lr * D, Lr * D, D, 1), (B, Lr, Lr, D))
+        ops.copy(x.transpose(1, 2), xt)
         return ops.axpby(x.contiguous(), 0.5, xt, 0.5, torch.empty_like(x))
 
 
@@ -1978,7 +1974,7 @@ class MsaUpdateWithPairLayer(RecordingModule):
         v_t = self._values(msa, xn)
         rows = torch.empty(B, N, h, D, device=msa.device, dtype=F32)   # msa[:, :, r0:r1]
         if h > 0:
-            ops.copy4d(msa, (N * Lr * D, Lr * D, D, 1), rows, (N * h * D, h * D, D, 1), (B, N, h, D), x_off=r0 * D)
+            ops.copy(msa[:, :, r0:r1], rows)
             self._add_attention_values(att, v_t, rows)
             self._feed_forward(rows, None)
         shard.all_gather_positions(rows, msa, row_group)
@@ -2031,10 +2027,10 @@ class MsaUpdateWithPairLayer(RecordingModule):
         del v
         _unscale([datt], s)
         mk = torch.empty if Lp == Lr else ops.zeros
-        go_tt = ops.copy4d(go_t, (N * Lr * D, Lr * D, 1, D), mk(B, N, D, Lp, device=dev, dtype=T()),
-                           (N * D * Lp, D * Lp, Lp, 1), (B, N, D, Lr))        # g key-contiguous, like the forward's v^T
-        att_tr = ops.copy4d(att, (0, Lr * Lp, 1, Lp), mk(H, B, Lr, Lp, device=dev, dtype=att.dtype),
-                            (0, Lr * Lp, Lp, 1), (1, H * B, Lr, Lr))
+        go_tt = mk(B, N, D, Lp, device=dev, dtype=T())        # g key-contiguous, like the forward's v^T
+        ops.copy(go_t.transpose(2, 3), go_tt[..., :Lr])
+        att_tr = mk(H, B, Lr, Lp, device=dev, dtype=att.dtype)
+        ops.copy(att[..., :Lr].transpose(2, 3), att_tr[..., :Lr])
         del go, go_t
         dv_t = torch.empty(B, N, Lr, D, device=dev, dtype=T())
         ops.gemm(att_tr, go_tt, dv_t, Lr, N * dv, Lp, batch=(H, B, 1),
@@ -2165,7 +2161,7 @@ def _msa_update_with_pair_backward(layers, tape, g, want_pair=True):
         if s != 1.0:
             ops.axpby(dz, s, None, 0.0, dz)
         dz16 = (torch.empty if nzp == NZ else ops.zeros)(B, Lr, Lr, nzp, device=dev, dtype=T())
-        ops.copy4d(dz, (0, 0, NZ, 1), dz16, (0, 0, nzp, 1), (1, 1, B * Lr * Lr, NZ))
+        ops.copy(dz, dz16[..., :NZ])
     dwf, dbf = ops.conv_wgrad(dz16 if h16 else dz, xs, 1, bias=True)   # the folded dW' [>= NZ, Dp], db' [>= NZ]
     del xs, dz, dz16
     _unscale([dwf, dbf], s)
@@ -2174,10 +2170,9 @@ def _msa_update_with_pair_backward(layers, tape, g, want_pair=True):
     for li, layer in enumerate(layers):
         lnm, lin = layer.pair2att[1], layer.pair2att[2]
         wt32 = layer.cached("att_w_t32", lambda: lin.weight.detach().float().t().contiguous())   # W^T [Dp, H]
-        dwf_t = ops.copy4d(dwf, (0, 0, 1, Dp), torch.empty(Dp, H, device=dev, dtype=F32), (0, 0, H, 1), (1, 1, Dp, H),
-                           x_off=li * H * Dp)
+        dwf_t = ops.copy(dwf[li * H:(li + 1) * H].t(), torch.empty(Dp, H, device=dev, dtype=F32))
         dw_t, dgamma = ops.scale_rows_bwd(wt32, H, 0, dwf_t, H, 0, _f(lnm.weight), 1.0, Dp, 1, H)
-        grads[lin.weight] = ops.copy4d(dw_t, (0, 0, 1, H), torch.empty(H, Dp, device=dev, dtype=F32), (0, 0, Dp, 1), (1, 1, H, Dp))
+        grads[lin.weight] = ops.copy(dw_t.t(), torch.empty(H, Dp, device=dev, dtype=F32))
         grads[lnm.weight] = dgamma
         if rec is None:
             # both biases add one constant per head to a whole softmax row: exact zeros (float64 autograd returns rounding noise)
@@ -2450,7 +2445,7 @@ def _node_input(mod, msa, seq_onehot, out_dtype=None, tape=None):
     Kp = pad8(D + 21)
     tmp = ops.zeros(B, Lr, Kp, device=msa.device, dtype=F32)
     ops.weighted_msa_sum(m, w, tmp, Kp)
-    ops.copy4d(seq_onehot.contiguous(), (0, 0, 21, 1), tmp, (0, 0, Kp, 1), (1, 1, B * Lr, 21), y_off=D)
+    ops.copy(seq_onehot, tmp[..., D:D + 21])
     return ops.cast(tmp, out_dtype or T()), Kp
 
 
@@ -2554,7 +2549,7 @@ class InitialCoordGenerationWithMsaAndPair(RecordingModule):
         # ---- output projection
         s = _grad_scale([g])
         gp = ops.zeros(B * Lr, 16, device=dev, dtype=F32)
-        ops.copy4d(_scaled_copy(g, s), (0, 0, 9, 1), gp, (0, 0, 16, 1), (1, 1, B * Lr, 9))
+        ops.copy(_scaled_copy(g, s).view(B * Lr, 9), gp[:, :9])
         gp = ops.cast(gp, T())
         node_t = ops.cast(tape["node"], T()).view(B * Lr, -1)
         dw, db = ops.conv_wgrad(gp, node_t, 1, bias=True)
@@ -2769,7 +2764,7 @@ class ResNet(RecordingModule):
         C, Cin = lo.weight.shape[1], l0.weight.shape[1]
         co8 = pad8(Co)   # the 37 / 19 logit channels, zero-padded to 16-byte rows
         gp = ops.zeros(B, H, W, co8, device=g.device, dtype=T())
-        ops.copy4d(g, (0, 0, Co, 1), gp, (0, 0, co8, 1), (1, 1, B * H * W, Co))
+        ops.copy(g, gp[..., :Co])
         dwo, dbo = ops.conv_wgrad(gp, tape["h_last"], 1, bias=True)
         grads = {lo.weight: dwo[:Co].view(Co, C, 1, 1), lo.bias: dbo[:Co]}
         dh = ops.linear(gp, self.wt_input_grad("out", lo, co8), None, out_dtype=F32, exact=True)
@@ -2835,11 +2830,10 @@ class PredictionHead(RecordingModule):
             d[name], gr = res._backward(tape[name], _scaled_copy(gs[name], s))
             _unscale([d[name]] + list(gr.values()), s)
             grads.update(gr)
-        B, Lr, _, Cc = d["theta"].shape
         # x feeds theta / phi, xs = (x + x^T) / 2 feeds dist / omega (rf.py:1160)
         da = ops.axpby(d["dist"], 1.0, d["omega"], 1.0, d["dist"])
         dat = torch.empty_like(da)
-        ops.copy4d(da, (Lr * Lr * Cc, Cc, Lr * Cc, 1), dat, (Lr * Lr * Cc, Lr * Cc, Cc, 1), (B, Lr, Lr, Cc))
+        ops.copy(da.transpose(1, 2), dat)
         dx = ops.axpby(d["theta"], 1.0, d["phi"], 1.0, d["theta"])
         ops.axpby(dx, 1.0, da, 0.5, dx)
         ops.axpby(dx, 1.0, dat, 0.5, dx)
@@ -2865,7 +2859,7 @@ class PredictionHead(RecordingModule):
         [B, h, L, C] (contiguous split shard.shard_range(L, world, rank)); the symmetrisation (rf.py:1160) fetches the
         transposed sub-blocks from the other ranks, the ResNets exchange halo rows and InstanceNorm sums; returns the same rows
         of the logit maps."""
-        B, h, Lr, Cc = pair.shape
+        _, h, Lr, Cc = pair.shape
         _check_backward_call(self, tape, row_group, Cc, self.proj[1].weight.shape[0])
         kwc = {} if row_group is None else {"row_group": row_group, "rows_global": Lr}
         drop = None
@@ -2889,7 +2883,7 @@ class PredictionHead(RecordingModule):
                 ops.center_apply(x, ops.channel_mean(x, **kwc))
         if row_group is None:
             xt = torch.empty_like(x)
-            ops.copy4d(x, (Lr * Lr * Cc, Cc, Lr * Cc, 1), xt, (Lr * Lr * Cc, Lr * Cc, Cc, 1), (B, Lr, Lr, Cc))
+            ops.copy(x.transpose(1, 2), xt)
             kw = {}
         else:
             from . import shard

@@ -434,7 +434,8 @@ def outer_pad_depth(t, Np):
     if n == Np and t.is_contiguous():
         return t
     out = zeros(B, L_, P, Np, device=t.device, dtype=t.dtype)
-    return copy4d(t.contiguous(), (L_ * P * n, P * n, n, 1), out, (L_ * P * Np, P * Np, Np, 1), (B, L_, P, n))
+    copy(t, out[..., :n])
+    return out
 
 
 def outer_operands(x, y, dtype, multiple=8):
@@ -447,7 +448,7 @@ def outer_operands(x, y, dtype, multiple=8):
     xt = mk(B, L_, P, Np, device=x.device, dtype=dtype)
     yt = mk(B, L_, P, Np, device=x.device, dtype=dtype)
     for src, dst in ((x, xt), (y, yt)):
-        copy4d(src.contiguous(), (N * L_ * P, P, 1, L_ * P), dst, (L_ * P * Np, P * Np, Np, 1), (B, L_, P, N))
+        copy(src.permute(0, 2, 3, 1), dst[..., :N])
     return xt, yt, Np
 
 
@@ -978,11 +979,38 @@ def pair_embed(seq, aa_idx, tl, tr, wsep, bias, pe):
     return y
 
 
-def copy4d(x, xs, y, ys, dims, x_off=0, y_off=0):
-    _need_cuda(x, y)
-    check(lib.rf_copy4d(ptr(x, x_off), dcode(x.dtype), _i4(xs), ptr(y, y_off), dcode(y.dtype), _i4(ys), _i4(dims),
-                        stream()), "rf_copy4d")
-    return y
+def copy_walk(shape, src_strides, dst_strides):
+    """(dims, xs, ys) of the row-major walk of one copy: dimensions of size 1 dropped, and a dimension merged into its right
+    neighbour where both sides step contiguously from one into the other.  The sequence of (source, destination) addresses is
+    that of the full shape; only the constants the kernel divides by change.  Host arithmetic on integers only."""
+    dims, xs, ys = [], [], []
+    for n, sx, sy in zip(shape, src_strides, dst_strides):
+        n, sx, sy = int(n), int(sx), int(sy)
+        if n == 1:
+            continue
+        if dims and xs[-1] == sx * n and ys[-1] == sy * n:
+            dims[-1], xs[-1], ys[-1] = dims[-1] * n, sx, sy
+        else:
+            dims.append(n), xs.append(sx), ys.append(sy)
+    return tuple(dims), tuple(xs), tuple(ys)
+
+
+def copy(src, dst):
+    """dst.copy_(src) by rf_copy4d between two views of equal shape (any rank that merges to four dimensions; fp32 <-> 16-bit
+    converts).  The elements are walked row-major over the views' shape, so the side that carries the permute is the strided
+    one.  Returns dst."""
+    _need_cuda(src, dst)
+    if src.shape != dst.shape:
+        raise ValueError(f"copy: shapes differ: {tuple(src.shape)} and {tuple(dst.shape)}")
+    dims, xs, ys = copy_walk(src.shape, src.stride(), dst.stride())
+    if len(dims) > 4:
+        raise ValueError(f"copy: {tuple(src.shape)} with strides {src.stride()} -> {dst.stride()} needs {len(dims)} dimensions")
+    if any(n > 1 and s == 0 for n, s in zip(dims, ys)):
+        raise ValueError(f"copy: the destination repeats elements (strides {dst.stride()} of shape {tuple(dst.shape)})")
+    pad = 4 - len(dims)
+    check(lib.rf_copy4d(ptr(src), dcode(src.dtype), _i4((0,) * pad + xs), ptr(dst), dcode(dst.dtype), _i4((0,) * pad + ys),
+                        _i4((1,) * pad + dims), stream()), "rf_copy4d")
+    return dst
 
 
 def cast(x, dtype):
@@ -1162,11 +1190,9 @@ def se3_attention(k0, k1, q0, q1, v0, v1, eid, heads, mk0, mk1, mv0, mv1, V, L_,
     check(lib.rf_se3_attention(ptr(k0), ptr(k1), ptr(q0), ptr(q1), ptr(v0), ptr(v1), ptr(eid), ptr(out0), ptr(out1),
                                heads, mk0, mk1, mv0, mv1, V, L_, c0, 3 * c1, stream()), "rf_se3_attention")
     if skip0 is not None:
-        m = skip0.shape[1]
-        copy4d(skip0, (0, 0, m, 1), out0, (0, 0, c0, 1), (1, 1, V, m), y_off=mv0)
+        copy(skip0, out0[:, mv0:])
     if skip1 is not None:
-        m = skip1.shape[1] * 3
-        copy4d(skip1, (0, 0, m, 1), out1, (0, 0, 3 * c1, 1), (1, 1, V, m), y_off=3 * mv1)
+        copy(skip1, out1[:, mv1:])
     return out0, out1
 
 

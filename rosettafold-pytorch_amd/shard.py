@@ -161,28 +161,25 @@ def exchange_row_halos(x, d, group=None):
     check_row_split(W, n, d)  # (square pictures: W = the number of rows of the whole picture) -- the same verdict on every rank
     if h < d:
         raise ValueError(f"row block of {h} rows is lower than the halo of {d}: halos would span more than one neighbour")
-    row = W * Cc
     xh = ops.zeros(B, h + 2 * d, W, Cc, device=x.device, dtype=x.dtype)
-    ops.copy4d(x, (h * row, row, Cc, 1), xh, ((h + 2 * d) * row, row, Cc, 1), (B, h, W, Cc), y_off=d * row)
+    ops.copy(x, xh[:, d:d + h])
     if n == 1:
         return xh
     host = dist.get_backend(group) == "gloo"
-    cut = lambda off: ops.copy4d(x, (h * row, row, Cc, 1), torch.empty(B, d, W, Cc, device=x.device, dtype=x.dtype),  # noqa: E731
-                                 (d * row, row, Cc, 1), (B, d, W, Cc), x_off=off)
     ops_, recv = [], {}
-    for peer, send_off, place_off in ((r - 1, 0, 0), (r + 1, (h - d) * row, (d + h) * row)):
+    for peer, send_row, place_row in ((r - 1, 0, 0), (r + 1, h - d, d + h)):
         if 0 <= peer < n:
-            out = cut(send_off)
+            out = ops.copy(x[:, send_row:send_row + d], torch.empty(B, d, W, Cc, device=x.device, dtype=x.dtype))
             buf = torch.empty(B, d, W, Cc, device="cpu" if host else x.device, dtype=x.dtype)
             ops_.append(dist.P2POp(dist.isend, out.cpu() if host else out, _peer(group, peer), group))
             ops_.append(dist.P2POp(dist.irecv, buf, _peer(group, peer), group))
-            recv[place_off] = buf
+            recv[place_row] = buf
     if not host:
         torch.cuda.current_stream().synchronize()  # the send buffers are complete before RCCL's stream reads them
     for w in dist.batch_isend_irecv(ops_):
         w.wait()
-    for place_off, buf in recv.items():
-        ops.copy4d(buf.to(x.device), (d * row, row, Cc, 1), xh, ((h + 2 * d) * row, row, Cc, 1), (B, d, W, Cc), y_off=place_off)
+    for place_row, buf in recv.items():
+        ops.copy(buf.to(x.device), xh[:, place_row:place_row + d])
     return xh
 
 
@@ -190,9 +187,8 @@ def drop_row_halos(y, d):
     """[B, h + 2 d, W, C] -> the contiguous inner [B, h, W, C]."""
     from . import ops
     B, hh, W, Cc = y.shape
-    h, row = hh - 2 * d, W * Cc
-    out = torch.empty(B, h, W, Cc, device=y.device, dtype=y.dtype)
-    return ops.copy4d(y, (hh * row, row, Cc, 1), out, (h * row, row, Cc, 1), (B, h, W, Cc), x_off=d * row)
+    h = hh - 2 * d
+    return ops.copy(y[:, d:d + h], torch.empty(B, h, W, Cc, device=y.device, dtype=y.dtype))
 
 
 def resblock_row_sharded(block, x_rows, rows_global, group=None):
@@ -217,7 +213,6 @@ def transpose_row_sharded(x_rows, group=None):
     if r1 - r0 != h:
         raise ValueError(f"rank {r} holds {h} rows; the contiguous split of {Lr} rows over {n} ranks gives it {r1 - r0}")
     out = torch.empty_like(x_rows)
-    row = Lr * Cc
     host = n > 1 and dist.get_backend(group) == "gloo"
     ops_, recv = [], {}
     for s_ in range(n):
@@ -226,11 +221,10 @@ def transpose_row_sharded(x_rows, group=None):
         if hs == 0 or h == 0:
             continue
         if s_ == r:  # the diagonal block never leaves: one transposing copy  out[b, i, r0 + j] = x[b, j, r0 + i]
-            ops.copy4d(x_rows, (h * row, Cc, row, 1), out, (h * row, row, Cc, 1), (B, h, h, Cc), x_off=r0 * Cc, y_off=r0 * Cc)
+            ops.copy(x_rows[:, :, r0:r1].transpose(1, 2), out[:, :, r0:r1])
             continue
         # my rows, columns of rank s: [B, h, hs, C] contiguous
-        blk = ops.copy4d(x_rows, (h * row, row, Cc, 1), torch.empty(B, h, hs, Cc, device=x_rows.device, dtype=x_rows.dtype),
-                         (h * hs * Cc, hs * Cc, Cc, 1), (B, h, hs, Cc), x_off=s0 * Cc)
+        blk = ops.copy(x_rows[:, :, s0:s1], torch.empty(B, h, hs, Cc, device=x_rows.device, dtype=x_rows.dtype))
         buf = torch.empty(B, hs, h, Cc, device="cpu" if host else x_rows.device, dtype=x_rows.dtype)  # rank s's rows, my columns
         ops_.append(dist.P2POp(dist.isend, blk.cpu() if host else blk, _peer(group, s_), group))
         ops_.append(dist.P2POp(dist.irecv, buf, _peer(group, s_), group))
@@ -242,9 +236,8 @@ def transpose_row_sharded(x_rows, group=None):
             w.wait()
     for s_, buf in recv.items():
         s0, s1 = shard_range(Lr, n, s_)
-        hs = s1 - s0
         # buf[b, j - s0, i - r0, c] -> out[b, i - r0, j, c]
-        ops.copy4d(buf.to(x_rows.device), (hs * h * Cc, Cc, h * Cc, 1), out, (h * row, row, Cc, 1), (B, h, hs, Cc), y_off=s0 * Cc)
+        ops.copy(buf.to(x_rows.device).transpose(1, 2), out[:, :, s0:s1])
     return out
 
 
@@ -271,13 +264,13 @@ def all_gather_positions(rows, full, group=None):
     Lr = full.shape[2]
     n, r = group_size(group), group_rank(group)
     if n == 1 and not (_FORCE and dist.is_initialized()):
-        ops.copy4d(rows, (N * h * D, h * D, D, 1), full, (N * Lr * D, Lr * D, D, 1), (B, N, h, D))
+        ops.copy(rows, full[:, :, :h])
         return full
     hmax = max(shard_range(Lr, n, k)[1] - shard_range(Lr, n, k)[0] for k in range(n))
     host = dist.get_backend(group) == "gloo"
     send = ops.zeros(B, N, hmax, D, device=rows.device, dtype=rows.dtype)
     if h > 0:
-        ops.copy4d(rows, (N * h * D, h * D, D, 1), send, (N * hmax * D, hmax * D, D, 1), (B, N, h, D))
+        ops.copy(rows, send[:, :, :h])
     if host:
         send = send.cpu()
     else:
@@ -287,8 +280,7 @@ def all_gather_positions(rows, full, group=None):
     for k, buf in enumerate(bufs):
         k0, k1 = shard_range(Lr, n, k)
         if k1 > k0:
-            ops.copy4d(buf.to(full.device), (N * hmax * D, hmax * D, D, 1), full, (N * Lr * D, Lr * D, D, 1),
-                       (B, N, k1 - k0, D), y_off=k0 * D)
+            ops.copy(buf.to(full.device)[:, :, :k1 - k0], full[:, :, k0:k1])
     return full
 
 
@@ -324,12 +316,11 @@ def take_rows(full, group=None):
     """This rank's rows shard_range(L, world, rank) of a replicated [B, L, ...] tensor, as a contiguous copy."""
     from . import ops
     B, Lr = full.shape[:2]
-    inner = full.numel() // max(B * Lr, 1)
     r0, r1 = shard_range(Lr, group_size(group), group_rank(group))
     h = r1 - r0
     out = torch.empty((B, h) + tuple(full.shape[2:]), device=full.device, dtype=full.dtype)
     if h > 0:
-        ops.copy4d(full.contiguous(), (Lr * inner, inner, 0, 1), out, (h * inner, inner, 0, 1), (B, h, 1, inner), x_off=r0 * inner)
+        ops.copy(full[:, r0:r1], out)
     return out
 
 

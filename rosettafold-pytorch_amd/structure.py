@@ -495,9 +495,9 @@ class MsaUpdateWithPairAndCoord(RecordingModule):
         del v
         _unscale([datt], s)
         dout_tt = torch.empty(B, N, D, Lr, device=dev, dtype=att.dtype)   # d out key-contiguous, like the forward's v^T
-        ops.copy4d(dout_t, (N * Lr * D, Lr * D, 1, D), dout_tt, (N * D * Lr, D * Lr, Lr, 1), (B, N, D, Lr))
+        ops.copy(dout_t.transpose(2, 3), dout_tt)
         att_tr = torch.empty(B, H, Lr, Lr, device=dev, dtype=att.dtype)
-        ops.copy4d(att, (0, Lr * Lr, 1, Lr), att_tr, (0, Lr * Lr, Lr, 1), (1, B * H, Lr, Lr))
+        ops.copy(att.transpose(2, 3), att_tr)
         del att, dout, dout_t
         dv_t = torch.empty(B, N, Lr, D, device=dev, dtype=att_tr.dtype)   # (fp32 where the map is: _map_dtype)
         ops.gemm(att_tr, dout_tt, dv_t, Lr, N * dv, Lr, batch=(B, H, 1),

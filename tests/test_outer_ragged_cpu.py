@@ -82,7 +82,7 @@ def test_outer_depth():
 def test_outer_operands_default_shapes(monkeypatch):
     """shapes only: the copies and the fill are device work, replaced here by host allocations"""
     monkeypatch.setattr(ops, "zeros", lambda *s, device=None, dtype=None: torch.zeros(*s, dtype=dtype))
-    monkeypatch.setattr(ops, "copy4d", lambda x, xs, y, ys, dims, **kw: y)
+    monkeypatch.setattr(ops, "copy", lambda src, dst: dst)
     for N in (1, 5, 8, 72, 100, 128, 130):
         x = torch.zeros(2, N, 7, 32)
         xt, yt, Np = ops.outer_operands(x, x, torch.bfloat16)
@@ -91,3 +91,18 @@ def test_outer_operands_default_shapes(monkeypatch):
         if N <= 128:
             xt, yt, Np = ops.outer_operands(x, x, torch.bfloat16, ops.outer_depth(N))
             assert Np == (64 if N <= 64 else 128) and xt.shape == (2, 7, 32, Np)
+
+
+def test_outer_operands_values(monkeypatch):
+    """the layout itself, with the copy's contract dst.copy_(src) in the kernel's place: the depth moves innermost, zero-padded"""
+    monkeypatch.setattr(ops, "zeros", lambda *s, device=None, dtype=None: torch.zeros(*s, dtype=dtype))
+    monkeypatch.setattr(ops, "copy", lambda s, d: d.copy_(s))
+    B, N, L_, P = 2, 5, 7, 3
+    g = torch.Generator().manual_seed(5)
+    x, y = torch.randn(B, N, L_, P, generator=g), torch.randn(B, N, L_, P, generator=g)
+    xt, yt, Np = ops.outer_operands(x, y, torch.float32)
+    assert Np == 8 and xt.shape == yt.shape == (B, L_, P, Np)
+    for src, dst in ((x, xt), (y, yt)):
+        want = torch.zeros(B, L_, P, Np)
+        want[..., :N] = src.permute(0, 2, 3, 1)
+        assert torch.equal(dst, want)
