@@ -789,6 +789,44 @@ int rf_pair_softmax_bwd(const float* logits, const float* datt, int64_t datt_ld,
 int rf_sym_layernorm_bwd(const float* pair, const float* dz, const float* w, float* dpair, int B, int L, int D, int NZ, float eps,
                          void* stream);
 
+/* ---- backward pass of MsaEmbedding and PairEmbedding (csrc/backward.hip; model.py, rf.py:106-181) ---------------------------
+ * Gradient of an embedding table (rf_version >= 21).  idx: int64 [rows], the token of each row; g: fp32 [rows, D], contiguous,
+ * the gradient of dropout(table[idx] + ...) + query_enc; dtable: fp32 [V, D]:
+ *   dtable[t, c] = sum over the rows r with idx[r] == t of keep(r, c) / (1 - p) * g[r, c]
+ * with keep the keep / drop decision of element r * D + c of rf_dropout's mask (p, seed, offset) over the contiguous [rows, D]
+ * tensor, replayed inside the kernel; the term is rf_dropout's own fp32 product g * (1 / (1 - p)).  p = 0: no dropout (seed and
+ * offset are not read).  dq, may be NULL: fp32 [2, D], the gradient of the two query-encoding rows from the UNMASKED g (the
+ * reference adds query_enc behind the dropout): with row r = (b, n, l) of [.., N, L], n = (r / L) % N,
+ *   dq[0, c] = sum over the rows with n == 0 of g[r, c],   dq[1, c] = sum over the rows with n >= 1 of g[r, c]
+ * The pair side calls it with rows = B * L, idx = seq and N = 1 (N and L are read for dq only).
+ * Accumulation: every sum in fp64, rounded once.  A wave owns 256 consecutive rows and 64 channels and keeps its [V, 64] sums in
+ * LDS; a block of 4, 2 or 1 waves (the most whose sums fit 64 KB) writes one fp64 partial [V + 2, D] to the workspace, and a
+ * second launch adds the partials in block order: no atomics, the same bits run to run.  g is read once.  A table row whose
+ * index never occurs is written as exact zeros, as is dq[1] at N == 1; a row whose index lies outside [0, V) adds to dq only.
+ * EVERY element of dtable (and of dq) is written, nothing else is.  Workspace (8-byte aligned): rf_embedding_bwd_ws_bytes bytes
+ * (0: an empty or refused problem).
+ * RF_EINVAL before any launch: idx, g, dtable or the workspace NULL, a size <= 0, p outside [0, 1), a workspace too small, or
+ * (V + 2) * 512 bytes of LDS > 64 KB (V > 126). */
+int64_t rf_embedding_bwd_ws_bytes(int64_t rows, int D, int V);
+int rf_embedding_bwd(const int64_t* idx, const float* g, float* dtable, float* dq, int64_t rows, int D, int V, int N, int L, float p,
+                     uint64_t seed, uint64_t offset, void* workspace, int64_t ws_bytes, void* stream);
+/* The sums of a pair-shaped gradient over each picture axis, and the gradients of rf_pair_embed's separation column and bias
+ * (rf_version >= 21).  g: fp32 [B,L,L,D], contiguous; aa_idx: int64 [B,L]:
+ *   rows[b,i,c] = sum_j g[b,i,j,c]            cols[b,j,c] = sum_i g[b,i,j,c]            (fp32 [B,L,D] each)
+ *   dsep[c]  = sum_{b,i,j} g[b,i,j,c] * logf((float)(|aa_idx[b,i] - aa_idx[b,j]| + 1))   (fp32 [D]; the forward's own expression)
+ *   dbias[c] = sum_{b,i,j} g[b,i,j,c]                                                    (fp32 [D])
+ * By linearity these are what every feature tiled along one axis of a pair picture needs for its gradient.
+ * Accumulation: every sum in fp64 (the product with the fp32 separation is exact there), rounded once.  g is read once: a block
+ * takes 16 rows x 64 columns of one sample and 64 channels, writes the column sums of its 16 rows and the row sums of its 64
+ * columns as fp64 partials, and a second launch adds the row tiles' (column tiles', blocks') partials in ascending order: no
+ * atomics, the same bits run to run.  L == 1: dsep = 0 exactly.  EVERY element of the four outputs is written, nothing else is.
+ * Workspace (8-byte aligned): rf_pair_axis_sums_ws_bytes bytes.  The LDS need is 40 KB at every shape.
+ * RF_EINVAL before any launch: a NULL tensor or workspace, a size <= 0, a workspace too small, or
+ * B * ceil(L/16) * ceil(L/64) >= 2^31. */
+int64_t rf_pair_axis_sums_ws_bytes(int B, int L, int D);
+int rf_pair_axis_sums(const float* g, const int64_t* aa_idx, float* rows, float* cols, float* dsep, float* dbias, int B, int L,
+                      int D, void* workspace, int64_t ws_bytes, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

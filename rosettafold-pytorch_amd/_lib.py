@@ -130,6 +130,10 @@ PROTOTYPES = {
     "rf_scale_rows_bwd": [vp, i32, i64, i64, vp, i32, i64, i64, vp, f32, vp, i32, i64, i64, vp, i64, i32, i32, vp],
     "rf_pair_softmax_bwd": [vp, vp, i64, vp, vp, i32, i32, i32, i32, vp],
     "rf_sym_layernorm_bwd": [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "rf_embedding_bwd_ws_bytes": [i64, i32, i32],  # returns int64
+    "rf_embedding_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, u64, vp, i64, vp],
+    "rf_pair_axis_sums_ws_bytes": [i32, i32, i32],  # returns int64
+    "rf_pair_axis_sums": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp],
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],
@@ -155,6 +159,8 @@ def _load(path):
     handle.rf_conv_wgrad_ws_bytes.restype = C.c_int64
     handle.rf_layernorm_bwd_ws_bytes.restype = C.c_int64
     handle.rf_layernorm_bwd_fused_ws_bytes.restype = C.c_int64
+    handle.rf_embedding_bwd_ws_bytes.restype = C.c_int64
+    handle.rf_pair_axis_sums_ws_bytes.restype = C.c_int64
     handle.rf_build_info.restype = C.c_char_p
     handle.rf_build_info.argtypes = []
     return handle

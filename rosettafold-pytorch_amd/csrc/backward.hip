@@ -1754,3 +1754,253 @@ extern "C" int rf_sym_layernorm_bwd(const float* pair, const float* dz, const fl
 #undef SLB_LAUNCH
   return rf_launch_status();
 }
+
+// ================================================================================================
+// Backward of MsaEmbedding and PairEmbedding (model.py; rf.py:106-181): the gradient of an embedding table (a reduction of the
+// output gradient keyed by the token index, with the forward's dropout mask replayed) and the sums of a pair-shaped gradient
+// over each of its two picture axes.  Both read the gradient once, accumulate in fp64 and write fp64 partials to a
+// caller-owned workspace, which one launch of ordered_sum_f64_kernel adds in a fixed order and rounds once: no atomics.
+// ================================================================================================
+// out[x] = (float) sum_{k = 0 .. S-1} part[k * stride + x] for up to four independent segments laid end to end
+struct SumSeg {
+  const double* part;
+  float* out;
+  int64_t n, stride;
+  int S;
+};
+struct SumSegs {
+  SumSeg s[4];
+};
+
+__global__ __launch_bounds__(256) void ordered_sum_f64_kernel(SumSegs a, int64_t total) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const double* part = nullptr;
+    float* out = nullptr;
+    int64_t x = e, stride = 0;
+    int S = 0;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (!found && x < a.s[k].n) {
+        part = a.s[k].part + x, out = a.s[k].out + x, stride = a.s[k].stride, S = a.s[k].S;
+        found = true;
+      }
+      if (!found) x -= a.s[k].n;
+    }
+    if (!found) continue;
+    double s = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < S; ++k) s += part[(int64_t)k * stride];
+    *out = (float)s;
+  }
+}
+
+static inline void launch_ordered_sum(const SumSegs& segs, hipStream_t s) {
+  int64_t total = 0;
+  for (int k = 0; k < 4; ++k) total += segs.s[k].n;
+  hipLaunchKernelGGL(ordered_sum_f64_kernel, dim3(min(cdiv(total, 256), 16384u)), dim3(256), 0, s, segs, total);
+}
+
+// ---- rf_embedding_bwd -----------------------------------------------------------------------------------------------------------
+// A wave owns EMB_ROWS consecutive rows and 64 channels (one per lane); a block is W = 4, 2 or 1 such waves on consecutive row
+// ranges.  Each wave keeps fp64 sums [V][64] of its own in LDS, every entry touched by its one lane only (no synchronisation
+// while accumulating), and the two query-encoding sums in registers; the block adds its waves' sums in wave order and writes
+// one partial [V + 2][D-tile] per block.  W is the largest count whose sums fit 64 KB of LDS.
+#define EMB_ROWS 256
+#define EMB_LDS_LIMIT (64 * 1024)
+
+static inline int emb_waves(int V) {
+  for (int W = 4; W >= 1; W >>= 1)
+    if ((size_t)W * (V + 2) * 64 * sizeof(double) <= EMB_LDS_LIMIT) return W;
+  return 0;
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __restrict__ idx, const float* __restrict__ g,
+                                                            double* __restrict__ part, int64_t rows, int D, int V, int N, int L,
+                                                            unsigned thresh, float inv_keep, uint64_t seed, uint64_t offset) {
+  extern __shared__ double emb_acc[];  // [W][V + 2][64]
+  const int W = blockDim.x >> 6, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.y * 64 + lane;
+  const int T = V + 2;
+  double* mine = emb_acc + (size_t)w * T * 64 + lane;
+  for (int t = 0; t < T; ++t) mine[t * 64] = 0.0;
+  const int64_t r0 = ((int64_t)blockIdx.x * W + w) * EMB_ROWS;
+  const int64_t r1 = r0 + EMB_ROWS < rows ? r0 + EMB_ROWS : rows;
+  if (c < D && r0 < r1) {
+    int l = (int)(r0 % L), n = (int)((r0 / L) % N);  // the row's position (n, l) of [.., N, L], stepped with the row
+    double q0 = 0.0, q1 = 0.0;
+    for (int64_t r = r0; r < r1; r += 8) {
+      float v[8];
+      int64_t t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const bool ok = r + u < r1;
+        t[u] = ok ? idx[r + u] : -1;
+        v[u] = ok ? g[(r + u) * D + c] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (r + u < r1) {
+          if (n == 0)
+            q0 += (double)v[u];
+          else
+            q1 += (double)v[u];
+          if (++l == L) {
+            l = 0;
+            if (++n == N) n = 0;
+          }
+          if ((uint64_t)t[u] < (uint64_t)V) {  // (an index outside the table contributes nothing)
+            float m = v[u];
+            if (DROP) m = dropout_keep(seed, offset, (r + u) * D + c, thresh) ? m * inv_keep : 0.f;  // rf_dropout's own product
+            mine[t[u] * 64] += (double)m;
+          }
+        }
+      }
+    }
+    mine[V * 64] = q0;
+    mine[(V + 1) * 64] = q1;
+  }
+  __syncthreads();
+  if (c < D)
+    for (int t = w; t < T; t += W) {
+      double s = 0.0;
+      for (int k = 0; k < W; ++k) s += emb_acc[((size_t)k * T + t) * 64 + lane];
+      part[((int64_t)blockIdx.x * T + t) * D + c] = s;
+    }
+}
+
+static inline int64_t emb_blocks(int64_t rows, int W) { return (rows + (int64_t)W * EMB_ROWS - 1) / ((int64_t)W * EMB_ROWS); }
+
+extern "C" int64_t rf_embedding_bwd_ws_bytes(int64_t rows, int D, int V) {
+  if (rows <= 0 || D <= 0 || V <= 0) return 0;
+  const int W = emb_waves(V);
+  if (!W) return 0;
+  return emb_blocks(rows, W) * (V + 2) * D * (int64_t)sizeof(double);
+}
+
+// include/rfmi.h: rf_embedding_bwd
+extern "C" int rf_embedding_bwd(const int64_t* idx, const float* g, float* dtable, float* dq, int64_t rows, int D, int V, int N,
+                                int L, float p, uint64_t seed, uint64_t offset, void* workspace, int64_t ws_bytes, void* stream) {
+  if (!idx || !g || !dtable || rows <= 0 || D <= 0 || V <= 0 || N <= 0 || L <= 0) return RF_EINVAL;
+  if (!(p >= 0.f) || !(p < 1.f)) return RF_EINVAL;
+  const int W = emb_waves(V);
+  if (!W) return RF_EINVAL;
+  const int64_t nblk = emb_blocks(rows, W);
+  if (nblk > 0x7fffffff || cdiv(D, 64) > 65535u) return RF_EINVAL;
+  if (!workspace || ((uintptr_t)workspace % 8) || ws_bytes < rf_embedding_bwd_ws_bytes(rows, D, V)) return RF_EINVAL;
+  double* part = (double*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nblk, cdiv(D, 64));
+  const size_t lds = (size_t)W * (V + 2) * 64 * sizeof(double);
+  if (p > 0.f)
+    hipLaunchKernelGGL(embedding_bwd_kernel<true>, grid, dim3(64 * W), lds, s, idx, g, part, rows, D, V, N, L,
+                       dropout_threshold(p), 1.f / (1.f - p), seed, offset);
+  else
+    hipLaunchKernelGGL(embedding_bwd_kernel<false>, grid, dim3(64 * W), lds, s, idx, g, part, rows, D, V, N, L, 0u, 1.f, seed,
+                       offset);
+  const int64_t T = V + 2;
+  SumSegs segs = {};
+  segs.s[0] = {part, dtable, (int64_t)V * D, T * D, (int)nblk};
+  if (dq) segs.s[1] = {part + (int64_t)V * D, dq, (int64_t)2 * D, T * D, (int)nblk};
+  launch_ordered_sum(segs, s);
+  return rf_launch_status();
+}
+
+// ---- rf_pair_axis_sums ----------------------------------------------------------------------------------------------------------
+// A block takes a PAS_TI x PAS_TJ tile (i, j) of one sample's picture and 64 channels (one per lane).  Wave w walks the tile's
+// columns j = w, w + 4, ..: per column the PAS_TI rows are loaded together, their sum is the column's partial for this row tile
+// (written at once), and each adds to the row's fp64 register sum and, times the separation feature, to dsep's.  The four waves'
+// row sums meet in LDS and are added in wave order into the row partial of this column tile; so do their dsep and dbias sums.
+#define PAS_TI 16
+#define PAS_TJ 64
+
+__global__ __launch_bounds__(256) void pair_axis_sums_kernel(const float* __restrict__ g, const int64_t* __restrict__ aa_idx,
+                                                             double* __restrict__ colp, double* __restrict__ rowp,
+                                                             double* __restrict__ sbp, int B, int L, int D, int nIt, int nJt) {
+  __shared__ float sep[PAS_TI][PAS_TJ];
+  __shared__ double red[4][PAS_TI][64];
+  __shared__ double red2[4][2][64];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.y * 64 + lane;
+  const int bid = blockIdx.x;
+  const int jt = bid % nJt, it = (bid / nJt) % nIt, b = bid / (nJt * nIt);
+  const int i0 = it * PAS_TI, j0 = jt * PAS_TJ;
+  for (int t = threadIdx.x; t < PAS_TI * PAS_TJ; t += 256) {
+    const int ii = t / PAS_TJ, jj = t % PAS_TJ;
+    float sv = 0.f;
+    if (i0 + ii < L && j0 + jj < L) {  // the forward's own expression (pair_embed_kernel, csrc/ops.hip)
+      const int64_t a = aa_idx[(int64_t)b * L + i0 + ii], e = aa_idx[(int64_t)b * L + j0 + jj];
+      const int64_t dd = a > e ? a - e : e - a;
+      sv = logf((float)(dd + 1));
+    }
+    sep[ii][jj] = sv;
+  }
+  __syncthreads();
+  const bool on = c < D;
+  double racc[PAS_TI];
+#pragma unroll
+  for (int ii = 0; ii < PAS_TI; ++ii) racc[ii] = 0.0;
+  double ds = 0.0;
+  for (int jj = w; jj < PAS_TJ; jj += 4) {
+    const int j = j0 + jj;
+    if (j >= L) break;
+    float v[PAS_TI];
+#pragma unroll
+    for (int ii = 0; ii < PAS_TI; ++ii)
+      v[ii] = (on && i0 + ii < L) ? g[(((int64_t)b * L + i0 + ii) * L + j) * D + c] : 0.f;
+    double cacc = 0.0;
+#pragma unroll
+    for (int ii = 0; ii < PAS_TI; ++ii) {
+      const double x = (double)v[ii];
+      cacc += x;
+      racc[ii] += x;
+      ds += x * (double)sep[ii][jj];
+    }
+    if (on) colp[(((int64_t)it * B + b) * L + j) * D + c] = cacc;
+  }
+  double db = 0.0;
+#pragma unroll
+  for (int ii = 0; ii < PAS_TI; ++ii) {
+    red[w][ii][lane] = racc[ii];
+    db += racc[ii];
+  }
+  red2[w][0][lane] = ds;
+  red2[w][1][lane] = db;
+  __syncthreads();
+  if (!on) return;
+  for (int ii = w; ii < PAS_TI; ii += 4)
+    if (i0 + ii < L)
+      rowp[(((int64_t)jt * B + b) * L + i0 + ii) * D + c] = ((red[0][ii][lane] + red[1][ii][lane]) + red[2][ii][lane]) + red[3][ii][lane];
+  if (w < 2) sbp[((int64_t)bid * 2 + w) * D + c] = ((red2[0][w][lane] + red2[1][w][lane]) + red2[2][w][lane]) + red2[3][w][lane];
+}
+
+extern "C" int64_t rf_pair_axis_sums_ws_bytes(int B, int L, int D) {
+  if (B <= 0 || L <= 0 || D <= 0) return 0;
+  const int64_t nIt = cdiv(L, PAS_TI), nJt = cdiv(L, PAS_TJ);
+  return ((nIt + nJt) * B * L + 2 * (int64_t)B * nIt * nJt) * D * (int64_t)sizeof(double);
+}
+
+// include/rfmi.h: rf_pair_axis_sums
+extern "C" int rf_pair_axis_sums(const float* g, const int64_t* aa_idx, float* rows, float* cols, float* dsep, float* dbias, int B,
+                                 int L, int D, void* workspace, int64_t ws_bytes, void* stream) {
+  if (!g || !aa_idx || !rows || !cols || !dsep || !dbias || B <= 0 || L <= 0 || D <= 0) return RF_EINVAL;
+  const int64_t nIt = cdiv(L, PAS_TI), nJt = cdiv(L, PAS_TJ);
+  const int64_t nblk = (int64_t)B * nIt * nJt;
+  if (nblk > 0x7fffffff || cdiv(D, 64) > 65535u) return RF_EINVAL;
+  if (!workspace || ((uintptr_t)workspace % 8) || ws_bytes < rf_pair_axis_sums_ws_bytes(B, L, D)) return RF_EINVAL;
+  const int64_t bld = (int64_t)B * L * D;
+  double* colp = (double*)workspace;
+  double* rowp = colp + nIt * bld;
+  double* sbp = rowp + nJt * bld;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pair_axis_sums_kernel, dim3((unsigned)nblk, cdiv(D, 64)), dim3(256), 0, s, g, aa_idx, colp, rowp, sbp, B, L, D,
+                     (int)nIt, (int)nJt);
+  SumSegs segs = {};
+  segs.s[0] = {colp, cols, bld, bld, (int)nIt};
+  segs.s[1] = {rowp, rows, bld, bld, (int)nJt};
+  segs.s[2] = {sbp, dsep, (int64_t)D, (int64_t)2 * D, (int)nblk};
+  segs.s[3] = {sbp + D, dbias, (int64_t)D, (int64_t)2 * D, (int)nblk};
+  launch_ordered_sum(segs, s);
+  return rf_launch_status();
+}

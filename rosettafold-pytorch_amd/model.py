@@ -477,8 +477,20 @@ class SinusoidalPositionalEncoding2D(RFModule):
         return ops.add_pos_enc(x.float().contiguous(), aa_idx, self.pos_enc, two_d=True)
 
 
-class MsaEmbedding(RFModule):
-    """rf.py:106-120."""
+def _f32_gradient(g):
+    """the output gradient autograd hands in, as a contiguous fp32 tensor (itself when it already is one)"""
+    return g if g.dtype == F32 and g.is_contiguous() else g.float().contiguous()
+
+
+class MsaEmbedding(RecordingModule):
+    """rf.py:106-120.  enable_backward(): with grad mode on, forward(x, aa_idx) records, and loss.backward() fills the .grad of
+    to_embedding and query_enc through one rf_embedding_bwd call (include/rfmi.h) over the [B, N, L, d_msa] gradient; the two
+    integer inputs carry no gradient and the positional table is a buffer.  In train() mode the backward replays the dropout of
+    the positional-encoding site inside that kernel; query_enc is added behind the dropout and takes the unmasked gradient.
+    Everything is fp32 in every compute mode: no channel count is restricted and nothing needs the fp16 mode's scale.
+    RoseTTAFold._trunk calls run() without a tape and never records here."""
+    _rf_n_inputs = 2   # x, aa_idx (integers: no gradient)
+    _rf_scales_own_grads = True   # (there is nothing to scale: no 16-bit operand anywhere)
 
     def __init__(self, d_input=21, d_msa=384, max_len=260, p_pe_drop=0.1):
         super().__init__()
@@ -488,25 +500,62 @@ class MsaEmbedding(RFModule):
 
     def forward(self, x, aa_idx):
         check_index_range(x.contiguous(), None, aa_idx.contiguous(), self.to_embedding.num_embeddings, self.pos_enc.max_len)
+        if _recording(self):
+            return _RecordedFn.apply(self, x, aa_idx, *self.parameters())
         return self.run(x, aa_idx)
 
-    def run(self, x, aa_idx):
-        """(indices already validated)"""
+    def run(self, x, aa_idx, tape=None):
+        """(indices already validated)  tape: a dict that receives what _backward needs (the tokens and the dropout record; same
+        kernels, same numbers)."""
         emb, pe, qe = _f(self.to_embedding.weight), self.pos_enc.pos_enc, _f(self.query_enc.weight)
         pd = self.pos_enc.p_dropout if self.training else 0.0
+        x = x.contiguous()
+        rec = None
         if pd and pd > 0:
             # rf.py:114-120: dropout(emb[msa] + pe[aa_idx]) + query_enc -- the dropout sits between the two additions
-            y = dropout_(ops.msa_embed(x.contiguous(), aa_idx.contiguous(), emb, pe, ops.zeros(*qe.shape, device=qe.device, dtype=F32)), pd)
-            yq = ops.msa_embed(x.contiguous(), aa_idx.contiguous(), ops.zeros(*emb.shape, device=emb.device, dtype=F32),
+            y = ops.msa_embed(x, aa_idx.contiguous(), emb, pe, ops.zeros(*qe.shape, device=qe.device, dtype=F32))
+            rec = _dropout_rec(y, pd)
+            yq = ops.msa_embed(x, aa_idx.contiguous(), ops.zeros(*emb.shape, device=emb.device, dtype=F32),
                                ops.zeros(*pe.shape, device=pe.device, dtype=F32), qe)
-            return ops.axpby(y, 1.0, yq, 1.0, y)
-        return ops.msa_embed(x.contiguous(), aa_idx.contiguous(), emb, pe, qe)
+            y = ops.axpby(y, 1.0, yq, 1.0, y)
+        else:
+            y = ops.msa_embed(x, aa_idx.contiguous(), emb, pe, qe)
+        if tape is not None:
+            tape.update(x=x, drop=rec)
+        return y
+
+    def _record(self, x, aa_idx, tape):
+        return self.run(x, aa_idx, tape=tape)
+
+    def _backward(self, tape, g):
+        """g: contiguous fp32 [B, N, L, d_msa] gradient of the output (read once).  Returns {param: grad}: d to_embedding from the
+        masked gradient keyed by the token, d query_enc from the unmasked one split first row / other rows."""
+        x, rec = tape["x"], tape["drop"]
+        _, N, Lr = x.shape
+        V = self.to_embedding.num_embeddings
+        dropped_all = rec is not None and rec[0] >= 1.0   # (dropout_ zeroes the tensor at p >= 1: no mask to replay)
+        dt, dq = ops.embedding_bwd(x, g, V, query=(N, Lr), drop=None if dropped_all else rec)
+        if dropped_all:
+            ops.fill(dt, 0.0)
+        return {self.to_embedding.weight: dt, self.query_enc.weight: dq}
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        return (None, None), self._backward(tape, _f32_gradient(gs[0]))
 
 
-class PairEmbedding(RFModule):
+class PairEmbedding(RecordingModule):
     """rf.py:123-181.  The (d_pair+1 [+d_template]) -> d_pair Linear is split by input block: the two sequence-embedding
     blocks fold into two 21-row tables, the separation column into one vector (rf_pair_embed), and with use_template
-    the LayerNorm'ed template block (rf.py:141-143,161-169) is one rf_gemm accumulated onto that result."""
+    the LayerNorm'ed template block (rf.py:141-143,161-169) is one rf_gemm accumulated onto that result.
+    enable_backward(): with grad mode on, forward(seq, aa_idx, template) records, and loss.backward() fills the .grad of
+    embed_seq, proj and ln_template and of template where it requires grad (seq and aa_idx carry none; template may be None).
+    The backward sums the [B, L, L, d_pair] gradient over each picture axis (rf_pair_axis_sums), keys the two sums by the residue
+    type into the gradients of the two folded tables (rf_embedding_bwd) and unfolds them through the cached tables in exact fp32
+    in every compute mode.  Only the template branch follows the compute mode (16-bit operands, the fp16 mode's scale), and only
+    it needs d_pair and d_template to be multiples of 8 while recording.  RoseTTAFold._trunk calls run() without a tape and
+    never records here."""
+    _rf_n_inputs = 3   # seq, aa_idx (integers: no gradient), template (may be None)
+    _rf_scales_own_grads = True   # the template branch alone carries 16-bit gradient operands: scaled in _backward
 
     def __init__(self, d_input=21, d_pair=288, max_len=260, p_pe_drop=0.1, use_template=False, d_template=64):
         super().__init__()
@@ -527,11 +576,16 @@ class PairEmbedding(RFModule):
             # the reference fails inside nn.LayerNorm(None) (rf.py:166); same exception type, clearer text
             raise TypeError(f"[{self.__class__.__name__}]: use_template is True but no template was given")
         check_index_range(None, seq.contiguous(), aa_idx.contiguous(), self.embed_seq.num_embeddings, self.pos_enc.max_len)
+        if _recording(self):
+            return _RecordedFn.apply(self, seq, aa_idx, template, *self.parameters())
         return self.run(seq, aa_idx, template)
 
-    def run(self, seq, aa_idx, template=None):
-        """(indices already validated)"""
+    def run(self, seq, aa_idx, template=None, tape=None):
+        """(indices already validated)  tape: a dict that receives what _backward needs (the two index tensors, the fp32 template
+        and its 16-bit LayerNorm; same kernels, same numbers)."""
         h = self.half_d_pair
+        if self.use_template:
+            _check_backward_call(self, tape, None, self.proj.weight.shape[0], self.ln_template.weight.shape[0])
 
         def tables():
             e = self.embed_seq.weight.detach().float().contiguous()
@@ -541,15 +595,70 @@ class PairEmbedding(RFModule):
             return tl, tr, w[:, 2 * h].contiguous()
 
         tl, tr, wsep = self.cached("tables", tables)
-        x = ops.pair_embed(seq.contiguous(), aa_idx.contiguous(), tl, tr, wsep, _f(self.proj.bias), self.pos_enc.pos_enc)
+        seq, aa_idx = seq.contiguous(), aa_idx.contiguous()
+        x = ops.pair_embed(seq, aa_idx, tl, tr, wsep, _f(self.proj.bias), self.pos_enc.pos_enc)
+        if tape is not None:
+            tape.update(seq=seq, aa_idx=aa_idx)
         if self.use_template:
             B, Lr = seq.shape
             if tuple(template.shape[:3]) != (B, Lr, Lr) or template.shape[-1] != self.ln_template.weight.shape[0]:
                 raise ValueError(f"[{self.__class__.__name__}]: template must be [B, L, L, {self.ln_template.weight.shape[0]}]")
             wt = self.cached("wtempl", lambda: self.proj.weight.detach()[:, 2 * h + 1:].to(T()).contiguous())
-            tn = ln(self.ln_template, template.float().contiguous())
+            t32 = template.float().contiguous()
+            tn = ln(self.ln_template, t32)
             ops.linear(tn, wt, None, out=x, residual=x)  # x += LayerNorm(template) @ W_template^T (fp32, in place)
+            if tape is not None:
+                tape.update(template=t32, tn=tn)
         return x
+
+    def _record(self, seq, aa_idx, template, tape):
+        return self.run(seq, aa_idx, template, tape=tape)
+
+    def _backward(self, tape, g, want_template=True):
+        """g: contiguous fp32 [B, L, L, d_pair] gradient of the output (read only).  Returns (fp32 d template or None,
+        {param: grad}), nothing scaled.  With E = embed_seq.weight [V, h], W = proj.weight and the forward's tables tl = E W_l^T
+        (indexed by seq[j]) and tr = E W_r^T (indexed by seq[i]), W_l = W[:, :h], W_r = W[:, h:2h]:
+            rows = sum_j g, cols = sum_i g, dsep, dbias                          rf_pair_axis_sums (g read once)
+            d tl = cols keyed by seq[b, j],   d tr = rows keyed by seq[b, i]     rf_embedding_bwd on [B*L, d_pair]
+            dE = d tl W_l + d tr W_r,  dW_l = d tl^T E,  dW_r = d tr^T E         exact fp32 rf_gemm in every mode
+            dW[:, 2h] = dsep,  d bias = dbias
+        and with use_template, on s g in the compute type (s: the fp16 mode's power-of-two scale, taken off in fp32):
+            dW[:, 2h+1:] = g^T LN(template)                                      rf_conv_wgrad (the forward's 16-bit LN output)
+            d tn = g W_t,   d template, d gamma, d beta = LayerNorm backward     rf_gemm, rf_layernorm_bwd"""
+        seq, aa_idx = tape["seq"], tape["aa_idx"]
+        h, dev = self.half_d_pair, g.device
+        V = self.embed_seq.num_embeddings
+        D, K = self.proj.weight.shape
+        rows, cols, dsep, dbias = ops.pair_axis_sums(g, aa_idx)
+        dtl, _ = ops.embedding_bwd(seq, cols, V)
+        dtr, _ = ops.embedding_bwd(seq, rows, V)
+        e = self.embed_seq.weight.detach().float().contiguous()
+        w = self.proj.weight.detach().float()
+        e_t = e.t().contiguous()
+        dW = torch.empty(D, K, device=dev, dtype=F32)
+        dE = None
+        for col0, dtab in ((0, dtl), (h, dtr)):
+            dE = ops.linear(dtab, w[:, col0:col0 + h].t().contiguous(), None, out=dE, out_dtype=F32, residual=dE, exact=True)
+            ops.gemm(dtab.t().contiguous(), e_t, dW, D, h, V, c_off=col0, c_row=(0, 0, K), exact=True)
+        ops.copy(dsep, dW[:, 2 * h])
+        grads = {self.embed_seq.weight: dE, self.proj.weight: dW, self.proj.bias: dbias}
+        dtempl = None
+        if self.use_template:
+            lnm = self.ln_template
+            s = _grad_scale([g])
+            gt = g if T() == F32 else ops.axpby(g, s, None, 0.0, torch.empty(g.shape, device=dev, dtype=T()))
+            dwt, _ = ops.conv_wgrad(gt, tape["tn"], 1)
+            wt_t = self.cached("wtempl_t", lambda: self.proj.weight.detach()[:, 2 * h + 1:].t().to(T()).contiguous())
+            dtn = ops.linear(gt, wt_t, None, out_dtype=F32, exact=True)
+            dtempl, dgamma, dbeta = ops.layernorm_bwd(tape["template"], dtn, _f(lnm.weight), eps=lnm.eps)
+            _unscale([dwt, dgamma, dbeta, dtempl if want_template else None], s)
+            ops.copy(dwt, dW[:, 2 * h + 1:])
+            grads.update({lnm.weight: dgamma, lnm.bias: dbeta})
+        return dtempl if want_template else None, grads
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        dtempl, grads = self._backward(tape, _f32_gradient(gs[0]), want_template=bool(want[2]))
+        return (None, None, dtempl), grads
 
 
 # ================================================================================================

@@ -860,6 +860,53 @@ def sym_layernorm_bwd(pair, dz, w, eps=1e-5):
     return dpair
 
 
+def embedding_bwd(idx, g, n_rows, *, query=None, drop=None):
+    """Gradient of an embedding table of n_rows rows (rf_embedding_bwd): idx contiguous int64 of any shape, g contiguous fp32
+    [*idx.shape, D], the gradient of the embedded tensor.  drop = (p, seed, offset): the forward's dropout mask over that tensor,
+    replayed inside the kernel (None: no dropout).  query = (N, L): also the gradient of the two query-encoding rows from the
+    unmasked g, the rows being [.., N, L] (first MSA row / the others).  Returns (fp32 [n_rows, D], fp32 [2, D] or None)."""
+    _need_cuda(idx, g)
+    D = g.shape[-1]
+    rows = idx.numel()
+    if (idx.dtype != torch.int64 or g.dtype != F32 or tuple(g.shape[:-1]) != tuple(idx.shape)
+            or not (idx.is_contiguous() and g.is_contiguous())):
+        raise ValueError("embedding_bwd: contiguous int64 idx [...] and fp32 g [..., D]")
+    p, seed, off = drop if drop is not None else (0.0, 0, 0)
+    N, L_ = query if query is not None else (1, 1)
+    ws_bytes = int(lib.rf_embedding_bwd_ws_bytes(rows, D, int(n_rows)))
+    if ws_bytes <= 0:
+        raise ValueError(f"embedding_bwd: unsupported problem ({rows} rows, D = {D}, a table of {n_rows} rows)")
+    ws = torch.empty(ws_bytes, device=g.device, dtype=torch.uint8)
+    dtable = torch.empty(n_rows, D, device=g.device, dtype=F32)
+    dq = torch.empty(2, D, device=g.device, dtype=F32) if query is not None else None
+    check(lib.rf_embedding_bwd(ptr(idx), ptr(g), ptr(dtable), ptr(dq), rows, D, int(n_rows), int(N), int(L_), float(p), int(seed),
+                               int(off), ptr(ws), ws_bytes, stream()), "rf_embedding_bwd")
+    return dtable, dq
+
+
+def pair_axis_sums(g, aa_idx):
+    """The sums of a pair-shaped gradient over each picture axis (rf_pair_axis_sums): g contiguous fp32 [B, L, L, D], aa_idx
+    contiguous int64 [B, L].  Returns (rows [B, L, D] = sum_j g, cols [B, L, D] = sum_i g, dsep [D] = sum g log(|idx_i - idx_j| + 1),
+    dbias [D] = sum g), all fp32."""
+    _need_cuda(g, aa_idx)
+    if g.dim() != 4 or g.shape[1] != g.shape[2] or g.dtype != F32 or not g.is_contiguous():
+        raise ValueError("pair_axis_sums: contiguous fp32 g [B, L, L, D]")
+    B, L_, _, D = g.shape
+    if aa_idx.dtype != torch.int64 or tuple(aa_idx.shape) != (B, L_) or not aa_idx.is_contiguous():
+        raise ValueError(f"pair_axis_sums: contiguous int64 aa_idx [{B}, {L_}]")
+    ws_bytes = int(lib.rf_pair_axis_sums_ws_bytes(B, L_, D))
+    if ws_bytes <= 0:
+        raise ValueError(f"pair_axis_sums: unsupported shape {tuple(g.shape)}")
+    ws = torch.empty(ws_bytes, device=g.device, dtype=torch.uint8)
+    rows = torch.empty(B, L_, D, device=g.device, dtype=F32)
+    cols = torch.empty(B, L_, D, device=g.device, dtype=F32)
+    dsep = torch.empty(D, device=g.device, dtype=F32)
+    dbias = torch.empty(D, device=g.device, dtype=F32)
+    check(lib.rf_pair_axis_sums(ptr(g), ptr(aa_idx), ptr(rows), ptr(cols), ptr(dsep), ptr(dbias), B, L_, D, ptr(ws), ws_bytes,
+                                stream()), "rf_pair_axis_sums")
+    return rows, cols, dsep, dbias
+
+
 def center_channels(x, out=None):
     """y[b, i, j, c] = x[b, i, j, c] - mean_{i,j} x[b, :, :, c]  (fp32 NHWC, in place by default): rf_instnorm_stats + the
     centre-only form of rf_instnorm_apply (gamma = beta = NULL).  Exact in front of anything an InstanceNorm follows through
