@@ -22,7 +22,7 @@ if not torch.cuda.is_available():
 import attn_oracle as A  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402,F401
 from rosettafold_pytorch_amd import ops, _lib as L_  # noqa: E402
-from test_rowops_bound_gpu import h16  # noqa: E402,F401  (the fixture: both 16-bit builds)
+from grad_oracle import h16  # noqa: E402,F401  (the fixture: both 16-bit builds)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = L_.lib

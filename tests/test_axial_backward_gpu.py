@@ -2,7 +2,11 @@
 PairUpdateWithAxialAttentionLayer and PairUpdateWithAxialAttention): the three new kernels against float64 CPU, the modules'
 gradients against float64 autograd through the CPU oracle (oracle/rf_oracle.py) in the three compute modes, unchanged forward
 numbers, dropout replay (finite differences), fp16 small losses, determinism, the refusals, and the full model with the final
-axial update and the head trainable."""
+axial update and the head trainable.
+
+The modules are held by the ceiling-or-kink-floor rule of tests/grad_oracle.py: the ReLUs of the feature map and of the
+feed-forward are the kinks.  The Performer's projection_matrix is a buffer of the state dict: jittered with the rest, and given
+no gradient."""
 import functools
 
 import pytest
@@ -12,81 +16,27 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
+MODES, CEIL, UNIT = G.MODES, G.CEIL, G.UNIT
+CENTRED = lambda name: "fn.0.weight" in name   # noqa: E731  the 1-D parameters drawn around 1
+_restore_mode = G.restore_mode()
 
 
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-# Rounding unit of each mode's 16-bit / fp32 operands.  The ReLUs (feature map, feed-forward) make the exact gradient a
-# discontinuous function of the forward's values: wherever a pre-activation lies within rounding distance of 0 the forward of
-# that mode may take the other side of the kink.  The oracle comparison therefore allows, besides the mode's ceiling, three
-# times the float64 gradient's own change under a relative perturbation of its inputs and weights of one rounding unit.
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-
-
-def oracle_grads(fn, P, x, w, dtype=None, seed=0):
-    """float64 autograd of sum(fn(P, x) * w): {"x": d/dx, name: d/dP[name]}, and with `dtype` also the same after a
-    one-rounding-unit relative jitter of x and every parameter (the kink floor, see UNIT)."""
-    def run(P, x):
-        P = {k: v.detach().clone().requires_grad_(not k.endswith("projection_matrix")) for k, v in P.items()}
-        xd = x.detach().double().cpu().clone().requires_grad_()
-        (fn(P, xd) * w.double().cpu()).sum().backward()
-        out = {k: v.grad for k, v in P.items() if v.grad is not None}
-        out["x"] = xd.grad
-        return out
-    ref = run(P, x)
-    if dtype is None:
-        return ref, None
-    g = gen(seed + 1000)
-    jit = lambda t: t * (1 + UNIT[dtype] * (2 * torch.rand(t.shape, generator=g, dtype=torch.float64) - 1))  # noqa: E731
-    refj = run({k: jit(v) for k, v in P.items()}, jit(x.detach().double().cpu()))
-    return ref, {k: rel(refj[k], ref[k]) for k in ref}
-
-
-def assert_close(got, ref, floor, dtype, key):
-    tol = max(CEIL[dtype], 3 * floor[key]) if floor is not None else CEIL[dtype]
-    err = rel(got, ref[key])
-    assert err < tol, (key, err, tol)
-
-
-def state(mod, pre):
-    return {f"{pre}.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
-
-
-def randomize(mod, seed):
-    """non-trivial LayerNorm affines and biases (the defaults 1 / 0 would hide their gradients' mistakes)"""
-    g = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.1 + (1.0 if "fn.0.weight" in name else 0.0)).to(p.device))
-    return mod
+def oracle(fn, P, x, w, dtype, seed=0):
+    frozen = [k for k in P if k.endswith("projection_matrix")]
+    return G.oracle_grads(fn, P, {"x": x}, w, UNIT[dtype], seed, frozen=frozen)
 
 
 # ------------------------------------------------------------------------------------------------ kernels
 @pytest.mark.parametrize("dtype", MODES)
 def test_linattn_normalize_bwd_against_cpu(dtype):
     R.set_compute_dtype(dtype)
-    g = gen(1)
+    g = G.gen(1)
     rows, dh, ld = 300, 64, 80
     num = torch.randn(rows, ld, generator=g)
     num[:, dh] = torch.rand(rows, generator=g) * 4 + 0.5
@@ -97,20 +47,20 @@ def test_linattn_normalize_bwd_against_cpu(dtype):
     out = nd[:, :dh] / nd[:, dh:dh + 1]
     (out * gy.double()).sum().backward()
     ref = nd.grad
-    assert rel(dn[:, :dh + 1], ref[:, :dh + 1]) < {torch.float32: 1e-6, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
+    assert G.rel(dn[:, :dh + 1], ref[:, :dh + 1]) < {torch.float32: 1e-6, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
     assert torch.all(dn[:, dh + 1:].float() == 0)
 
 
 @pytest.mark.parametrize("dtype", MODES)
 def test_relu_feature_bwd_against_cpu(dtype):
     R.set_compute_dtype(dtype)
-    g = gen(2)
+    g = G.gen(2)
     rows, ld, m = 257, 288, 266
     dphi, z = torch.randn(rows, ld, generator=g), torch.randn(rows, ld, generator=g)
     dz = ops.relu_feature_bwd(dphi.to(DEV), z.to(DEV), m, dtype)
     ref = torch.where(z > 0, dphi, torch.zeros(()))
     ref[:, m:] = 0
-    assert rel(dz, ref) < {torch.float32: 1e-7, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
+    assert G.rel(dz, ref) < {torch.float32: 1e-7, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
     assert torch.all(dz[:, m:].float() == 0)
 
 
@@ -118,7 +68,7 @@ def test_relu_feature_bwd_against_cpu(dtype):
 @pytest.mark.parametrize("p", [0.0, 0.25])
 def test_relu_dropout_bwd_against_cpu(dtype, p):
     R.set_compute_dtype(dtype)
-    g = gen(3)
+    g = G.gen(3)
     n = 4099
     gh, h = torch.randn(n, generator=g), torch.randn(n, generator=g)
     seed, off = 1234, 77
@@ -126,7 +76,7 @@ def test_relu_dropout_bwd_against_cpu(dtype, p):
     dh = ops.relu_dropout_bwd(gh.to(DEV), h.to(DEV), dtype, drop)
     mask = ops.dropout(torch.ones(n, device=DEV), p, seed, off).cpu().double() if p > 0 else torch.ones(n, dtype=torch.float64)
     ref = gh.double() * (h > 0).double() * mask
-    assert rel(dh, ref) < {torch.float32: 1e-7, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
+    assert G.rel(dh, ref) < {torch.float32: 1e-7, torch.float16: 1e-3, torch.bfloat16: 8e-3}[dtype]
     if p > 0:
         assert 0 < (mask == 0).sum() < n
 
@@ -139,7 +89,7 @@ def _perf_oracle_grads(mod, xn, w, axis, H, dtype):
             return O.performer_self_attention(P, "a", xd.reshape(B * L1, L2, D), H, True).view(B, L1, L2, D)
         xs = xd.permute(0, 2, 1, 3).reshape(B * L2, L1, D)
         return O.performer_self_attention(P, "a", xs, H, True).view(B, L2, L1, D).permute(0, 2, 1, 3)
-    return oracle_grads(fn, state(mod, "a"), xn, w, dtype)
+    return oracle(fn, G.state(mod, "a"), xn, w, dtype)
 
 
 @pytest.mark.parametrize("dtype", MODES)
@@ -150,8 +100,8 @@ def test_performer_grads_against_oracle(dtype, axis, Ls):
     torch.manual_seed(Ls + axis)
     D, H, B, Lo = 32, 2, 1, 3
     mod = R.PerformerSelfAttention(D, heads=H, generalized_attention=True).to(DEV)
-    randomize(mod, 5)
-    g = gen(Ls * 10 + axis)
+    G.randomize(mod, 5, CENTRED)
+    g = G.gen(Ls * 10 + axis)
     shape = (B, Ls, Lo, D) if axis == 1 else (B, Lo, Ls, D)
     xn = (torch.randn(shape, generator=g)).to(dtype).to(DEV)
     w = torch.randn(shape, generator=g)
@@ -160,9 +110,8 @@ def test_performer_grads_against_oracle(dtype, axis, Ls):
     mod.attend(xn, out, axis, tape=tape)
     dxn, grads = mod._backward(tape, w.to(DEV).clone())
     ref, floor = _perf_oracle_grads(mod, xn, w, axis, H, dtype)
-    assert_close(dxn, ref, floor, dtype, "x")
-    for name, p in mod.named_parameters():
-        assert_close(grads[p], ref, floor, dtype, "a." + name)
+    got = dict({"a." + name: grads[p] for name, p in mod.named_parameters()}, x=dxn)
+    G.compare(got, ref, dtype, f"Performer axis {axis} L={Ls}", floor)
     assert "fast_attention.projection_matrix" not in dict(mod.named_parameters())
 
 
@@ -173,16 +122,13 @@ def test_performer_module_forward_autograd(dtype):
     torch.manual_seed(9)
     D, H = 32, 2
     mod = R.PerformerSelfAttention(D, heads=H, generalized_attention=True).to(DEV).enable_backward()
-    randomize(mod, 6)
-    g = gen(9)
+    G.randomize(mod, 6, CENTRED)
+    g = G.gen(9)
     x = torch.randn(3, 96, D, generator=g).to(dtype).float()
     w = torch.randn(3, 96, D, generator=g)
-    xg = x.to(DEV).requires_grad_()
-    (mod(xg) * w.to(DEV)).sum().backward()
+    got, _ = G.grads_of(mod, {"x": x}, w, pre="a")
     ref, floor = _perf_oracle_grads(mod, x.view(1, 3, 96, D), w.view(1, 3, 96, D), 2, H, dtype)
-    assert_close(xg.grad.view(1, 3, 96, D), ref, floor, dtype, "x")
-    for name, p in mod.named_parameters():
-        assert_close(p.grad, ref, floor, dtype, "a." + name)
+    G.compare(dict(got, x=got["x"].view(1, 3, 96, D)), ref, dtype, "Performer forward()", floor)
 
 
 # ------------------------------------------------------------------------------------------------ feed-forward
@@ -192,18 +138,15 @@ def test_feed_forward_grads_against_oracle(dtype, D, hidden, L):
     R.set_compute_dtype(dtype)
     torch.manual_seed(D)
     ff = R.FeedForward(D, hidden).to(DEV).enable_backward()
-    randomize(ff, 7)
-    g = gen(D + L)
+    G.randomize(ff, 7, CENTRED)
+    g = G.gen(D + L)
     x = torch.randn(1, L, L, D, generator=g).to(dtype).float()
     w = torch.randn(1, L, L, D, generator=g)
     if D == 288 and dtype != torch.float32:
         assert ops.ffn_fused_applies(x.to(dtype).to(DEV), x.to(DEV), D, hidden)   # the fused forward is what recorded
-    xg = x.to(DEV).requires_grad_()
-    (ff(xg) * w.to(DEV)).sum().backward()
-    ref, floor = oracle_grads(lambda P, xd: O.feed_forward(P, "ff", xd), state(ff, "ff"), x, w, dtype)
-    assert_close(xg.grad, ref, floor, dtype, "x")
-    for name, p in ff.named_parameters():
-        assert_close(p.grad, ref, floor, dtype, "ff." + name)
+    got, _ = G.grads_of(ff, {"x": x}, w, pre="ff")
+    ref, floor = oracle(lambda P, xd: O.feed_forward(P, "ff", xd), G.state(ff, "ff"), x, w, dtype)
+    G.compare(got, ref, dtype, f"FeedForward {D}x{hidden} L={L}", floor)
 
 
 # ------------------------------------------------------------------------------------------------ layer and stack
@@ -215,8 +158,8 @@ def _stack_module(D, H, n_layers, L, seed):
         mod = R.PairUpdateWithAxialAttentionLayer(D, 4 * D, H, 0.1, {})
     else:
         mod = R.PairUpdateWithAxialAttention(D, 4 * D, H, 0.1, n_layers)
-    randomize(mod, seed)
-    g = gen(seed)
+    G.randomize(mod, seed, CENTRED)
+    g = G.gen(seed)
     return mod, torch.randn(1, L, L, D, generator=g), torch.randn(1, L, L, D, generator=g)
 
 
@@ -227,19 +170,13 @@ def _check_stack(dtype, D, H, n_layers, L, seed):
         fn = lambda P, xd: O.pair_axial_layer(P, "m", xd, H)   # noqa: E731
     else:
         fn = lambda P, xd: O.pair_update_with_axial_attention(P, "m", xd, n_layers)   # noqa: E731
-    ref, floor = oracle_grads(fn, state(mod, "m"), x, w, dtype, seed)
+    ref, floor = oracle(fn, G.state(mod), x, w, dtype, seed)
     mod = mod.to(DEV)
     mod.enable_backward()
     try:
-        for p in mod.parameters():
-            p.grad = None
-        xg = x.to(DEV).requires_grad_()
-        (mod(xg) * w.to(DEV)).sum().backward()
-        assert_close(xg.grad, ref, floor, dtype, "x")
-        assert {"m." + n for n, _ in mod.named_parameters()} | {"x"} == set(ref)
-        for name, p in mod.named_parameters():
-            assert p.grad is not None
-            assert_close(p.grad, ref, floor, dtype, "m." + name)
+        got, _ = G.grads_of(mod, {"x": x}, w)
+        assert set(got) == set(ref) and all(t is not None for t in got.values())
+        G.compare(got, ref, dtype, f"axial D={D} layers={n_layers} L={L}", floor)
     finally:
         mod.enable_backward(False)
 
@@ -267,7 +204,7 @@ def test_recording_forward_is_bitwise_unchanged(dtype):
     R.set_compute_dtype(dtype)
     torch.manual_seed(21)
     mod = R.PairUpdateWithAxialAttention(288, 1152, 8, 0.1, 2).to(DEV)
-    x = torch.randn(1, 128, 128, 288, generator=gen(21)).to(DEV)
+    x = torch.randn(1, 128, 128, 288, generator=G.gen(21)).to(DEV)
     with torch.no_grad():
         ref = mod(x)
     mod.enable_backward()
@@ -285,9 +222,9 @@ def test_dropout_replay_finite_differences():
     torch.manual_seed(31)
     D, H, L = 32, 2, 16
     mod = R.PairUpdateWithAxialAttentionLayer(D, 2 * D, H, 0.2, {}).to(DEV)
-    randomize(mod, 31)
+    G.randomize(mod, 31, CENTRED)
     mod.train().enable_backward()
-    g = gen(31)
+    g = G.gen(31)
     x = torch.randn(1, L, L, D, generator=g).to(DEV)
     w = torch.randn(1, L, L, D, generator=g).to(DEV)
     v = torch.randn(1, L, L, D, generator=g).to(DEV)
@@ -330,7 +267,7 @@ def test_feed_forward_output_drops_replayed():
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(32)
     ff = R.FeedForward(32, 64, 0.3).to(DEV).train()
-    g = gen(32)
+    g = G.gen(32)
     x = torch.randn(1, 8, 8, 32, generator=g).to(DEV)
     w = torch.randn(1, 8, 8, 32, generator=g).to(DEV)
     R.manual_seed(3)
@@ -356,20 +293,14 @@ def test_fp16_small_loss_does_not_underflow():
     R.set_compute_dtype(torch.float16)
     torch.manual_seed(41)
     mod = R.PairUpdateWithAxialAttention(64, 256, 2, 0.1, 2).to(DEV).enable_backward()
-    randomize(mod, 41)
-    g = gen(41)
+    G.randomize(mod, 41, CENTRED)
+    g = G.gen(41)
     x = torch.randn(1, 24, 24, 64, generator=g).to(DEV)
     w = torch.randn(1, 24, 24, 64, generator=g).to(DEV)
-    res = []
-    for scale in (1.0, 1e-6):
-        for p in mod.parameters():
-            p.grad = None
-        xg = x.clone().requires_grad_()
-        ((mod(xg) * w).sum() * scale).backward()
-        res.append([xg.grad] + [p.grad for p in mod.parameters()])
+    res = [list(G.grads_of(mod, {"x": x}, w, scale)[0].values()) for scale in (1.0, 1e-6)]
     for a, b in zip(res[0], res[1]):
         assert torch.isfinite(b).all() and b.abs().max() > 0
-        assert rel(b * 1e6, a) < CEIL[torch.float16]
+        assert G.rel(b * 1e6, a) < CEIL[torch.float16]
 
 
 # ------------------------------------------------------------------------------------------------ determinism
@@ -377,16 +308,10 @@ def test_backward_is_deterministic():
     R.set_compute_dtype(torch.bfloat16)
     torch.manual_seed(51)
     mod = R.PairUpdateWithAxialAttention(288, 1152, 8, 0.1, 1).to(DEV).enable_backward()
-    g = gen(51)
+    g = G.gen(51)
     x = torch.randn(1, 128, 128, 288, generator=g).to(DEV)
     w = torch.randn(1, 128, 128, 288, generator=g).to(DEV)
-    res = []
-    for _ in range(2):
-        for p in mod.parameters():
-            p.grad = None
-        xg = x.clone().requires_grad_()
-        (mod(xg) * w).sum().backward()
-        res.append([xg.grad.clone()] + [p.grad.clone() for p in mod.parameters()])
+    res = [[t.clone() for t in G.grads_of(mod, {"x": x}, w)[0].values()] for _ in range(2)]
     assert all(torch.equal(a, b) for a, b in zip(*res))
 
 
@@ -409,7 +334,7 @@ CFG = dict(d_input=21, d_msa=96, d_pair=72, d_node=8, d_edge=8, d_state=8, n_two
 
 
 def _inputs(L=16):
-    g = gen(61)
+    g = G.gen(61)
     msa = torch.randint(0, 21, (1, 6, L), generator=g)
     return msa.to(DEV), msa[:, 0].clone().to(DEV), torch.arange(L).unsqueeze(0).to(DEV)
 
@@ -440,7 +365,7 @@ def test_full_model_final_axial_and_head_train():
     for k in ref_logits:
         assert torch.equal(logits[k].detach(), ref_logits[k]), k
     assert torch.equal(xyz, ref_xyz) and torch.equal(plddt, ref_plddt)
-    target = {k: torch.randint(0, v.shape[-1], v.shape[:-1], generator=gen(64)).to(DEV) for k, v in ref_logits.items()}
+    target = {k: torch.randint(0, v.shape[-1], v.shape[:-1], generator=G.gen(64)).to(DEV) for k, v in ref_logits.items()}
 
     def loss_of(lg):
         return sum(torch.nn.functional.cross_entropy(lg[k].reshape(-1, lg[k].shape[-1]), target[k].reshape(-1)) for k in lg)

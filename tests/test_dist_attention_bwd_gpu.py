@@ -1,10 +1,7 @@
 """rf_dist_masked_attention_bwd (csrc/backward.hip): the backward of MsaUpdateWithPairAndCoord's distance-masked attention map.
 
-The kernel is held against float64 autograd of a restatement of the forward on the operands, by the rule of
-tests/test_poswise_bwd_gpu.py: the ceiling of each output is MARGIN = 4 times a yardstick measured at run time, the larger of
-(a) the error of torch's own float32 autograd of the same restatement on the same operands against the float64 result and
-(b) 2^-24, the rounding unit of the fp32 outputs.  Relative L2 error of the whole tensor and of the worst row -- one (b, i) for
-dq, one (b, j) for dk.  A row whose float64 gradient is exactly zero must be exactly zero.
+The kernel is held against float64 autograd of a restatement of the forward on the operands, by the yardstick rule of
+tests/grad_oracle.py, with 2^-24, the rounding unit of the fp32 outputs.  A row is one (b, i) of dq, one (b, j) of dk.
 
 Coordinates are a random walk of 3.8 A steps for CA plus unit noise for the other two atoms.  Before any launch each case
 asserts on the CPU that every pairwise CA distance is at least 1e-4 A away from every bin (the fp32 distance error at these
@@ -13,8 +10,6 @@ unmasked entries off the diagonal.
 
 RF_MSA_COORD_BACKWARD_ERRORS=FILE: the measured errors are also merged into that JSON file (key "kernel_errors")."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -23,6 +18,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 
@@ -34,31 +30,12 @@ BINS4 = (8.0, 12.0, 16.0, 20.0)
 SHAPES = {(2, 1, 4, 32): BINS4, (1, 5, 4, 32): BINS4, (2, 24, 4, 32): BINS4, (1, 63, 1, 8): (12.0,),
           (1, 65, 5, 24): (6.0, 8.0, 12.0, 16.0, 20.0), (1, 100, 4, 32): BINS4, (1, 257, 4, 32): BINS4}
 SEED = {**{s: 0 for s in SHAPES}, (2, 24, 4, 32): 5}   # (seed 5: the 20 A head has entries out of range in both samples)
-UNIT = 2.0 ** -24
-MARGIN = 4.0
 GAP = 1e-4
 NAMES = ("dq", "dk")
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_MSA_COORD_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, 2^-24)", "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+HELD = dict(units=G.UNIT[torch.float32], rows=1, records=RECORDS)
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_MSA_COORD_BACKWARD_ERRORS", RECORDS, "max(torch float32 autograd vs float64, 2^-24)")
 
 
 @pytest.fixture(params=[torch.bfloat16, torch.float16], ids=["bf16-build", "f16-build"])
@@ -134,34 +111,6 @@ def run_bwd(c, **over):
     return {"dq": dq, "dk": dk, "ds": ds}
 
 
-def errors(got, want):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one row [b, l, :]).  A row that is exactly zero in
-    `want` must be exactly zero in `got` (infinite error otherwise)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    gr, wr = g.reshape(g.shape[0] * g.shape[1], -1), w.reshape(g.shape[0] * g.shape[1], -1)
-    num, den = (gr - wr).norm(dim=-1), wr.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    if w.norm() > 0:
-        return ((g - w).norm() / w.norm()).item(), rows.max().item()
-    return (float("inf") if (g != 0).any() else 0.0), rows.max().item()
-
-
-def held(got, ref64, ref32, tag):
-    """both gradients under MARGIN x their yardstick, whole tensor and worst row; prints and records the figures"""
-    ok = True
-    for n in NAMES:
-        m_all, m_row = errors(got[n], ref64[n])
-        y_all, y_row = errors(ref32[n], ref64[n])
-        c_all, c_row = MARGIN * max(y_all, UNIT), MARGIN * max(y_row, UNIT)
-        print(f"{tag} {n}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, ceiling {c_all:.3e}), "
-              f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-        RECORDS.append(dict(case=tag, grad=n, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                            unit=UNIT, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-        ok = ok and m_all <= c_all and m_row <= c_row
-    return ok
-
-
 # ---- 1. the kernel against float64 autograd ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", list(SHAPES), ids=[str(s) for s in SHAPES])
 def test_kernel_against_float64_autograd(shape, build):
@@ -172,14 +121,14 @@ def test_kernel_against_float64_autograd(shape, build):
     for n in NAMES:
         assert got[n].dtype == torch.float32 and tuple(got[n].shape) == (B, L, H * d)
     tag = f"{'bf16' if build == torch.bfloat16 else 'f16'}-build {shape}"
-    assert held(got, ref64, ref32, tag)
+    assert G.held(got, ref64, ref32, tag, **HELD)
     # a masked entry has p = 0, and so ds = 0, exactly; the float64 mask is the kernel's
     assert (got["ds"].cpu()[~c["mask"]] == 0).all()
     if L == 1:
         assert (got["dq"] == 0).all() and (got["dk"] == 0).all() and (got["ds"] == 0).all()
     if L >= 5:   # the check has teeth: the gradient of the transposed map must fail it
         wrong = run_bwd(c, datt=c["datt"].transpose(-1, -2).contiguous())
-        assert not held(wrong, ref64, ref32, f"{tag} (transposed gradient: must fail)")
+        assert not G.held(wrong, ref64, ref32, f"{tag} (transposed gradient: must fail)", **HELD)
         del RECORDS[-len(NAMES):]
 
 
@@ -198,7 +147,7 @@ def test_a_residue_out_of_range_gets_exact_zeros():
     got = run_bwd(c)
     assert (got["dq"][:, r] == 0).all() and (got["dk"][:, r] == 0).all()
     assert (got["dq"][:, r + 1] != 0).any() and (got["dk"][:, r + 1] != 0).any()
-    assert held(got, autograd(c, torch.float64), autograd(c, torch.float32), f"{shape} residue {r} moved 1000 A")
+    assert G.held(got, autograd(c, torch.float64), autograd(c, torch.float32), f"{shape} residue {r} moved 1000 A", **HELD)
     del RECORDS[-len(NAMES):]
 
 

@@ -2,16 +2,12 @@
 adds, in both builds.
 
 Each output is held against float64 autograd of a torch restatement (a gather, i.e. index_add backwards, and broadcast sums) on
-the same operands, by the rule of tests/test_pair_softmax_bwd_gpu.py: the ceiling of an output is MARGIN = 4 times a yardstick
-measured at run time, the larger of (a) the error of torch's own float32 autograd of the same restatement on the same operands
-against the float64 result and (b) 2^-24, the rounding unit of the fp32 outputs.  Relative L2 error of the whole tensor and of the
-worst row (the last dimension: one table row, one (b, i) channel row).  A row whose float64 gradient is exactly zero must be
-exactly zero.  Every run goes through sentinel-filled outputs with a tail, and two runs must give the same bits.
+the same operands, by the yardstick rule of tests/grad_oracle.py, with 2^-24, the rounding unit of the fp32 outputs.  A row is the
+last dimension: one table row, one (b, i) channel row.  Every run goes through sentinel-filled outputs with a tail, and two
+runs must give the same bits.
 
 RF_EMBEDDING_BACKWARD_ERRORS=FILE: the measured errors are also merged into that JSON file (key "kernel_errors")."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -20,6 +16,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 
@@ -37,30 +34,11 @@ DROP = (0.3, 1234, 77)   # (p, seed, offset)
 # two column tiles and five row tiles; 257: five column tiles, seventeen row tiles, the last of one row / one column.
 PAIR_SHAPES = [(2, 1, 16), (1, 2, 8), (2, 13, 40), (1, 65, 288), (1, 257, 72)]
 BUILDS = [("bf16-build", torch.bfloat16), ("f16-build", torch.float16)]
-UNIT = 2.0 ** -24
-MARGIN = 4.0
 SENTINEL = 7.0
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_EMBEDDING_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, 2^-24)", "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+HELD = dict(units=G.UNIT[torch.float32], rows=1, records=RECORDS, key="out")
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_EMBEDDING_BACKWARD_ERRORS", RECORDS, "max(torch float32 autograd vs float64, 2^-24)")
 
 
 @pytest.fixture(params=BUILDS, ids=[b[0] for b in BUILDS])
@@ -70,41 +48,13 @@ def build(request):
     return request.param[0]
 
 
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def errors(got, want):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one row: the last dimension).  A row that is exactly
-    zero in `want` must be exactly zero in `got` (infinite error otherwise)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    num, den = (g - w).norm(dim=-1), w.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    if w.norm() > 0:
-        return ((g - w).norm() / w.norm()).item(), rows.max().item()
-    return (float("inf") if (g != 0).any() else 0.0), rows.max().item()
-
-
-def held(got, ref64, ref32, tag, out):
-    """the output under MARGIN x its yardstick, whole tensor and worst row; prints and records the figures"""
-    m_all, m_row = errors(got, ref64)
-    y_all, y_row = errors(ref32, ref64)
-    c_all, c_row = MARGIN * max(y_all, UNIT), MARGIN * max(y_row, UNIT)
-    print(f"{tag} {out}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, ceiling {c_all:.3e}), "
-          f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-    RECORDS.append(dict(case=tag, out=out, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                        unit=UNIT, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-    return m_all <= c_all and m_row <= c_row
-
-
 # ================================================================================================ rf_embedding_bwd
 @functools.lru_cache(maxsize=None)
 def emb_case(shape):
     """One set of operands per shape, shared and left unchanged: the tokens [B,N,L], the gradient [B,N,L,D] and the dropout
     factors keep / (1 - p) of DROP, read off ops.dropout of a tensor of ones with the same record."""
     B, N, L, D, V = shape
-    g_ = gen(7100 + 13 * L + D + V)
+    g_ = G.gen(7100 + 13 * L + D + V)
     idx = torch.randint(0, V, (B, N, L), generator=g_)
     if shape in WITHHELD:
         t = WITHHELD[shape]
@@ -165,8 +115,8 @@ def test_embedding_bwd_against_float64_autograd(shape, build):
     (t64, q64), (t32, q32) = emb_refs(shape, False)
     dt, dq = run_embedding_bwd(c, V)
     tag = f"{build} embedding_bwd {shape}"
-    assert held(dt, t64, t32, tag, "dtable")
-    assert held(dq, q64, q32, tag, "dq")
+    ref64, ref32 = {"dtable": t64, "dq": q64}, {"dtable": t32, "dq": q32}
+    assert G.held({"dtable": dt, "dq": dq}, ref64, ref32, tag, **HELD)
     used = torch.zeros(V, dtype=torch.bool)
     used[c["idx"].cpu().view(-1)] = True
     assert (dt[~used.to(DEV)] == 0).all()               # a table row whose index never occurs: exact zeros
@@ -184,7 +134,7 @@ def test_embedding_bwd_against_float64_autograd(shape, build):
     assert torch.equal(w_dt, dt) and torch.equal(w_dq, dq)
     if B * N * L > 1:   # the check has teeth: the tokens shifted by one row must fail it
         wrong, _ = run_embedding_bwd(dict(c, idx=c["idx"].view(-1).roll(1).view(B, N, L).contiguous()), V)
-        assert not held(wrong, t64, t32, "(tokens rolled by one: must fail)", "dtable")
+        assert not G.held({"dtable": wrong}, {"dtable": t64}, {"dtable": t32}, "(tokens rolled by one: must fail)", **HELD)
         del RECORDS[-1]
 
 
@@ -196,11 +146,10 @@ def test_embedding_bwd_replays_the_dropout_mask(shape, build):
     (t64, q64), (t32, q32) = emb_refs(shape, True)
     dt, dq = run_embedding_bwd(c, V, drop=DROP)
     tag = f"{build} embedding_bwd {shape} p={DROP[0]}"
-    assert held(dt, t64, t32, tag, "dtable")
-    assert held(dq, q64, q32, tag, "dq")
+    assert G.held({"dtable": dt, "dq": dq}, {"dtable": t64, "dq": q64}, {"dtable": t32, "dq": q32}, tag, **HELD)
     plain, plain_q = run_embedding_bwd(c, V)
     assert torch.equal(dq, plain_q)                     # query_enc is added behind the dropout
-    assert not held(plain, t64, t32, "(no mask: must fail)", "dtable")
+    assert not G.held({"dtable": plain}, {"dtable": t64}, {"dtable": t32}, "(no mask: must fail)", **HELD)
     del RECORDS[-1]
     again, _ = run_embedding_bwd(c, V, drop=DROP)
     assert torch.equal(again, dt)
@@ -213,13 +162,13 @@ def test_embedding_bwd_replays_the_dropout_mask(shape, build):
 def test_embedding_bwd_serves_the_pair_side(build):
     """rows = B * L, idx = seq, N = 1: the call PairEmbedding's backward makes"""
     B, L, D, V = 2, 13, 40, 21
-    g_ = gen(7900)
+    g_ = G.gen(7900)
     seq, g = torch.randint(0, V, (B, L), generator=g_).to(DEV), torch.randn(B, L, D, generator=g_).to(DEV)
     want = torch.zeros(V, D, dtype=torch.float64).index_add_(0, seq.cpu().view(-1), g.cpu().double().view(-1, D))
     want32 = torch.zeros(V, D).index_add_(0, seq.cpu().view(-1), g.cpu().view(-1, D))
     dt, none = ops.embedding_bwd(seq, g, V)
     assert none is None
-    assert held(dt, want, want32, f"{build} embedding_bwd pair side {(B, L, D, V)}", "dtable")
+    assert G.held({"dtable": dt}, {"dtable": want}, {"dtable": want32}, f"{build} embedding_bwd pair side {(B, L, D, V)}", **HELD)
 
 
 def test_embedding_bwd_refuses_before_a_launch(build):
@@ -261,7 +210,7 @@ def pair_case(shape):
     """the gradient [B,L,L,D], and residue numbers that increase strictly with random gaps of 1..40 (so that the separation is
     not log(|i - j| + 1)); sep: the forward's feature in fp32"""
     B, L, D = shape
-    g_ = gen(8100 + 11 * L + D)
+    g_ = G.gen(8100 + 11 * L + D)
     g = torch.randn(B, L, L, D, generator=g_)
     aa_idx = torch.randint(1, 41, (B, L), generator=g_).cumsum(-1)
     sep = torch.log(((aa_idx[:, :, None] - aa_idx[:, None, :]).abs() + 1).float())
@@ -309,15 +258,15 @@ def test_pair_axis_sums_against_float64_autograd(shape, build):
     ref64, ref32 = pair_refs(shape)
     got = run_pair_axis_sums(c)
     tag = f"{build} pair_axis_sums {shape}"
-    ok = [held(o, r64, r32, tag, name) for o, r64, r32, name in zip(got, ref64, ref32, ("rows", "cols", "dsep", "dbias"))]
-    assert all(ok), ok
+    names = ("rows", "cols", "dsep", "dbias")
+    assert G.held(dict(zip(names, got)), dict(zip(names, ref64)), dict(zip(names, ref32)), tag, **HELD)
     if L == 1:
         assert (got[2] == 0).all()                        # log(1) = 0: dsep exactly zero
         assert torch.equal(got[0], c["g"].view(B, L, D)) and torch.equal(got[1], c["g"].view(B, L, D))
     assert all(torch.equal(a, b) for a, b in zip(run_pair_axis_sums(c), got))       # the same bits on a second run
     assert all(torch.equal(a, b) for a, b in zip(ops.pair_axis_sums(c["g"], c["aa_idx"]), got))   # the wrapper: the same bits
     if L > 1:   # the check has teeth: the two axes swapped must fail it
-        assert not held(got[1], ref64[0], ref32[0], "(cols for rows: must fail)", "rows")
+        assert not G.held({"rows": got[1]}, {"rows": ref64[0]}, {"rows": ref32[0]}, "(cols for rows: must fail)", **HELD)
         del RECORDS[-1]
 
 

@@ -2,21 +2,19 @@
 (csrc/backward.hip: rf_graph_attention_bwd, rf_elu_bwd).
 
 Kernel accuracy is held against float64 autograd of a restatement of the forward (the one of tests/test_edge_mask_gpu.py, made
-differentiable) on the operands as rounded.  The ceiling of dq, dk, dv, de is not fixed in advance: it is MARGIN = 4 times a
-yardstick measured at run time, the larger of (a) the error of torch's own float32 autograd of the same restatement on the same
-operands against the float64 result and (b) the rounding unit of the output's storage type (2^-24 for the fp32 dq, dk, dv; the
-operand type's unit for de).  Relative L2 error of the whole tensor and of the worst (b, i) row; the margin is 4 because a row of
-one or two edges averages no rounding error away.  A row whose float64 gradient is exactly zero (dq of a node with no or one
-edge) must be exactly zero.
+differentiable) on the operands as rounded, by the yardstick rule of tests/grad_oracle.py.  The units are 2^-24 for the fp32 dq,
+dk, dv and the operand type's unit for de.  A row is one (b, i); the margin is 4 because a row of one or two edges averages no
+rounding error away.  A row whose float64 gradient is exactly zero (dq of a node with no or one edge) must be exactly zero.
 
-The modules are held to the project's standing ceilings per gradient (relative L2 1e-4 / 1e-2 / 5e-2 in fp32 / fp16 / bf16), or
-three times the float64 gradient's own change under a one-rounding-unit jitter of inputs and weights where that is larger.
+The modules are held by the ceiling-or-kink-floor rule of the same file.  b_k moves every logit of a row by the same q_i . b_k,
+which a softmax ignores (sum_j ds_ij = 0, under a mask and under dropout too): the exact gradient of node_to_k.bias is 0 and the
+float64 reference holds only its own rounding noise, so a relative error has no denominator.  The gradient is sum_j dk_j, the sum
+of the rows whose outer products with node_j make up node_to_k.weight's gradient: its error is taken against that gradient's norm
+per input channel, under the same ceiling.
 
 RF_GRAPH_BACKWARD_ERRORS=FILE: the measured kernel errors are also merged into that JSON file (key "kernel_errors")."""
 import copy
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -25,6 +23,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 from rosettafold_pytorch_amd.runtime import RT  # noqa: E402
@@ -37,50 +36,23 @@ OPERANDS = [("fp32", torch.bfloat16, torch.float32), ("bf16", torch.bfloat16, to
             ("fp16", torch.float16, torch.float16)]
 OP_DTYPE = {o[0]: o[2] for o in OPERANDS}
 MASKS = ["none", "ones", "mixed"]
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-MARGIN = 4.0
+UNIT, CEIL, MODES = G.UNIT, G.CEIL, G.MODES
 TINY = {torch.float16: 2.0 ** -25}   # half the spacing of fp16 below 2^-14: the rounding of a stored value that small
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
 NAMES = ("dq", "dk", "dv", "de")
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_GRAPH_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, unit of the storage type)",
-                                "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+# de's storage type -> the units of the four gradients; a row is one (b, i): the last dimension of dq, dk, dv, the last two of de
+UNITS = {dt: dict(dict.fromkeys(NAMES, G.UNIT[torch.float32]), de=G.UNIT[dt]) for dt in G.UNIT}
+HELD = dict(rows={"dq": 1, "dk": 1, "dv": 1, "de": 2}, records=RECORDS)
+CENTRED = lambda name: name.endswith("ln.weight")   # noqa: E731  the 1-D parameters drawn around 1
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_GRAPH_BACKWARD_ERRORS", RECORDS,
+                                   "max(torch float32 autograd vs float64, unit of the storage type)")
 
 
 @pytest.fixture(params=OPERANDS, ids=[o[0] for o in OPERANDS])
 def operand(request):
     R.set_compute_dtype(request.param[1])
     return request.param
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
 
 
 # ---- the forward, restated (any floating type, any device; differentiable) ---------------------------------------------------
@@ -109,21 +81,10 @@ def autograd(q, k, v, e, g, mask, H, scale, dtype, keep=None, p=0.0, device="cpu
     return {n: t.grad.detach().cpu() for n, t in zip(NAMES, leaves)}
 
 
-def errors(got, want):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one (b, i) row).  A row that is exactly zero in
-    `want` must be exactly zero in `got` (infinite error otherwise)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    gr, wr = g.reshape(g.shape[0] * g.shape[1], -1), w.reshape(g.shape[0] * g.shape[1], -1)
-    num, den = (gr - wr).norm(dim=-1), wr.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    return ((g - w).norm() / w.norm().clamp_min(1e-300)).item(), rows.max().item()
-
-
 def mixed_mask(B, L, seed):
     """uint8 [B, L, L]: rows of degree 0, 1, 2, 63, 64, 65 and L (those that fit) in turn, random columns: asymmetric, and
     another assignment for every batch item."""
-    g = gen(seed)
+    g = G.gen(seed)
     degs = sorted({x for x in (0, 1, 2, 63, 64, 65, L) if x <= L})
     m = torch.zeros(B, L, L, dtype=torch.uint8)
     for b in range(B):
@@ -137,7 +98,7 @@ def case(shape, op_id):
     """One set of operands per (shape, operand type), shared by the tests below and left unchanged."""
     B, L, H, d = shape
     dt = OP_DTYPE[op_id]
-    g_ = gen(2000 + L)
+    g_ = G.gen(2000 + L)
     q, k, v = (torch.randn(B, L, H * d, generator=g_).to(dt).to(DEV) for _ in range(3))
     e = torch.randn(B, L, L, H * d, generator=g_).to(dt).to(DEV)
     g = torch.randn(B, L, H * d, generator=g_).to(DEV)
@@ -176,22 +137,6 @@ def run_bwd(c, mask, H, dropout=None, **over):
     return dict(zip(NAMES + ("pd", "ds"), out))
 
 
-def held(got, ref64, ref32, op_dtype, tag):
-    """every gradient under MARGIN x its yardstick, whole tensor and worst row; prints and records the figures"""
-    ok = True
-    for n in NAMES:
-        unit = UNIT[op_dtype if n == "de" else torch.float32]
-        m_all, m_row = errors(got[n], ref64[n])
-        y_all, y_row = errors(ref32[n], ref64[n])
-        c_all, c_row = MARGIN * max(y_all, unit), MARGIN * max(y_row, unit)
-        print(f"{tag} {n}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, unit {unit:.1e}, ceiling {c_all:.3e}), "
-              f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-        RECORDS.append(dict(case=tag, grad=n, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                            unit=unit, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-        ok = ok and m_all <= c_all and m_row <= c_row
-    return ok
-
-
 # ---- 1. the kernel against float64 autograd ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mask_kind", MASKS)
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
@@ -200,10 +145,10 @@ def test_kernel_against_float64_autograd(shape, operand, mask_kind):
     ref64, ref32 = refs(shape, operand[0], mask_kind)
     got = run_bwd(c, c[mask_kind], shape[2])
     assert got["dq"].dtype == got["dk"].dtype == got["dv"].dtype == torch.float32 and got["de"].dtype == operand[2]
-    assert held(got, ref64, ref32, operand[2], f"{operand[0]} {shape} mask={mask_kind}")
+    assert G.held(got, ref64, ref32, f"{operand[0]} {shape} mask={mask_kind}", UNITS[operand[2]], **HELD)
     if mask_kind == "mixed":   # the check has teeth: the mask's axes swapped must fail it
         swapped = run_bwd(c, c["mixed"].transpose(1, 2).contiguous(), shape[2])
-        assert not held(swapped, ref64, ref32, operand[2], f"{operand[0]} {shape} (swapped axes: must fail)")
+        assert not G.held(swapped, ref64, ref32, f"{operand[0]} {shape} (swapped axes: must fail)", UNITS[operand[2]], **HELD)
         del RECORDS[-len(NAMES):]
 
 
@@ -211,7 +156,7 @@ def test_kernel_at_L_1024_H_4():
     """the longest row the issue names, in the 16-bit type: float64 and float32 autograd on the device"""
     R.set_compute_dtype(torch.bfloat16)
     B, L, H, d = 1, 1024, 4, 8
-    g_ = gen(77)
+    g_ = G.gen(77)
     q, k, v = (torch.randn(B, L, H * d, generator=g_).to(torch.bfloat16).to(DEV) for _ in range(3))
     e = torch.randn(B, L, L, H * d, generator=g_).to(torch.bfloat16).to(DEV)
     g = torch.randn(B, L, H * d, generator=g_).to(DEV)
@@ -220,7 +165,7 @@ def test_kernel_at_L_1024_H_4():
     args = (q, k, v, e, g, None, H, c["scale"])
     ref64 = autograd(*args, torch.float64, device=DEV)
     ref32 = autograd(*args, torch.float32, device=DEV)
-    assert held(got, ref64, ref32, torch.bfloat16, f"bf16 {(B, L, H, d)} mask=none")
+    assert G.held(got, ref64, ref32, f"bf16 {(B, L, H, d)} mask=none", UNITS[torch.bfloat16], **HELD)
 
 
 # ---- 2. exact facts ------------------------------------------------------------------------------------------------------------
@@ -284,20 +229,20 @@ def test_dropout_replay(operand, mask_kind):
     c = case(shape, operand[0])
     ref64, ref32 = refs(shape, operand[0], mask_kind, drop)
     got = run_bwd(c, c[mask_kind], shape[2], dropout=drop)
-    assert held(got, ref64, ref32, operand[2], f"{operand[0]} {shape} mask={mask_kind} dropout={drop[0]}")
+    assert G.held(got, ref64, ref32, f"{operand[0]} {shape} mask={mask_kind} dropout={drop[0]}", UNITS[operand[2]], **HELD)
     again = run_bwd(c, c[mask_kind], shape[2], dropout=drop)
     other = run_bwd(c, c[mask_kind], shape[2], dropout=(drop[0], drop[1] + 1, drop[2]))
     for n in NAMES:
         assert torch.equal(got[n], again[n]) and not torch.equal(got[n], other[n]), n
     plain64, _ = refs(shape, operand[0], mask_kind)     # and the dropout matters: the reference without it is far away
-    assert rel(got["dq"], plain64["dq"]) > 0.1
+    assert G.rel(got["dq"], plain64["dq"]) > 0.1
 
 
 # ---- rf_elu_bwd ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", MODES)
 def test_elu_bwd_against_cpu(dtype):
     R.set_compute_dtype(dtype)
-    g_ = gen(5)
+    g_ = G.gen(5)
     n = 4099
     x, z, gy = (torch.randn(n, generator=g_) for _ in range(3))
     y = x + torch.nn.functional.elu(z)
@@ -305,7 +250,7 @@ def test_elu_bwd_against_cpu(dtype):
     zd = z.double().requires_grad_()
     (torch.nn.functional.elu(zd) * gy.double()).sum().backward()
     # a = y - x carries the fp32 rounding of y: 2^-23 |y| against a derivative of order 1
-    assert da.dtype == dtype and rel(da, zd.grad) < max(4 * UNIT[dtype], 1e-6)
+    assert da.dtype == dtype and G.rel(da, zd.grad) < max(4 * UNIT[dtype], 1e-6)
     assert torch.equal(ops.elu_bwd(gy.to(DEV), torch.nn.functional.elu(z).to(DEV), None, dtype),
                        ops.elu_bwd(gy.to(DEV), torch.nn.functional.elu(z).to(DEV), torch.zeros(n, device=DEV), dtype))
 
@@ -330,76 +275,27 @@ def restate(P, pre, node, edge, mask, H, block, keep=None, p=0.0):
     return torch.nn.functional.elu(lin(x, pre + ".to_out.0")) + node
 
 
-def oracle_grads(fn, P, node, edge, w, dtype=None, seed=0):
-    """float64 autograd of sum(fn(P, node, edge) * w): {"node", "edge", parameter names}, and with `dtype` also each gradient's
-    relative change after a one-rounding-unit relative jitter of both inputs and every parameter."""
-    def run(P, node, edge):
-        P = {k: v.detach().clone().requires_grad_() for k, v in P.items()}
-        nd, ed = (t.detach().double().cpu().clone().requires_grad_() for t in (node, edge))
-        (fn(P, nd, ed) * w.double().cpu()).sum().backward()
-        out = {k: v.grad for k, v in P.items()}
-        out["node"], out["edge"] = nd.grad, ed.grad
-        return out
-    ref = run(P, node, edge)
-    if dtype is None:
-        return ref, None
-    g_ = gen(seed + 1000)
-    jit = lambda t: t * (1 + UNIT[dtype] * (2 * torch.rand(t.shape, generator=g_, dtype=torch.float64) - 1))  # noqa: E731
-    refj = run({k: jit(v) for k, v in P.items()}, jit(node.detach().double().cpu()), jit(edge.detach().double().cpu()))
-    return ref, {k: rel(refj[k], ref[k]) for k in ref}
-
-
-def assert_close(got, ref, floor, dtype, key):
-    if key.endswith("node_to_k.bias"):
-        # b_k moves every logit of a row by the same q_i . b_k, which a softmax ignores (sum_j ds_ij = 0, under a mask and under
-        # dropout too): the exact gradient is 0 and the float64 reference holds only its own rounding noise, so a relative error
-        # has no denominator.  The gradient is sum_j dk_j, the sum of the rows whose outer products with node_j make up
-        # node_to_k.weight's gradient: the error is taken against that gradient's norm per input channel, under the same ceiling.
-        wref = ref[key[:-len("bias")] + "weight"]
-        den = wref.norm().item() / wref.shape[1] ** 0.5
-        assert ref[key].norm().item() < 1e-10 * den
-        err = (got.detach().double().cpu() - ref[key]).norm().item() / den
-        assert err < CEIL[dtype], (key, err, CEIL[dtype])
-        return
-    tol = max(CEIL[dtype], 3 * floor[key]) if floor is not None else CEIL[dtype]
-    err = rel(got, ref[key])
-    assert err < tol, (key, err, tol)
-
-
-def state(mod, pre):
-    return {f"{pre}.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
-
-
-def randomize(mod, seed):
-    """non-trivial biases and LayerNorm affines (the defaults 0 / 1 would hide their gradients' mistakes)"""
-    g_ = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g_) * 0.1 + (1.0 if name.endswith("ln.weight") else 0.0)).to(p.device))
-    return mod
+def check(got, ref, floor, dtype, tag):
+    """G.compare with every node_to_k.bias taken against its weight's gradient norm per input channel (the docstring above)"""
+    norms = {}
+    for key in ref:
+        if key.endswith("node_to_k.bias"):
+            wref = ref[key[:-len("bias")] + "weight"]
+            norms[key] = wref.norm().item() / wref.shape[1] ** 0.5
+    G.compare(got, ref, dtype, tag, floor, norms=norms)
 
 
 def make(block, dn, H, p_dropout=0.0, seed=0):
     torch.manual_seed(100 + seed + dn)
     cls = R.GraphTransformerBlock if block else R.GraphTransformer
-    return randomize(cls(dn, dn, dn, H, p_dropout).to(DEV), 7 + seed)
+    return G.randomize(cls(dn, dn, dn, H, p_dropout).to(DEV), 7 + seed, CENTRED)
 
 
 def inputs(B, L, dn, dtype, seed):
-    g_ = gen(seed)
+    g_ = G.gen(seed)
     node = torch.randn(B, L, dn, generator=g_).to(dtype).float()
     edge = torch.randn(B, L, L, dn, generator=g_).to(dtype).float()
     return node, edge
-
-
-def public_grads(mod, node, edge, mask, w):
-    for p in mod.parameters():
-        p.grad = None
-    ng, eg = node.to(DEV).requires_grad_(), edge.to(DEV).requires_grad_()
-    out = mod(ng, eg, None if mask is None else mask.to(DEV))
-    (out * w.to(DEV)).sum().backward()
-    return out.detach(), ng.grad, eg.grad
 
 
 @pytest.mark.parametrize("dtype", MODES, ids=["fp32", "bf16", "fp16"])
@@ -411,19 +307,16 @@ def test_module_grads_against_float64(block, L, dn, masked, dtype):
     B, H = 2, 4
     mod = make(block, dn, H).enable_backward()
     node, edge = inputs(B, L, dn, dtype, 31 + L)
-    w = torch.randn(B, L, dn if block else H * dn, generator=gen(L + dn))
+    w = torch.randn(B, L, dn if block else H * dn, generator=G.gen(L + dn))
     mask = mixed_mask(B, L, 5 + L) if masked else None
-    _, dnode, dedge = public_grads(mod, node, edge, mask, w)
+    got, _ = G.grads_of(mod, {"node": node, "edge": edge, "mask": mask}, w)
     if masked:
         fn = lambda P, nd, ed: restate(P, "m", nd, ed, mask, H, block)  # noqa: E731
     else:
         fn = lambda P, nd, ed: (O.graph_transformer_block if block else O.graph_transformer)(P, "m", nd, ed, H)  # noqa: E731
-    ref, floor = oracle_grads(fn, state(mod, "m"), node, edge, w, dtype)
-    assert_close(dnode, ref, floor, dtype, "node")
-    assert_close(dedge, ref, floor, dtype, "edge")
-    for name, p in mod.named_parameters():
-        assert p.grad is not None, name
-        assert_close(p.grad, ref, floor, dtype, "m." + name)
+    ref, floor = G.oracle_grads(fn, G.state(mod), {"node": node, "edge": edge}, w, UNIT[dtype])
+    assert all(t is not None for t in got.values()), got
+    check(got, ref, floor, dtype, f"{'block' if block else 'attn'} L={L} dn={dn} masked={masked}")
     # the set of gradients _backward returns is the set of parameters
     tape = {}
     y = mod.run(node.to(DEV), ops.cast(edge.to(DEV), dtype), None if mask is None else mask.to(DEV), tape=tape)
@@ -440,7 +333,7 @@ def test_training_mode_replays_the_attention_dropout(block, masked, dtype):
     B, L, dn, H, p, seed = 2, 16, 8, 4, 0.25, 77
     mod = make(block, dn, H, p_dropout=p, seed=1).enable_backward()
     node, edge = inputs(B, L, dn, dtype, 41)
-    w = torch.randn(B, L, dn if block else H * dn, generator=gen(43))
+    w = torch.randn(B, L, dn if block else H * dn, generator=G.gen(43))
     mask = mixed_mask(B, L, 17) if masked else None
     with torch.no_grad():
         plain = mod(node.to(DEV), edge.to(DEV), mask)
@@ -448,19 +341,16 @@ def test_training_mode_replays_the_attention_dropout(block, masked, dtype):
     runs = []
     for _ in range(2):
         R.manual_seed(seed)
-        out, dnode, dedge = public_grads(mod, node, edge, mask, w)
-        runs.append([out, dnode.clone(), dedge.clone()] + [q.grad.clone() for q in mod.parameters()])
+        got, out = G.grads_of(mod, {"node": node, "edge": edge, "mask": mask}, w)
+        runs.append([out] + [t.clone() for t in got.values()])
     assert all(torch.equal(a, b) for a, b in zip(*runs))
     assert not torch.equal(runs[0][0], plain)   # the dropout acts
     # the one dropout of the forward takes the counters from 0 on (R.manual_seed): its keep map, replayed in the reference
     keep = keep_map(B, H, L, (p, seed, 0)).cpu()
     assert RT.train_seed == seed and RT.train_offset == (B * H * L * L + 3) // 4
     fn = lambda P, nd, ed: restate(P, "m", nd, ed, mask, H, block, keep, p)  # noqa: E731
-    ref, floor = oracle_grads(fn, state(mod, "m"), node, edge, w, dtype)
-    assert_close(runs[0][1], ref, floor, dtype, "node")
-    assert_close(runs[0][2], ref, floor, dtype, "edge")
-    for name, q in mod.named_parameters():
-        assert_close(q.grad, ref, floor, dtype, "m." + name)
+    ref, floor = G.oracle_grads(fn, G.state(mod), {"node": node, "edge": edge}, w, UNIT[dtype])
+    check(got, ref, floor, dtype, f"{'block' if block else 'attn'} train masked={masked}")
 
 
 # ---- 6. the forward is unchanged --------------------------------------------------------------------------------------------------
@@ -490,16 +380,15 @@ def test_fp16_small_loss_does_not_underflow(block):
     B, L, dn, H = 2, 16, 8, 4
     mod = make(block, dn, H, seed=2).enable_backward()
     node, edge = inputs(B, L, dn, torch.float16, 61)
-    w = torch.randn(B, L, dn if block else H * dn, generator=gen(63))
+    w = torch.randn(B, L, dn if block else H * dn, generator=G.gen(63))
     mask = mixed_mask(B, L, 19)
     small = 2.0 ** -20
-    _, dnode, dedge = public_grads(mod, node, edge, mask, w * small)
+    got, _ = G.grads_of(mod, {"node": node, "edge": edge, "mask": mask}, w * small)
     fn = lambda P, nd, ed: restate(P, "m", nd, ed, mask, H, block)  # noqa: E731
-    ref, floor = oracle_grads(fn, state(mod, "m"), node, edge, w, torch.float16)
-    got = dict({"m." + n: q.grad for n, q in mod.named_parameters()}, node=dnode, edge=dedge)
+    ref, floor = G.oracle_grads(fn, G.state(mod), {"node": node, "edge": edge}, w, UNIT[torch.float16])
     for key, t in got.items():
         assert torch.isfinite(t).all() and t.abs().max() > 0, key
-        assert_close(t / small, ref, floor, torch.float16, key)
+    check({key: t / small for key, t in got.items()}, ref, floor, torch.float16, f"{'block' if block else 'attn'} small loss")
 
 
 # ---- 8. determinism and refusals -----------------------------------------------------------------------------------------------
@@ -508,11 +397,11 @@ def test_backward_is_deterministic():
     B, L, dn, H = 2, 65, 32, 4
     mod = make(True, dn, H, seed=3).enable_backward()
     node, edge = inputs(B, L, dn, torch.bfloat16, 71)
-    w = torch.randn(B, L, dn, generator=gen(73))
+    w = torch.randn(B, L, dn, generator=G.gen(73))
     runs = []
     for _ in range(2):
-        _, dnode, dedge = public_grads(mod, node, edge, mixed_mask(B, L, 23), w)
-        runs.append([dnode.clone(), dedge.clone()] + [q.grad.clone() for q in mod.parameters()])
+        got, _ = G.grads_of(mod, {"node": node, "edge": edge, "mask": mixed_mask(B, L, 23)}, w)
+        runs.append([t.clone() for t in got.values()])
     assert all(torch.equal(a, b) for a, b in zip(*runs))
     c = case(SHAPES[4], "bf16")
     a, b = run_bwd(c, c["mixed"], 4, dropout=(0.25, 3, 1)), run_bwd(c, c["mixed"], 4, dropout=(0.25, 3, 1))

@@ -1,7 +1,11 @@
 """Backward pass of PredictionHead / ResNet / ResBlock2D (enable_backward): the three new kernels against float64 CPU autograd,
 the modules' gradients against the CPU oracle (torch autograd through oracle/rf_oracle.py) in the three compute modes, dropout
 replay in training mode (finite differences), the fp16 gradient scaling, unchanged forward numbers, determinism, and the full
-model with a trainable head."""
+model with a trainable head.
+
+The references come from tests/grad_oracle.py (oracle_grads with one weight tensor per output).  The comparison is this file's
+own `compare`: the mode's ceiling with `<=` (the ELUs are smooth: no kink floor), and an absolute bound for the two biases that
+are exactly zero in exact arithmetic."""
 import functools
 
 import pytest
@@ -12,28 +16,14 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
+MODES, CEIL = G.MODES, G.CEIL
+_restore_mode = G.restore_mode()
 
 
 # ------------------------------------------------------------------------------------------------ kernels
@@ -43,7 +33,7 @@ def gen(seed):
                                              (288, 1, 1, 40, 24), (64, 1, 1, 40, 288), (64, 1, 1, 37, 64)])
 def test_conv_wgrad_against_cpu(dtype, C, taps, dil, L, Co):
     R.set_compute_dtype(dtype)
-    g = gen(C + taps + dil + L + Co)
+    g = G.gen(C + taps + dil + L + Co)
     B = 2
     x = torch.randn(B, L, L, C, generator=g).to(dtype)
     dy = torch.randn(B, L, L, Co, generator=g).to(dtype)
@@ -52,8 +42,8 @@ def test_conv_wgrad_against_cpu(dtype, C, taps, dil, L, Co):
     ref = torch.nn.grad.conv2d_weight(x.double().permute(0, 3, 1, 2), (Co, C, k, k), dy.double().permute(0, 3, 1, 2),
                                       padding=dil if taps == 9 else 0, dilation=dil)
     ref = ref.permute(0, 2, 3, 1).reshape(Co, taps * C)   # the forward's [co][tap][ci] layout
-    assert rel(dw, ref) < 1e-5
-    assert rel(db, dy.double().sum((0, 1, 2))) < 1e-5
+    assert G.rel(dw, ref) < 1e-5
+    assert G.rel(db, dy.double().sum((0, 1, 2))) < 1e-5
     dw2, db2 = ops.conv_wgrad(dy.to(DEV), x.to(DEV), taps, dil, bias=True)
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
@@ -62,7 +52,7 @@ def test_conv_wgrad_against_cpu(dtype, C, taps, dil, L, Co):
 @pytest.mark.parametrize("act", [False, True])
 def test_instnorm_bwd_against_cpu(dtype, act):
     R.set_compute_dtype(dtype)
-    g = gen(7 + act)
+    g = G.gen(7 + act)
     B, L, C = 2, 40, 64
     x = (torch.randn(B, L, L, C, generator=g) * 2 + 0.5).to(dtype)
     gamma = torch.rand(C, generator=g) + 0.5
@@ -80,15 +70,15 @@ def test_instnorm_bwd_against_cpu(dtype, act):
     a = y.detach().permute(0, 2, 3, 1).float().contiguous().to(DEV) if act else None
     dx, dgam, dbet = ops.instnorm_bwd(gy.to(DEV), xg, stats[0], gamma.to(DEV), eps=1e-6, act_out=a, dx_dtype=R.T())
     tol = {torch.float32: 1e-4, torch.bfloat16: 8e-3, torch.float16: 1e-3}[dtype]
-    assert rel(dx, xd.grad.permute(0, 2, 3, 1)) < tol
-    assert rel(dgam, gd.grad) < 1e-4 and rel(dbet, bd.grad) < 1e-4
+    assert G.rel(dx, xd.grad.permute(0, 2, 3, 1)) < tol
+    assert G.rel(dgam, gd.grad) < 1e-4 and G.rel(dbet, bd.grad) < 1e-4
     dx2, dgam2, dbet2 = ops.instnorm_bwd(gy.to(DEV), xg, stats[0], gamma.to(DEV), eps=1e-6, act_out=a, dx_dtype=R.T())
     assert torch.equal(dx, dx2) and torch.equal(dgam, dgam2) and torch.equal(dbet, dbet2)
 
 
 @pytest.mark.parametrize("D", [64, 288])
 def test_layernorm_bwd_against_cpu(D):
-    g = gen(D)
+    g = G.gen(D)
     x = torch.randn(3, 40, 40, D, generator=g) * 3 + 1
     gamma, beta = torch.rand(D, generator=g) + 0.5, torch.randn(D, generator=g)
     gy = torch.randn(3, 40, 40, D, generator=g)
@@ -96,7 +86,7 @@ def test_layernorm_bwd_against_cpu(D):
     gd, bd = gamma.double().requires_grad_(), beta.double().requires_grad_()
     (F.layer_norm(xd, (D,), gd, bd, 1e-5) * gy.double()).sum().backward()
     dx, dgam, dbet = ops.layernorm_bwd(x.to(DEV), gy.to(DEV), gamma.to(DEV), eps=1e-5)
-    assert rel(dx, xd.grad) < 1e-5 and rel(dgam, gd.grad) < 1e-5 and rel(dbet, bd.grad) < 1e-5
+    assert G.rel(dx, xd.grad) < 1e-5 and G.rel(dgam, gd.grad) < 1e-5 and G.rel(dbet, bd.grad) < 1e-5
     dx2, dgam2, dbet2 = ops.layernorm_bwd(x.to(DEV), gy.to(DEV), gamma.to(DEV), eps=1e-5)
     assert torch.equal(dx, dx2) and torch.equal(dgam, dgam2) and torch.equal(dbet, dbet2)
 
@@ -104,7 +94,7 @@ def test_layernorm_bwd_against_cpu(D):
 # ------------------------------------------------------------------------------------------------ modules vs oracle
 def _init_affine(mod, seed):
     """non-trivial InstanceNorm / LayerNorm affine parameters (the default 1 / 0 would hide a swapped gamma / beta)"""
-    g = gen(seed)
+    g = G.gen(seed)
     with torch.no_grad():
         for m in mod.modules():
             if isinstance(m, (torch.nn.InstanceNorm2d, torch.nn.LayerNorm)):
@@ -112,24 +102,23 @@ def _init_affine(mod, seed):
                 m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
 
 
-def oracle_grads(fn, mod, pre, inp, R_):
-    P = {pre + "." + k: v.detach().double().cpu().requires_grad_() for k, v in mod.state_dict().items()}
-    x = inp.detach().double().cpu().requires_grad_()
-    out = fn(P, x)
-    outs = out if isinstance(out, dict) else {"out": out}
-    sum((outs[k] * R_[k].double()).sum() for k in outs).backward()
-    return {k[len(pre) + 1:]: v.grad for k, v in P.items()}, x.grad
+def outputs(out):
+    return out if isinstance(out, dict) else {"out": out}
+
+
+def reference(fn, mod, pre, inp, R_):
+    """({parameter name: float64 gradient}, the input's) of sum_k sum(fn(P, x)[k] * R_[k])"""
+    ref, _ = G.oracle_grads(fn, G.state(mod, pre), {"x": inp},
+                            lambda out: sum((o * R_[k].double()).sum() for k, o in outputs(out).items()))
+    return {k[len(pre) + 1:]: v for k, v in ref.items() if k != "x"}, ref["x"]
 
 
 def module_grads(mod, inp, R_):
-    for p in mod.parameters():
-        p.grad = None
-    x = inp.detach().to(DEV).requires_grad_()
-    out = mod(x)
-    outs = out if isinstance(out, dict) else {"out": out}
-    assert all(o.requires_grad for o in outs.values())
-    sum((outs[k] * R_[k].to(DEV)).sum() for k in outs).backward()
-    return {k: p.grad for k, p in mod.named_parameters()}, x.grad, outs
+    def loss(out):
+        assert all(o.requires_grad for o in outputs(out).values())
+        return sum((o * R_[k].to(DEV)).sum() for k, o in outputs(out).items())
+    got, out = G.grads_of(mod, {"x": inp}, loss, pre="")
+    return {k[1:]: v for k, v in got.items() if k != "x"}, got["x"], outputs(out)
 
 
 def compare(dtype, got, ref, gx, rx, zero_keys=()):
@@ -140,8 +129,8 @@ def compare(dtype, got, ref, gx, rx, zero_keys=()):
         assert torch.isfinite(got[k]).all(), k
         if k in zero_keys:   # exactly zero in exact arithmetic: an absolute bound scaled by the matching weight's gradient
             continue
-        errs[k] = rel(got[k], r)
-    errs["input"] = rel(gx, rx)
+        errs[k] = G.rel(got[k], r)
+    errs["input"] = G.rel(gx, rx)
     bad = {k: e for k, e in errs.items() if e > ceil}
     print(f"{dtype} max rel-L2 {max(errs.values()):.3e} ({max(errs, key=errs.get)})")
     assert not bad, bad
@@ -156,10 +145,10 @@ def test_resblock2d_against_oracle(dtype):
     torch.manual_seed(1)
     mod = R.ResBlock2D(64, 3, 2).to(DEV).enable_backward()
     _init_affine(mod, 1)
-    x = torch.randn(2, 64, 40, 40, generator=gen(2))
-    R_ = {"out": torch.randn(2, 64, 40, 40, generator=gen(3))}
+    x = torch.randn(2, 64, 40, 40, generator=G.gen(2))
+    R_ = {"out": torch.randn(2, 64, 40, 40, generator=G.gen(3))}
     got, gx, _ = module_grads(mod, x, R_)
-    ref, rx = oracle_grads(lambda P, x: O.resblock2d(P, "m", x, 2), mod, "m", x, R_)
+    ref, rx = reference(lambda P, x: O.resblock2d(P, "m", x, 2), mod, "m", x, R_)
     compare(dtype, got, ref, gx, rx)
 
 
@@ -169,10 +158,10 @@ def test_resnet_against_oracle(dtype):
     torch.manual_seed(2)
     mod = R.ResNet(4, 64, 64, 37).to(DEV).enable_backward()
     _init_affine(mod, 2)
-    x = torch.randn(2, 64, 40, 40, generator=gen(4))
-    R_ = {"out": torch.randn(2, 37, 40, 40, generator=gen(5))}
+    x = torch.randn(2, 64, 40, 40, generator=G.gen(4))
+    R_ = {"out": torch.randn(2, 37, 40, 40, generator=G.gen(5))}
     got, gx, _ = module_grads(mod, x, R_)
-    ref, rx = oracle_grads(lambda P, x: O.resnet(P, "m", x, 4), mod, "m", x, R_)
+    ref, rx = reference(lambda P, x: O.resnet(P, "m", x, 4), mod, "m", x, R_)
     compare(dtype, got, ref, gx, rx)
 
 
@@ -180,8 +169,8 @@ def head_case(seed=3, C=64, B=2, L=40):
     torch.manual_seed(seed)
     head = R.PredictionHead(C, 4, 0.15).to(DEV)
     _init_affine(head, seed)
-    pair = torch.randn(B, L, L, C, generator=gen(seed)) + 0.3
-    R_ = {k: torch.randn(B, L, L, 19 if k == "phi" else 37, generator=gen(seed + i)) for i, k in enumerate(("theta", "phi", "dist", "omega"))}
+    pair = torch.randn(B, L, L, C, generator=G.gen(seed)) + 0.3
+    R_ = {k: torch.randn(B, L, L, 19 if k == "phi" else 37, generator=G.gen(seed + i)) for i, k in enumerate(("theta", "phi", "dist", "omega"))}
     return head, pair, R_
 
 
@@ -191,7 +180,7 @@ def test_prediction_head_against_oracle(dtype):
     head, pair, R_ = head_case()
     head.enable_backward()
     got, gx, _ = module_grads(head, pair, R_)
-    ref, rx = oracle_grads(lambda P, x: O.prediction_head(P, "h", x, 4), head, "h", pair, R_)
+    ref, rx = reference(lambda P, x: O.prediction_head(P, "h", x, 4), head, "h", pair, R_)
     # LayerNorm beta and the projection bias: exactly zero (every consumer starts bias-free 1x1 conv -> InstanceNorm)
     compare(dtype, got, ref, gx, rx, zero_keys=("proj.0.bias", "proj.1.bias"))
 
@@ -201,8 +190,8 @@ def _production_case():
     torch.manual_seed(5)
     mod = R.ResNet(4, 288, 288, 37)
     _init_affine(mod, 5)
-    x = torch.randn(1, 288, 256, 256, generator=gen(6))
-    R_ = {"out": torch.randn(1, 37, 256, 256, generator=gen(7))}
+    x = torch.randn(1, 288, 256, 256, generator=G.gen(6))
+    R_ = {"out": torch.randn(1, 37, 256, 256, generator=G.gen(7))}
     P = {"m." + k: v.detach().float().requires_grad_() for k, v in mod.state_dict().items()}
     xr = x.clone().requires_grad_()
     (O.resnet(P, "m", xr, 4) * R_["out"]).sum().backward()
@@ -234,7 +223,7 @@ def test_training_mode_finite_difference():
     for p in head.parameters():
         p.grad = None
     loss().backward()
-    v = [torch.randn(p.shape, generator=gen(i)).to(DEV) for i, p in enumerate(head.parameters())]
+    v = [torch.randn(p.shape, generator=G.gen(i)).to(DEV) for i, p in enumerate(head.parameters())]
     dot = sum((p.grad * vi).sum() for p, vi in zip(head.parameters(), v)).item()
     eps = 1e-4   # (1e-3 leaves a 5e-2 curvature term across the ELUs)
     with torch.no_grad():
@@ -259,8 +248,8 @@ def test_fp16_small_loss_does_not_underflow():
     g2, x2, _ = module_grads(head, pair, {k: v * 1e-6 for k, v in R_.items()})
     for k in g1:
         if k not in ("proj.0.bias", "proj.1.bias"):
-            assert rel(g2[k] * 1e6, g1[k]) < CEIL[torch.float16], k
-    assert rel(x2 * 1e6, x1) < CEIL[torch.float16]
+            assert G.rel(g2[k] * 1e6, g1[k]) < CEIL[torch.float16], k
+    assert G.rel(x2 * 1e6, x1) < CEIL[torch.float16]
 
 
 # ------------------------------------------------------------------------------------------------ forward, determinism, errors
@@ -313,7 +302,7 @@ def test_full_model_trains_the_head():
     torch.manual_seed(29)
     model = R.RoseTTAFold(**CFG1).to(DEV)
     model.prediction_head.enable_backward()
-    g = gen(31)
+    g = G.gen(31)
     B, N, L = 1, 8, 48
     msa = torch.randint(0, 21, (B, N, L), generator=g).to(DEV)
     seq, idx = msa[:, 0].clone(), torch.arange(L).repeat(B, 1).to(DEV)

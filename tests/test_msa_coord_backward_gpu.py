@@ -2,13 +2,11 @@
 oracle (oracle/rf_oracle.py: msa_update_with_pair_and_coord) in the three compute modes, unchanged forward numbers, the exact
 facts (to_k.bias, xyz, L = 1), dropout replay (finite differences), fp16 small losses, determinism and the refusal.
 
-Tolerance: the rule of tests/test_axial_backward_gpu.py, restated here.  The feed-forward's ReLU makes the exact gradient a
-discontinuous function of the forward's values: wherever a pre-activation lies within rounding distance of 0 the forward of a
-mode may take the other side of the kink.  A gradient is held to max(CEIL, 3 x kink floor): CEIL is the mode's ceiling (1e-4
-fp32, 1e-2 fp16, 5e-2 bf16) and the kink floor is the float64 gradient's own change under a relative jitter of one rounding
-unit of the mode on state, msa and every parameter.  xyz is never jittered: it enters through the distance mask alone, and every
-case asserts on the CPU that each pairwise CA distance is at least 1e-4 A away from every bin, so that the float64 mask is the
-kernels' (the fp32 distance error at these ranges is about 1e-5)."""
+Tolerance: the ceiling-or-kink-floor rule of tests/grad_oracle.py; the feed-forward's ReLU is the kink, and the jitter falls on
+state, msa and every parameter.  xyz is never jittered: it enters through the distance mask alone, and every case asserts on the
+CPU that each pairwise CA distance is at least 1e-4 A away from every bin, so that the float64 mask is the kernels' (the fp32
+distance error at these ranges is about 1e-5).  to_k.bias adds q_i . b_k to every logit of a row and drops out of the softmax:
+an exact zero here, rounding noise in the oracle."""
 import functools
 
 import pytest
@@ -18,14 +16,13 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+MODES, CEIL, UNIT = G.MODES, G.CEIL, G.UNIT
 BINS = (8.0, 12.0, 16.0, 20.0)
 GAP = 1e-4
 # (B, N, L, d_msa, d_state) -> seed of the coordinates (chosen so that the preconditions below hold).  L = 65: no multiple of 8
@@ -35,24 +32,13 @@ SHAPES = {(1, 3, 24, 32, 16): 2, (2, 2, 65, 64, 32): 0}
 WIDE, WIDE_SEED = (1, 4, 64, 384, 32), 0
 
 
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
+CENTRED = lambda name: name.endswith("weight")   # noqa: E731  the 1-D parameters drawn around 1
+_restore_mode = G.restore_mode()
 
 
 def coordinates(B, L, seed):
     """fp32 [B, L, 3, 3]: CA (atom 1) a random walk of 3.8 A steps, N and C at unit noise around it; asserts the preconditions"""
-    g_ = gen(7300 + seed)
+    g_ = G.gen(7300 + seed)
     step = torch.randn(B, L, 3, generator=g_)
     ca = (3.8 * step / step.norm(dim=-1, keepdim=True)).cumsum(1)
     xyz = (ca[:, :, None, :] + torch.randn(B, L, 3, 3, generator=g_) * torch.tensor([1.0, 0.0, 1.0])[:, None]).float().contiguous()
@@ -69,47 +55,13 @@ def coordinates(B, L, seed):
     return xyz
 
 
-def randomize(mod, seed):
-    """non-trivial LayerNorm affines and biases (the defaults 1 / 0 would hide their gradients' mistakes)"""
-    g = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.1 + (1.0 if name.endswith("weight") else 0.0)).to(p.device))
-    return mod
-
-
-def state_dict64(mod):
-    return {f"m.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
-
-
-def oracle_grads(P, xyz, st, msa, w, dtype=None, seed=0):
-    """float64 autograd of sum(oracle(P, xyz, st, msa) * w): {"state", "msa", name: gradient}, whether xyz got one, and with
-    `dtype` the kink floor: the same after a one-rounding-unit relative jitter of st, msa and every parameter (never xyz)."""
-    def run(P, st, msa):
-        P = {k: v.detach().clone().requires_grad_() for k, v in P.items()}
-        xd = xyz.detach().double().cpu().clone().requires_grad_()
-        sd, md = (t.detach().double().cpu().clone().requires_grad_() for t in (st, msa))
-        (O.msa_update_with_pair_and_coord(P, "m", xd, sd, md) * w.double().cpu()).sum().backward()
-        out = {k: v.grad for k, v in P.items() if v.grad is not None}
-        out.update(state=sd.grad, msa=md.grad)
-        return out, xd.grad
-    ref, dxyz = run(P, st, msa)
-    if dtype is None:
-        return ref, None, dxyz
-    g = gen(seed + 1000)
-    jit = lambda t: t.double().cpu() * (1 + UNIT[dtype] * (2 * torch.rand(t.shape, generator=g, dtype=torch.float64) - 1))  # noqa: E731
-    refj, _ = run({k: jit(v) for k, v in P.items()}, jit(st), jit(msa))
-    return ref, {k: rel(refj[k], ref[k]) for k in ref}, dxyz
-
-
 @functools.lru_cache(maxsize=None)
 def setup(shape, seed, p_dropout=0.0):
     """module (fp32 weights, CPU) and inputs, shared by the modes and left unchanged"""
     B, N, L, D, Ds = shape
     torch.manual_seed(100 + seed)
-    mod = randomize(R.MsaUpdateWithPairAndCoord(D, Ds, 32, 4 * D, p_dropout=p_dropout), 200 + seed)
-    g = gen(300 + seed)
+    mod = G.randomize(R.MsaUpdateWithPairAndCoord(D, Ds, 32, 4 * D, p_dropout=p_dropout), 200 + seed, CENTRED)
+    g = G.gen(300 + seed)
     xyz = coordinates(B, L, seed)
     st, msa = torch.randn(B, L, Ds, generator=g), torch.randn(B, N, L, D, generator=g)
     return mod, xyz, st, msa, torch.randn(B, N, L, D, generator=g)
@@ -117,48 +69,28 @@ def setup(shape, seed, p_dropout=0.0):
 
 @functools.lru_cache(maxsize=None)
 def reference(shape, seed, dtype):
+    """float64 autograd through the oracle and the kink floors; xyz takes part as an input that is never jittered"""
     mod, xyz, st, msa, w = setup(shape, seed)
-    return oracle_grads(state_dict64(mod), xyz, st, msa, w, dtype, seed)
+    fn = lambda P, xd, sd, md: O.msa_update_with_pair_and_coord(P, "m", xd, sd, md)  # noqa: E731
+    return G.oracle_grads(fn, G.state(mod), {"xyz": xyz, "state": st, "msa": msa}, w, UNIT[dtype], seed, fixed=("xyz",))
 
 
 def backward_of(mod, xyz, st, msa, w, scale=1.0, xyz_grad=False):
-    """loss.backward() on the device: (d state, d msa, {name: grad}, the xyz leaf)"""
-    for p in mod.parameters():
-        p.grad = None
-    xg = xyz.to(DEV).requires_grad_(xyz_grad)
-    sg, mg = st.to(DEV).requires_grad_(), msa.to(DEV).requires_grad_()
-    ((mod(xg, sg, mg) * w.to(DEV)).sum() * scale).backward()
-    return sg.grad, mg.grad, {n: p.grad for n, p in mod.named_parameters()}, xg
+    """loss.backward() on the device: {"state", "msa", "m." + name: gradient} (and "xyz" with xyz_grad)"""
+    leaves = ("xyz", "state", "msa") if xyz_grad else ("state", "msa")
+    return G.grads_of(mod, {"xyz": xyz, "state": st, "msa": msa}, w, scale, leaves)[0]
 
 
 def check_against_oracle(shape, seed, dtype):
     R.set_compute_dtype(dtype)
     mod, xyz, st, msa, w = setup(shape, seed)
-    ref, floor, dxyz = reference(shape, seed, dtype)
-    assert dxyz is None   # the oracle's autograd gives xyz no gradient: the mask is piecewise constant
-    mod = mod.to(DEV).enable_backward()
-    try:
-        dst, dmsa, grads, xg = backward_of(mod, xyz, st, msa, w, xyz_grad=True)
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
-    assert xg.grad is None
-    assert {"m." + n for n, g_ in grads.items() if g_ is not None} | {"state", "msa"} == set(ref)
-    # to_k.bias: q_i . b_k is added to every logit of a row and drops out of the softmax.  An exact zero here; rounding noise in
-    # the oracle, which a relative comparison would be meaningless against
-    assert (grads["to_k.bias"] == 0).all()
-    assert ref["m.to_k.bias"].norm() < 1e-9 * ref["m.to_q.bias"].norm()
-    got = dict({"m." + n: g_ for n, g_ in grads.items()}, state=dst, msa=dmsa)
-    worst = {}
-    for key in ref:
-        if key == "m.to_k.bias":
-            continue
-        tol = max(CEIL[dtype], 3 * floor[key])
-        err = rel(got[key], ref[key])
-        worst[key] = (err, tol)
-        print(f"{dtype} {shape} {key}: rel-L2 {err:.3e} (tolerance {tol:.3e}, kink floor {floor[key]:.3e})")
-    bad = {k: v for k, v in worst.items() if not v[0] < v[1]}
-    assert not bad, bad
+    ref, floor = reference(shape, seed, dtype)
+    assert "xyz" not in ref   # the oracle's autograd gives xyz no gradient: the mask is piecewise constant
+    with G.recording(mod):
+        got = backward_of(mod, xyz, st, msa, w, xyz_grad=True)
+    assert got.pop("xyz") is None
+    assert {k for k, g_ in got.items() if g_ is not None} == set(ref)
+    G.compare(got, ref, dtype, str(shape), floor, zero={"m.to_k.bias": 1e-9 * ref["m.to_q.bias"].norm()})
 
 
 # ------------------------------------------------------------------------------------------------ against the oracle
@@ -183,19 +115,13 @@ def test_fused_feed_forward_records_the_same_gradients(monkeypatch):
     B, N, L, D, _ = shape
     x = torch.zeros(B, N, L, D, device=DEV)
     mod, xyz, st, msa, w = setup(shape, WIDE_SEED)
-    mod = mod.to(DEV).enable_backward()
-    try:
+    with G.recording(mod):
         assert ops.ffn_fused_applies(x.to(torch.bfloat16), x, D, 4 * D)
-        dst, dmsa, grads, _ = backward_of(mod, xyz, st, msa, w)
-        fused = [dst.clone(), dmsa.clone()] + [g_.clone() for g_ in grads.values()]
+        fused = [g_.clone() for g_ in backward_of(mod, xyz, st, msa, w).values()]
         monkeypatch.setattr(ops, "FUSE_FFN", False)
         assert not ops.ffn_fused_applies(x.to(torch.bfloat16), x, D, 4 * D)
-        dst, dmsa, grads, _ = backward_of(mod, xyz, st, msa, w)
-        plain = [dst.clone(), dmsa.clone()] + [g_.clone() for g_ in grads.values()]   # (before the module, and its .grad, move)
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
-    assert all(torch.isfinite(a).all() for a in fused) and (fused[0] != 0).any()
+        plain = [g_.clone() for g_ in backward_of(mod, xyz, st, msa, w).values()]   # (before the module, and its .grad, move)
+    assert all(torch.isfinite(a).all() for a in fused) and (fused[-2] != 0).any()   # (d state)
     assert all(torch.equal(a, b) for a, b in zip(fused, plain))
 
 
@@ -204,14 +130,14 @@ def test_one_residue_gives_state_an_exact_zero():
     """L = 1: the softmax is the constant 1 whatever q and k are, so state receives exactly nothing (and msa still does)"""
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(5)
-    mod = randomize(R.MsaUpdateWithPairAndCoord(32, 16, 32, 128, p_dropout=0.0), 5).to(DEV).enable_backward()
-    g = gen(5)
+    mod = G.randomize(R.MsaUpdateWithPairAndCoord(32, 16, 32, 128, p_dropout=0.0), 5, CENTRED).to(DEV).enable_backward()
+    g = G.gen(5)
     xyz, st, msa = torch.randn(2, 1, 3, 3, generator=g), torch.randn(2, 1, 16, generator=g), torch.randn(2, 3, 1, 32, generator=g)
-    dst, dmsa, grads, _ = backward_of(mod, xyz, st, msa, torch.randn(2, 3, 1, 32, generator=g))
-    assert dst is not None and (dst == 0).all()
-    assert (dmsa != 0).any()
+    grads = backward_of(mod, xyz, st, msa, torch.randn(2, 3, 1, 32, generator=g))
+    assert grads["state"] is not None and (grads["state"] == 0).all()
+    assert (grads["msa"] != 0).any()
     for n in ("to_q.weight", "to_q.bias", "to_k.weight", "to_k.bias", "ln_state.weight", "ln_state.bias"):
-        assert (grads[n] == 0).all(), n
+        assert (grads["m." + n] == 0).all(), n
 
 
 # ------------------------------------------------------------------------------------------------ forward unchanged
@@ -245,11 +171,9 @@ def test_dropout_replay_finite_differences():
     R.set_compute_dtype(torch.float32)
     shape, seed = (1, 3, 24, 32, 16), SHAPES[(1, 3, 24, 32, 16)]
     mod, xyz, st, msa, w = setup(shape, seed, 0.2)
-    mod = mod.to(DEV)
-    try:
-        mod.train().enable_backward()
+    with G.recording(mod, train=True):
         xyz, st, msa, w = (t.to(DEV) for t in (xyz, st, msa, w))
-        g = gen(31)
+        g = G.gen(31)
         vs, vm = torch.randn(st.shape, generator=g).to(DEV), torch.randn(msa.shape, generator=g).to(DEV)
 
         def loss(s_, m_):
@@ -281,9 +205,6 @@ def test_dropout_replay_finite_differences():
             wq.copy_(w0)
         an_w = (mod.to_q.weight.grad * dw).sum().item()
         assert abs((lp - lm) / (2 * eps) - an_w) <= 2e-2 * abs(an_w) + 1e-3, ((lp - lm) / (2 * eps), an_w)
-    finally:
-        mod.eval().enable_backward(False)
-        mod.to("cpu")
 
 
 # ------------------------------------------------------------------------------------------------ fp16 small losses
@@ -291,23 +212,16 @@ def test_fp16_small_loss_does_not_underflow():
     R.set_compute_dtype(torch.float16)
     shape = (1, 3, 24, 32, 16)
     mod, xyz, st, msa, w = setup(shape, SHAPES[shape])
-    mod = mod.to(DEV).enable_backward()
-    try:
-        res = []
-        for scale in (1.0, 1e-6):
-            dst, dmsa, grads, _ = backward_of(mod, xyz, st, msa, w, scale=scale)
-            res.append(dict(grads, state=dst, msa=dmsa))
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
+    with G.recording(mod):
+        res = [backward_of(mod, xyz, st, msa, w, scale=scale) for scale in (1.0, 1e-6)]
     for key, a in res[0].items():
         b = res[1][key]
         assert torch.isfinite(b).all(), key
-        if key == "to_k.bias":
+        if key == "m.to_k.bias":
             assert (b == 0).all()
             continue
         assert b.abs().max() > 0, key
-        assert rel(b * 1e6, a) < CEIL[torch.float16], key
+        assert G.rel(b * 1e6, a) < CEIL[torch.float16], key
 
 
 # ------------------------------------------------------------------------------------------------ determinism
@@ -315,15 +229,8 @@ def test_backward_is_deterministic():
     R.set_compute_dtype(torch.bfloat16)
     shape = (2, 2, 65, 64, 32)
     mod, xyz, st, msa, w = setup(shape, SHAPES[shape])
-    mod = mod.to(DEV).enable_backward()
-    try:
-        res = []
-        for _ in range(2):
-            dst, dmsa, grads, _ = backward_of(mod, xyz, st, msa, w)
-            res.append([dst.clone(), dmsa.clone()] + [g_.clone() for g_ in grads.values()])
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
+    with G.recording(mod):
+        res = [[g_.clone() for g_ in backward_of(mod, xyz, st, msa, w).values()] for _ in range(2)]
     assert all(torch.equal(a, b) for a, b in zip(*res))
 
 
@@ -332,7 +239,7 @@ def test_channel_counts_checked_while_recording():
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(7)
     mod = R.MsaUpdateWithPairAndCoord(36, 16, 32, 144, p_dropout=0.0).to(DEV)
-    g = gen(7)
+    g = G.gen(7)
     xyz, st, msa = (torch.randn(s, generator=g).to(DEV) for s in ((1, 8, 3, 3), (1, 8, 16), (1, 2, 8, 36)))
     with torch.no_grad():
         plain = mod(xyz, st, msa)   # d_msa = 36 is fine for the forward

@@ -3,11 +3,9 @@ parameter against float64 autograd through the CPU oracle (oracle/rf_oracle.py: 
 in the three compute modes, unchanged forward numbers, the exact facts (the pair2att biases in eval mode, L = 1), dropout replay
 at all four sites (finite differences), fp16 small losses, determinism and the refusals.
 
-Tolerance: the rule of tests/test_msa_coord_backward_gpu.py, restated here.  The feed-forward's ReLU makes the exact gradient a
-discontinuous function of the forward's values: wherever a pre-activation lies within rounding distance of 0 the forward of a
-mode may take the other side of the kink.  A gradient is held to max(CEIL, 3 x kink floor): CEIL is the mode's ceiling (1e-4
-fp32, 1e-2 fp16, 5e-2 bf16) and the kink floor is the float64 gradient's own change under a relative jitter of one rounding
-unit of the mode on msa, pair and every parameter."""
+Tolerance: the ceiling-or-kink-floor rule of tests/grad_oracle.py; the feed-forward's ReLU is the kink, and the jitter falls on
+msa, pair and every parameter.  In eval mode both pair2att biases add one constant per head to a whole softmax row and drop out of
+it: exact zeros here, rounding noise in the oracle."""
 import functools
 
 import pytest
@@ -17,13 +15,12 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+MODES, CEIL, UNIT = G.MODES, G.CEIL, G.UNIT
 # (B, N, L, d_msa, d_pair, H, layers); layers = 0: the layer class alone.  L = 65: no multiple of 8 nor of a wave, two samples,
 # and one layer of 4 heads: the 16-bit copy of dz is padded to 8 columns; WIDE: the model's width and depth.
 SHAPES = [(1, 3, 24, 32, 32, 4, 2), (2, 2, 65, 64, 40, 4, 1), (1, 2, 13, 32, 32, 4, 0)]
@@ -37,33 +34,8 @@ SEEDS = {SHAPES[0]: 0, SHAPES[1]: 1, SHAPES[2]: 0, WIDE: 0}
 BIASES = ("pair2att.1.bias", "pair2att.2.bias")
 
 
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def randomize(mod, seed):
-    """non-trivial LayerNorm affines and biases (the defaults 1 / 0 would hide their gradients' mistakes)"""
-    g = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.1 + (1.0 if name.endswith("weight") else 0.0)).to(p.device))
-    return mod
-
-
-def state_dict64(mod):
-    return {f"m.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
+CENTRED = lambda name: name.endswith("weight")   # noqa: E731  the 1-D parameters drawn around 1
+_restore_mode = G.restore_mode()
 
 
 def build_module(shape, p_dropout=0.0):
@@ -80,33 +52,14 @@ def oracle_forward(shape, P, msa, pair):
     return O.msa_update_with_pair(P, "m", msa, pair, nl, H)
 
 
-def oracle_grads(shape, P, msa, pair, w, dtype=None, seed=0):
-    """float64 autograd of sum(oracle(P, msa, pair) * w): {"msa", "pair", name: gradient}, and with `dtype` the kink floor: the
-    same after a one-rounding-unit relative jitter of msa, pair and every parameter."""
-    def run(P, msa, pair):
-        P = {k: v.detach().clone().requires_grad_() for k, v in P.items()}
-        md, pd = (t.detach().double().cpu().clone().requires_grad_() for t in (msa, pair))
-        (oracle_forward(shape, P, md, pd) * w.double().cpu()).sum().backward()
-        out = {k: v.grad for k, v in P.items() if v.grad is not None}
-        out.update(msa=md.grad, pair=pd.grad)
-        return out
-    ref = run(P, msa, pair)
-    if dtype is None:
-        return ref, None
-    g = gen(seed + 1000)
-    jit = lambda t: t.double().cpu() * (1 + UNIT[dtype] * (2 * torch.rand(t.shape, generator=g, dtype=torch.float64) - 1))  # noqa: E731
-    refj = run({k: jit(v) for k, v in P.items()}, jit(msa), jit(pair))
-    return ref, {k: rel(refj[k], ref[k]) for k in ref}
-
-
 @functools.lru_cache(maxsize=None)
 def setup(shape, p_dropout=0.0):
     """module (fp32 weights, CPU) and inputs, shared by the modes and left unchanged"""
     B, N, L, D, Dp, H, nl = shape
     seed = 17 * L + nl + 1000 * SEEDS[shape]
     torch.manual_seed(100 + seed)
-    mod = randomize(build_module(shape, p_dropout), 200 + seed)
-    g = gen(300 + seed)
+    mod = G.randomize(build_module(shape, p_dropout), 200 + seed, CENTRED)
+    g = G.gen(300 + seed)
     msa, pair = torch.randn(B, N, L, D, generator=g), torch.randn(B, L, L, Dp, generator=g)
     return mod, msa, pair, torch.randn(B, N, L, D, generator=g)
 
@@ -114,45 +67,25 @@ def setup(shape, p_dropout=0.0):
 @functools.lru_cache(maxsize=None)
 def reference(shape, dtype):
     mod, msa, pair, w = setup(shape)
-    return oracle_grads(shape, state_dict64(mod), msa, pair, w, dtype, shape[2])
+    fn = lambda P, md, pd: oracle_forward(shape, P, md, pd)  # noqa: E731
+    return G.oracle_grads(fn, G.state(mod), {"msa": msa, "pair": pair}, w, UNIT[dtype], shape[2])
 
 
 def backward_of(mod, msa, pair, w, scale=1.0):
-    """loss.backward() on the device: (d msa, d pair, {name: grad})"""
-    for p in mod.parameters():
-        p.grad = None
-    mg, pg = msa.to(DEV).requires_grad_(), pair.to(DEV).requires_grad_()
-    ((mod(mg, pg) * w.to(DEV)).sum() * scale).backward()
-    return mg.grad, pg.grad, {n: p.grad for n, p in mod.named_parameters()}
+    """loss.backward() on the device: {"msa", "pair", "m." + name: gradient}"""
+    return G.grads_of(mod, {"msa": msa, "pair": pair}, w, scale)[0]
 
 
 def check_against_oracle(shape, dtype):
     R.set_compute_dtype(dtype)
     mod, msa, pair, w = setup(shape)
     ref, floor = reference(shape, dtype)
-    mod = mod.to(DEV).enable_backward()
-    try:
-        dmsa, dpair, grads = backward_of(mod, msa, pair, w)
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
-    assert {"m." + n for n, g_ in grads.items() if g_ is not None} | {"msa", "pair"} == set(ref)
-    got = dict({"m." + n: g_ for n, g_ in grads.items()}, msa=dmsa, pair=dpair)
-    assert torch.equal(dpair, dpair.transpose(1, 2))   # the symmetrisation's gradient, bit for bit
-    worst = {}
-    for key in ref:
-        if key.endswith(BIASES):
-            # eval mode: both add one constant per head to a whole softmax row and drop out of it.  An exact zero here; rounding
-            # noise in the oracle, which a relative comparison would be meaningless against
-            assert (got[key] == 0).all(), key
-            assert ref[key].norm() < 1e-9 * ref[key.rsplit(".", 1)[0] + ".weight"].norm(), key
-            continue
-        tol = max(CEIL[dtype], 3 * floor[key])
-        err = rel(got[key], ref[key])
-        worst[key] = (err, tol)
-        print(f"{dtype} {shape} {key}: rel-L2 {err:.3e} (tolerance {tol:.3e}, kink floor {floor[key]:.3e})")
-    bad = {k: v for k, v in worst.items() if not v[0] < v[1]}
-    assert not bad, bad
+    with G.recording(mod):
+        got = backward_of(mod, msa, pair, w)
+    assert {k for k, g_ in got.items() if g_ is not None} == set(ref)
+    assert torch.equal(got["pair"], got["pair"].transpose(1, 2))   # the symmetrisation's gradient, bit for bit
+    zero = {k: 1e-9 * ref[k.rsplit(".", 1)[0] + ".weight"].norm() for k in ref if k.endswith(BIASES)}
+    G.compare(got, ref, dtype, str(shape), floor, zero=zero)
 
 
 # ------------------------------------------------------------------------------------------------ against the oracle
@@ -174,12 +107,12 @@ def test_one_residue_gives_pair_an_exact_zero():
     still does)"""
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(5)
-    mod = randomize(R.MsaUpdateWithPair(32, 24, 4, n_encoder_layers=2, p_dropout=0.0), 5).to(DEV).enable_backward()
-    g = gen(5)
+    mod = G.randomize(R.MsaUpdateWithPair(32, 24, 4, n_encoder_layers=2, p_dropout=0.0), 5, CENTRED).to(DEV).enable_backward()
+    g = G.gen(5)
     msa, pair = torch.randn(2, 3, 1, 32, generator=g), torch.randn(2, 1, 1, 24, generator=g)
-    dmsa, dpair, grads = backward_of(mod, msa, pair, torch.randn(2, 3, 1, 32, generator=g))
-    assert dpair is not None and (dpair == 0).all()
-    assert (dmsa != 0).any()
+    grads = backward_of(mod, msa, pair, torch.randn(2, 3, 1, 32, generator=g))
+    assert grads["pair"] is not None and (grads.pop("pair") == 0).all()
+    assert (grads.pop("msa") != 0).any()
     seen = 0
     for n, g_ in grads.items():
         if ".pair2att." in n:
@@ -228,11 +161,9 @@ def test_dropout_replay_finite_differences():
     R.set_compute_dtype(torch.float32)
     shape = SHAPES[0]
     mod, msa, pair, w = setup(shape, 0.2)
-    mod = mod.to(DEV)
-    try:
-        mod.train().enable_backward()
+    with G.recording(mod, train=True):
         msa, pair, w = (t.to(DEV) for t in (msa, pair, w))
-        g = gen(31)
+        g = G.gen(31)
         vm, vp = torch.randn(msa.shape, generator=g).to(DEV), torch.randn(pair.shape, generator=g).to(DEV)
 
         def loss(m_, p_):
@@ -280,9 +211,6 @@ def test_dropout_replay_finite_differences():
                 bad[name] = (fd, an_w, typical)
         assert not bad, bad
         assert (layer.pair2att[2].bias.grad != 0).any() and (layer.pair2att[1].bias.grad != 0).any()
-    finally:
-        mod.eval().enable_backward(False)
-        mod.to("cpu")
 
 
 # ------------------------------------------------------------------------------------------------ fp16 small losses
@@ -290,15 +218,8 @@ def test_fp16_small_loss_does_not_underflow():
     R.set_compute_dtype(torch.float16)
     shape = SHAPES[0]
     mod, msa, pair, w = setup(shape)
-    mod = mod.to(DEV).enable_backward()
-    try:
-        res = []
-        for scale in (1.0, 1e-6):
-            dmsa, dpair, grads = backward_of(mod, msa, pair, w, scale=scale)
-            res.append(dict(grads, msa=dmsa, pair=dpair))
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
+    with G.recording(mod):
+        res = [backward_of(mod, msa, pair, w, scale=scale) for scale in (1.0, 1e-6)]
     for key, a in res[0].items():
         b = res[1][key]
         assert torch.isfinite(b).all(), key
@@ -306,7 +227,7 @@ def test_fp16_small_loss_does_not_underflow():
             assert (b == 0).all()
             continue
         assert b.abs().max() > 0, key
-        assert rel(b * 1e6, a) < CEIL[torch.float16], key
+        assert G.rel(b * 1e6, a) < CEIL[torch.float16], key
 
 
 # ------------------------------------------------------------------------------------------------ determinism
@@ -314,15 +235,8 @@ def test_backward_is_deterministic():
     R.set_compute_dtype(torch.bfloat16)
     shape = SHAPES[1]
     mod, msa, pair, w = setup(shape)
-    mod = mod.to(DEV).enable_backward()
-    try:
-        res = []
-        for _ in range(2):
-            dmsa, dpair, grads = backward_of(mod, msa, pair, w)
-            res.append([dmsa.clone(), dpair.clone()] + [g_.clone() for g_ in grads.values()])
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
+    with G.recording(mod):
+        res = [[g_.clone() for g_ in backward_of(mod, msa, pair, w).values()] for _ in range(2)]
     assert all(torch.equal(a, b) for a, b in zip(*res))
 
 
@@ -350,7 +264,7 @@ def test_a_module_that_did_not_opt_in_records_nothing():
 def test_row_group_and_channel_counts_refused_while_recording():
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(7)
-    g = gen(7)
+    g = G.gen(7)
     mod = R.MsaUpdateWithPair(32, 24, 4, n_encoder_layers=1, p_dropout=0.0).to(DEV)
     msa, pair = torch.randn(1, 2, 8, 32, generator=g).to(DEV), torch.randn(1, 8, 8, 24, generator=g).to(DEV)
     group = object()   # never reached: the refusal comes first

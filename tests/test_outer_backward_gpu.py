@@ -2,7 +2,7 @@
 autograd, the module's gradients against float64 autograd through the CPU oracle (oracle/rf_oracle.py) in the three compute
 modes on every route (general forward, fused forward, several slabs), unchanged forward numbers, the memory bound that "the
 P^2-wide tensor never exists" means, determinism, fp16 small losses, the refusals, and the one-input modules the change to
-the autograd Function must leave alone."""
+the autograd Function must leave alone.  The module is held by the ceiling-or-kink-floor rule of tests/grad_oracle.py."""
 import functools
 
 import pytest
@@ -12,17 +12,14 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops  # noqa: E402
 from rosettafold_pytorch_amd.runtime import RT  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-# the rule of tests/test_axial_backward_gpu.py: the mode's ceiling, or three times the float64 gradient's own change under a
-# one-rounding-unit relative jitter of inputs and weights, whichever is larger
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+MODES, CEIL, UNIT = G.MODES, G.CEIL, G.UNIT
 KERNEL_TOL = {torch.float32: 1e-6, torch.float16: 1e-3, torch.bfloat16: 8e-3}   # one pass, one rounding of the result
 
 # (P, Dout, B, N, L): the smallest shape of each route
@@ -30,63 +27,8 @@ GENERAL = (4, 16, 2, 5, 7)       # general forward, depth padded to 8, odd L, P 
 FUSED = (32, 288, 1, 64, 16)     # 16-bit modes: the fused forward records
 SLABS = (32, 288, 1, 64, 48)     # slab budget forced down: 20 + 20 + 8 rows (16-bit), 10 x 4 + 8 (fp32)
 SLAB_BYTES = 20 * 3 * 48 * 1024 * 2
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    budget = RT.outer_bwd_slab_bytes
-    yield
-    RT.outer_bwd_slab_bytes = budget
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def oracle_grads(fn, P, xs, w, dtype=None, seed=0):
-    """float64 autograd of sum(fn(P, **xs) * w): {input name: d/dinput, param name: d/dP[name]}, and with `dtype` also the
-    relative change of each under a one-rounding-unit relative jitter of every input and parameter."""
-    def run(P, xs):
-        P = {k: v.detach().clone().requires_grad_() for k, v in P.items()}
-        xd = {k: v.detach().double().cpu().clone().requires_grad_() for k, v in xs.items()}
-        (fn(P, **xd) * w.double().cpu()).sum().backward()
-        out = {k: v.grad for k, v in P.items() if v.grad is not None}
-        out.update({k: v.grad for k, v in xd.items()})
-        return out
-    ref = run(P, xs)
-    if dtype is None:
-        return ref, None
-    g = gen(seed + 1000)
-    jit = lambda t: t * (1 + UNIT[dtype] * (2 * torch.rand(t.shape, generator=g, dtype=torch.float64) - 1))  # noqa: E731
-    refj = run({k: jit(v) for k, v in P.items()}, {k: jit(v.detach().double().cpu()) for k, v in xs.items()})
-    return ref, {k: rel(refj[k], ref[k]) for k in ref}
-
-
-def assert_close(got, ref, floor, dtype, key):
-    tol = max(CEIL[dtype], 3 * floor[key]) if floor is not None else CEIL[dtype]
-    err = rel(got, ref[key])
-    print(f"{key}: err {err:.3e} tol {tol:.3e}")
-    assert err < tol, (key, err, tol)
-
-
-def state(mod, pre):
-    return {f"{pre}.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
-
-
-def randomize(mod, seed):
-    """non-trivial LayerNorm affines and biases (the defaults 1 / 0 would hide their gradients' mistakes)"""
-    g = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.1 + (1.0 if "fn.0.weight" in name else 0.0)).to(p.device))
-    return mod
+CENTRED = lambda name: "fn.0.weight" in name   # noqa: E731  the 1-D parameters drawn around 1
+_restore_mode = G.restore_mode(also=(RT, "outer_bwd_slab_bytes"))
 
 
 # ------------------------------------------------------------------------------------------------ the kernel
@@ -94,7 +36,7 @@ def randomize(mod, seed):
 @pytest.mark.parametrize("D", [1024, 16])
 def test_layernorm_bwd_fused_against_cpu(dtype, D):
     R.set_compute_dtype(dtype)
-    g = gen(D)
+    g = G.gen(D)
     rows, eps = 70, 1e-5   # 70 rows: 8 full blocks of 8 rows and one of 6, its last wave idle
     o = (torch.randn(rows, D, generator=g) * 0.8 + 0.3).to(dtype)
     dz = torch.randn(rows, D, generator=g).to(dtype)
@@ -107,7 +49,7 @@ def test_layernorm_bwd_fused_against_cpu(dtype, D):
     (zr * dz.double()).sum().backward()   # (from the same rounded o and dz the kernel read)
     tol = KERNEL_TOL[dtype]
     for name, got, ref in (("do", do, od.grad), ("z", z, zr), ("dgamma", dgam, gd.grad), ("dbeta", dbet, bd.grad)):
-        err = rel(got, ref)
+        err = G.rel(got, ref)
         print(f"{name}: err {err:.3e} tol {tol:.3e}")
         assert err < tol, (name, err, tol)
     # in place (dx over g, z over x) and accumulating: the same bits, and the column sums added to what was there
@@ -138,8 +80,8 @@ def _case(shape):
     """module (fp32 weights, CPU), x ~ randn, y ~ 0.1 randn, output weights: shared by the modes and the tests"""
     P, Dout, B, N, L = shape
     torch.manual_seed(P + L)
-    mod = randomize(R.OuterProductMean(P, Dout), L)
-    g = gen(L)
+    mod = G.randomize(R.OuterProductMean(P, Dout), L, CENTRED)
+    g = G.gen(L)
     return (mod, torch.randn(B, N, L, P, generator=g), 0.1 * torch.randn(B, N, L, P, generator=g),
             torch.randn(B, L, L, Dout, generator=g))
 
@@ -150,8 +92,8 @@ def _reference(shape, dtype, one):
     mod, x, y, w = _case(shape)
     x, y = x.to(dtype).float(), y.to(dtype).float()
     if one:
-        return oracle_grads(lambda P, x: O.outer_product_mean(P, "m", x, x), state(mod, "m"), {"x": x}, w, dtype)
-    return oracle_grads(lambda P, x, y: O.outer_product_mean(P, "m", x, y), state(mod, "m"), {"x": x, "y": y}, w, dtype)
+        return G.oracle_grads(lambda P, x: O.outer_product_mean(P, "m", x, x), G.state(mod), {"x": x}, w, UNIT[dtype])
+    return G.oracle_grads(lambda P, x, y: O.outer_product_mean(P, "m", x, y), G.state(mod), {"x": x, "y": y}, w, UNIT[dtype])
 
 
 def _slabs(mod, shape):
@@ -178,19 +120,12 @@ def test_module_grads_against_oracle(dtype, one, shape):
         assert n >= 3 and ragged, (n, ragged)
     else:
         assert _slabs(mod, shape) == (1, 0)
-    xg = x.to(dtype).float().to(DEV).requires_grad_()
-    yg = y.to(dtype).float().to(DEV).requires_grad_()
-    out = mod(xg) if one else mod(xg, yg)
-    (out * w.to(DEV)).sum().backward()
-    assert_close(xg.grad, ref, floor, dtype, "x")
-    if one:
-        assert yg.grad is None
-    else:
-        assert_close(yg.grad, ref, floor, dtype, "y")
-    assert {"m." + n_ for n_, _ in mod.named_parameters()} | ({"x"} if one else {"x", "y"}) == set(ref)
+    xs = {"x": x.to(dtype).float()} if one else {"x": x.to(dtype).float(), "y": y.to(dtype).float()}
+    got, _ = G.grads_of(mod, xs, w)
+    assert set(got) == set(ref)
     for name, p in mod.named_parameters():
         assert p.grad is not None and p.grad.shape == p.shape
-        assert_close(p.grad, ref, floor, dtype, "m." + name)
+    G.compare(got, ref, dtype, f"{shape} {'x' if one else 'xy'}", floor)
 
 
 def test_only_the_wanted_input_gets_a_gradient():
@@ -200,10 +135,10 @@ def test_only_the_wanted_input_gets_a_gradient():
     mod = R.OuterProductMean(GENERAL[0], GENERAL[1])
     mod.load_state_dict(cpu_mod.state_dict())
     mod = mod.to(DEV).enable_backward()
-    xg, yg = x.to(DEV), y.to(DEV).requires_grad_()
-    (mod(xg, yg) * w.to(DEV)).sum().backward()
-    assert xg.grad is None
-    assert_close(yg.grad, ref, None, torch.float32, "y")
+    xg = x.to(DEV)
+    got, _ = G.grads_of(mod, {"x": xg, "y": y}, w, leaves=("y",))
+    assert xg.grad is None and "x" not in got
+    G.compare(got, {"y": ref["y"]}, torch.float32, f"{GENERAL} y alone")
 
 
 # ------------------------------------------------------------------------------------------------ forward unchanged
@@ -235,7 +170,7 @@ def test_backward_never_holds_the_wide_tensor():
     torch.manual_seed(71)
     B, L, N, P, Dout = 1, 128, 64, 32, 288
     mod = R.OuterProductMean(P, Dout).to(DEV).enable_backward()
-    g = gen(71)
+    g = G.gen(71)
     x = torch.randn(B, N, L, P, generator=g).to(DEV).requires_grad_()
     y = (0.1 * torch.randn(B, N, L, P, generator=g)).to(DEV).requires_grad_()
     w = torch.randn(B, L, L, Dout, generator=g).to(DEV)
@@ -261,13 +196,7 @@ def test_backward_is_deterministic():
     mod.load_state_dict(cpu_mod.state_dict())
     mod = mod.to(DEV).enable_backward()
     assert _slabs(mod, SLABS)[0] >= 3
-    res = []
-    for _ in range(2):
-        for p in mod.parameters():
-            p.grad = None
-        xg, yg = x.to(DEV).requires_grad_(), y.to(DEV).requires_grad_()
-        (mod(xg, yg) * w.to(DEV)).sum().backward()
-        res.append([xg.grad.clone(), yg.grad.clone()] + [p.grad.clone() for p in mod.parameters()])
+    res = [[t.clone() for t in G.grads_of(mod, {"x": x, "y": y}, w)[0].values()] for _ in range(2)]
     assert all(torch.equal(a, b) for a, b in zip(*res))
 
 
@@ -278,16 +207,10 @@ def test_fp16_small_loss_does_not_underflow():
     mod = R.OuterProductMean(FUSED[0], FUSED[1])
     mod.load_state_dict(cpu_mod.state_dict())
     mod = mod.to(DEV).enable_backward()
-    res = []
-    for scale in (1.0, 1e-6):
-        for p in mod.parameters():
-            p.grad = None
-        xg, yg = x.to(DEV).requires_grad_(), y.to(DEV).requires_grad_()
-        ((mod(xg, yg) * w.to(DEV)).sum() * scale).backward()
-        res.append([xg.grad, yg.grad] + [p.grad for p in mod.parameters()])
+    res = [list(G.grads_of(mod, {"x": x, "y": y}, w, scale)[0].values()) for scale in (1.0, 1e-6)]
     for a, b in zip(res[0], res[1]):
         assert torch.isfinite(b).all() and b.abs().max() > 0
-        assert rel(b * 1e6, a) < CEIL[torch.float16]
+        assert G.rel(b * 1e6, a) < CEIL[torch.float16]
 
 
 # ------------------------------------------------------------------------------------------------ refusals
@@ -313,18 +236,15 @@ def test_one_input_modules_unchanged():
     of every parameter, the same bits on a second run"""
     R.set_compute_dtype(torch.bfloat16)
     torch.manual_seed(81)
-    g = gen(81)
+    g = G.gen(81)
     for mod, shape in ((R.FeedForward(64, 96), (1, 8, 8, 64)),
                        (R.PerformerSelfAttention(32, heads=2, generalized_attention=True), (3, 64, 32))):
-        mod = randomize(mod.to(DEV), 81).enable_backward()
+        mod = G.randomize(mod.to(DEV), 81, CENTRED).enable_backward()
         x, w = torch.randn(shape, generator=g).to(DEV), torch.randn(shape, generator=g).to(DEV)
         res = []
         for _ in range(2):
-            for p in mod.parameters():
-                p.grad = None
-            xg = x.clone().requires_grad_()
-            (mod(xg) * w).sum().backward()
-            assert xg.grad.shape == x.shape and all(p.grad is not None for p in mod.parameters())
-            res.append([xg.grad.clone()] + [p.grad.clone() for p in mod.parameters()])
+            got, _ = G.grads_of(mod, {"x": x}, w)
+            assert got["x"].shape == x.shape and all(t is not None for t in got.values())
+            res.append([t.clone() for t in got.values()])
         assert all(torch.equal(a, b) for a, b in zip(*res))
         assert all(torch.isfinite(t).all() and t.abs().max() > 0 for t in res[0])

@@ -1,16 +1,12 @@
 """rf_pair_softmax_bwd and rf_sym_layernorm_bwd (csrc/backward.hip): the two kernels the backward of MsaUpdateWithPair adds, in
 both builds.
 
-Each is held against float64 autograd of a restatement of the forward on the same operands, by the rule of
-tests/test_dist_attention_bwd_gpu.py: the ceiling of an output is MARGIN = 4 times a yardstick measured at run time, the larger
-of (a) the error of torch's own float32 autograd of the same restatement on the same operands against the float64 result and
-(b) 2^-24, the rounding unit of the fp32 outputs.  Relative L2 error of the whole tensor and of the worst row -- one (b, i, z)
-softmax row of dz, one (b, i, j) channel row of d pair.  A row whose float64 gradient is exactly zero must be exactly zero.
+Each is held against float64 autograd of a restatement of the forward on the same operands, by the yardstick rule of
+tests/grad_oracle.py, with 2^-24, the rounding unit of the fp32 outputs.  A row is one (b, i, z) softmax row of dz, one (b, i, j)
+channel row of d pair.
 
 RF_MSA_PAIR_BACKWARD_ERRORS=FILE: the measured errors are also merged into that JSON file (key "kernel_errors")."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -19,6 +15,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 
@@ -32,31 +29,12 @@ SOFTMAX_SHAPES = [(2, 1, 4), (1, 5, 4), (2, 24, 16), (1, 63, 12), (1, 65, 5), (1
 # last with w (64 x 1024 x 4 bytes) read from memory instead of LDS.
 SYM_SHAPES = [(2, 1, 32, 4), (1, 2, 32, 8), (2, 5, 72, 12), (1, 33, 288, 16), (1, 8, 288, 4), (1, 3, 520, 4), (1, 3, 1024, 64)]
 BUILDS = [("bf16-build", torch.bfloat16), ("f16-build", torch.float16)]
-UNIT = 2.0 ** -24
-MARGIN = 4.0
 SENTINEL = 7.0
 EPS = 1e-5
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_MSA_PAIR_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, 2^-24)", "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+HELD = dict(units=G.UNIT[torch.float32], rows=1, records=RECORDS, key="out")
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_MSA_PAIR_BACKWARD_ERRORS", RECORDS, "max(torch float32 autograd vs float64, 2^-24)")
 
 
 @pytest.fixture(params=BUILDS, ids=[b[0] for b in BUILDS])
@@ -66,41 +44,13 @@ def build(request):
     return request.param[1]
 
 
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def errors(got, want):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one row: the last dimension).  A row that is exactly
-    zero in `want` must be exactly zero in `got` (infinite error otherwise)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    num, den = (g - w).norm(dim=-1), w.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    if w.norm() > 0:
-        return ((g - w).norm() / w.norm()).item(), rows.max().item()
-    return (float("inf") if (g != 0).any() else 0.0), rows.max().item()
-
-
-def held(got, ref64, ref32, tag, out):
-    """the output under MARGIN x its yardstick, whole tensor and worst row; prints and records the figures"""
-    m_all, m_row = errors(got, ref64)
-    y_all, y_row = errors(ref32, ref64)
-    c_all, c_row = MARGIN * max(y_all, UNIT), MARGIN * max(y_row, UNIT)
-    print(f"{tag} {out}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, ceiling {c_all:.3e}), "
-          f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-    RECORDS.append(dict(case=tag, out=out, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                        unit=UNIT, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-    return m_all <= c_all and m_row <= c_row
-
-
 # ================================================================================================ rf_pair_softmax_bwd
 @functools.lru_cache(maxsize=None)
 def softmax_case(shape):
     """One set of operands per shape, shared and left unchanged: logits [B,L,L,NZ] normal with a standard deviation of 3, the
     maps' gradient [NZ,B,L,L]."""
     B, L, NZ = shape
-    g_ = gen(5100 + 7 * L + NZ)
+    g_ = G.gen(5100 + 7 * L + NZ)
     logits = torch.randn(B, L, L, NZ, generator=g_) * 3
     datt = torch.randn(NZ, B, L, L, generator=g_)
     return dict(logits=logits.to(DEV), datt=datt.to(DEV))
@@ -144,13 +94,13 @@ def test_softmax_bwd_against_float64_autograd(shape, build):
     c = softmax_case(shape)
     ref64, ref32 = softmax_refs(shape)
     dz, _ = run_softmax_bwd(c["logits"], c["datt"])
-    assert held(dz.permute(0, 1, 3, 2), ref64, ref32, f"{build} pair_softmax_bwd {shape}", "dz")
+    assert G.held({"dz": dz.permute(0, 1, 3, 2)}, {"dz": ref64}, {"dz": ref32}, f"{build} pair_softmax_bwd {shape}", **HELD)
     assert torch.equal(ops.pair_softmax_bwd(c["logits"], c["datt"])[0], dz)   # the wrapper: the same bits
     if L == 1:
         assert (dz == 0).all()
     else:   # the check has teeth: the gradient of the transposed maps must fail it
         wrong, _ = run_softmax_bwd(c["logits"], c["datt"].transpose(-1, -2).contiguous())
-        assert not held(wrong.permute(0, 1, 3, 2), ref64, ref32, "(transposed datt: must fail)", "dz")
+        assert not G.held({"dz": wrong.permute(0, 1, 3, 2)}, {"dz": ref64}, {"dz": ref32}, "(transposed datt: must fail)", **HELD)
         del RECORDS[-1]
 
 
@@ -218,7 +168,7 @@ def test_softmax_bwd_is_deterministic_and_refuses_before_a_launch(build):
 def sym_case(shape):
     """pair [B,L,L,D] with a per-channel offset and scale (so that the statistics matter), the folded weight [NZ,D], dz"""
     B, L, D, NZ = shape
-    g_ = gen(6100 + 11 * L + D + NZ)
+    g_ = G.gen(6100 + 11 * L + D + NZ)
     pair = torch.randn(B, L, L, D, generator=g_) * (1 + torch.rand(D, generator=g_)) + torch.randn(D, generator=g_)
     w = torch.randn(NZ, D, generator=g_) * D ** -0.5
     dz = torch.randn(B, L, L, NZ, generator=g_)
@@ -257,14 +207,15 @@ def test_sym_layernorm_bwd_against_float64_autograd(shape, build):
     c = sym_case(shape)
     ref64, ref32 = sym_refs(shape)
     got = run_sym_bwd(c)
-    assert held(got, ref64, ref32, f"{build} sym_layernorm_bwd {shape}", "dpair")
+    ref64, ref32 = {"dpair": ref64}, {"dpair": ref32}
+    assert G.held({"dpair": got}, ref64, ref32, f"{build} sym_layernorm_bwd {shape}", **HELD)
     assert torch.equal(got, got.transpose(1, 2))                       # dpair[b,i,j] == dpair[b,j,i] bit for bit
     assert torch.equal(run_sym_bwd(c), got)                            # and the same bits on a second run
     assert torch.equal(ops.sym_layernorm_bwd(c["pair"], c["dz"], c["w"], eps=EPS), got)
     # the check has teeth: without the second row of dz (g = dz_ij . w alone) it must fail
     if shape[1] > 1:
         lower = torch.tril(torch.ones(shape[1], shape[1], device=DEV))[None, :, :, None]
-        assert not held(run_sym_bwd(dict(c, dz=c["dz"] * lower)), ref64, ref32, "(half of dz: must fail)", "dpair")
+        assert not G.held({"dpair": run_sym_bwd(dict(c, dz=c["dz"] * lower))}, ref64, ref32, "(half of dz: must fail)", **HELD)
         del RECORDS[-1]
 
 

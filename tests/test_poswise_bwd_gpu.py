@@ -1,18 +1,13 @@
 """rf_poswise_bwd (csrc/backward.hip): the backward of rf_poswise, alone (the direct form, any number of heads) and with
 rf_weighted_msa_sum fused behind it (the collapsed one-head form of the structure track's node input).
 
-The kernel is held against float64 autograd of a restatement of the forward on the operands as rounded, by the rule of
-tests/test_graph_backward_gpu.py: the ceiling of each output is MARGIN = 4 times a yardstick measured at run time, the larger
-of (a) the error of torch's own float32 autograd of the same restatement on the same operands against the float64 result and
-(b) the rounding unit of the output's storage type (2^-24 for the fp32 dq0 and an fp32 dk; the 16-bit type's unit for a 16-bit
-dk).  Relative L2 error of the whole tensor and of the worst (b, l) row -- one softmax over the MSA depth each; the margin is 4
-because a depth of two or three averages no rounding error away.  A row whose float64 gradient is exactly zero (all of dq0 at
-N = 1) must be exactly zero.
+The kernel is held against float64 autograd of a restatement of the forward on the operands as rounded, by the yardstick rule
+of tests/grad_oracle.py.  The units are 2^-24 for the fp32 dq0 and an fp32 dk, the 16-bit type's unit for a 16-bit dk.  A row is
+one (b, l) -- one softmax over the MSA depth each (for dk: every n of it); the margin is 4 because a depth of two or three
+averages no rounding error away.  A row whose float64 gradient is exactly zero (all of dq0 at N = 1) must be exactly zero.
 
 RF_INITIAL_COORD_BACKWARD_ERRORS=FILE: the measured errors are also merged into that JSON file (key "kernel_errors")."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -21,6 +16,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 
@@ -36,41 +32,20 @@ SHAPES = [("direct", (2, 1, 5, 3, 8)), ("direct", (1, 2, 7, 1, 8)), ("direct", (
 OPERANDS = [("fp32", torch.bfloat16, torch.float32), ("bf16", torch.bfloat16, torch.bfloat16),
             ("fp16", torch.float16, torch.float16)]
 OP_DTYPE = {o[0]: o[2] for o in OPERANDS}
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-MARGIN = 4.0
 NAMES = ("dq0", "dk")
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_INITIAL_COORD_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, unit of the storage type)",
-                                "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+# dk's storage type -> the units of (dq0, dk); a row is every n of one (b, l)
+UNITS = {dt: {"dq0": G.UNIT[torch.float32], "dk": G.UNIT[dt]} for dt in G.UNIT}
+HELD = dict(rows="bl", records=RECORDS)
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_INITIAL_COORD_BACKWARD_ERRORS", RECORDS,
+                                   "max(torch float32 autograd vs float64, unit of the storage type)")
 
 
 @pytest.fixture(params=OPERANDS, ids=[o[0] for o in OPERANDS])
 def operand(request):
     R.set_compute_dtype(request.param[1])
     return request.param
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 # ---- the forward, restated (any floating type; differentiable) -------------------------------------------------------------------
@@ -100,19 +75,6 @@ def autograd(c, dtype, keep=None, p=0.0):
     return {"dq0": q0.grad, "dk": k.grad}
 
 
-def errors(got, want):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one (b, l) row).  A row that is exactly zero in `want`
-    must be exactly zero in `got` (infinite error otherwise).  dq0 [B, L, *]; dk [B, N, L, *]: a row is every n of one (b, l)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    if g.dim() == 4:
-        g, w = g.permute(0, 2, 1, 3), w.permute(0, 2, 1, 3)
-    gr, wr = g.reshape(g.shape[0] * g.shape[1], -1), w.reshape(g.shape[0] * g.shape[1], -1)
-    num, den = (gr - wr).norm(dim=-1), wr.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    return ((g - w).norm() / w.norm().clamp_min(1e-300)).item(), rows.max().item()
-
-
 @functools.lru_cache(maxsize=None)
 def case(form, shape, op_id):
     """One set of operands per (form, shape, operand type), shared by the tests below and left unchanged.  Direct: q0 and k of
@@ -120,7 +82,7 @@ def case(form, shape, op_id):
     operand type, ds, and an fp32 dk (what the node input asks for)."""
     B, N, L, H, dlen = shape
     dt = OP_DTYPE[op_id]
-    g_ = gen(3000 + 7 * N + dlen)
+    g_ = G.gen(3000 + 7 * N + dlen)
     k = torch.randn(B, N, L, H * dlen, generator=g_).to(dt).to(DEV)
     q0 = torch.randn(B, L, H * dlen, generator=g_).to(dt if form == "direct" else torch.float32).to(DEV)
     dw = torch.randn(B, N, H, L, generator=g_).to(DEV) if form == "direct" else None
@@ -154,22 +116,6 @@ def run_bwd(c, dropout=None, **over):
     return {"dq0": dq0, "dk": dk}
 
 
-def held(got, ref64, ref32, dk_dtype, tag):
-    """both gradients under MARGIN x their yardstick, whole tensor and worst row; prints and records the figures"""
-    ok = True
-    for n in NAMES:
-        unit = UNIT[dk_dtype if n == "dk" else torch.float32]
-        m_all, m_row = errors(got[n], ref64[n])
-        y_all, y_row = errors(ref32[n], ref64[n])
-        c_all, c_row = MARGIN * max(y_all, unit), MARGIN * max(y_row, unit)
-        print(f"{tag} {n}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, unit {unit:.1e}, ceiling {c_all:.3e}), "
-              f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-        RECORDS.append(dict(case=tag, grad=n, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                            unit=unit, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-        ok = ok and m_all <= c_all and m_row <= c_row
-    return ok
-
-
 # ---- 1. the kernel against float64 autograd ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("form,shape", SHAPES, ids=[f"{f}-{s}" for f, s in SHAPES])
 def test_kernel_against_float64_autograd(form, shape, operand):
@@ -178,10 +124,11 @@ def test_kernel_against_float64_autograd(form, shape, operand):
     got = run_bwd(c)
     assert got["dq0"].dtype == torch.float32 and got["dk"].dtype == c["dk_dtype"]
     assert got["dq0"].shape == c["q0"].shape and got["dk"].shape == c["k"].shape
-    assert held(got, ref64, ref32, c["dk_dtype"], f"{operand[0]} {form} {shape}")
+    assert G.held(got, ref64, ref32, f"{operand[0]} {form} {shape}", UNITS[c["dk_dtype"]], **HELD)
     if shape[1] > 1:   # the check has teeth: the weights' gradient with two MSA rows swapped must fail it
         swap = {n: None if c[n] is None else c[n].flip(1 if n == "dw" else 2).contiguous() for n in ("dw", "ds")}
-        assert not held(run_bwd(c, **swap), ref64, ref32, c["dk_dtype"], f"{operand[0]} {form} {shape} (flipped gradient: must fail)")
+        assert not G.held(run_bwd(c, **swap), ref64, ref32, f"{operand[0]} {form} {shape} (flipped gradient: must fail)",
+                          UNITS[c["dk_dtype"]], **HELD)
         del RECORDS[-len(NAMES):]
 
 
@@ -202,7 +149,7 @@ def test_depth_one_gives_exact_zeros(form, shape, operand):
     assert (dropped["dq0"] == 0).all()
     if form == "fused":   # wd = keep / (1 - p)
         want = c["ds"][:, None] * (keep[:, :, 0, :, None].float() / (1.0 - p))
-        torch.testing.assert_close(dropped["dk"], want, rtol=2 * UNIT[torch.float32], atol=0.0)
+        torch.testing.assert_close(dropped["dk"], want, rtol=2 * G.UNIT[torch.float32], atol=0.0)
         assert (dropped["dk"][~keep[:, :, 0]] == 0).all()
 
 
@@ -212,9 +159,10 @@ def test_both_gradients_add_and_strided_addressing_gives_the_same_bits(operand):
     dt = operand[2]
     shape = (1, 3, 7, 1, 24)
     c = dict(case("fused", shape, operand[0]))
-    c["dw"] = torch.randn(1, 3, 1, 7, generator=gen(5)).to(DEV)
+    c["dw"] = torch.randn(1, 3, 1, 7, generator=G.gen(5)).to(DEV)
     got = run_bwd(c)
-    assert held(got, autograd(c, torch.float64), autograd(c, torch.float32), c["dk_dtype"], f"{operand[0]} fused+dw {shape}")
+    assert G.held(got, autograd(c, torch.float64), autograd(c, torch.float32), f"{operand[0]} fused+dw {shape}", UNITS[c["dk_dtype"]],
+                  **HELD)
     del RECORDS[-len(NAMES):]
     B, N, L, H, dlen = shape = (2, 3, 5, 12, 32)
     c = case("direct", shape, operand[0])
@@ -234,7 +182,8 @@ def test_both_gradients_add_and_strided_addressing_gives_the_same_bits(operand):
     dq0b, _ = ops.poswise_bwd(c["q0"], HD, kbuf2, ld, 3, dlen, dlen, B, N, L, H, c["scale"], dw=c["dw"], dk=dkbuf2, dk_ld=ld,
                               dk_col0=5, dk_hs=dlen)
     ref64, ref32 = refs("direct", shape, operand[0])
-    assert held({"dq0": dq0b, "dk": dkbuf2[..., 5:5 + HD]}, ref64, ref32, dt, f"{operand[0]} direct {shape} (scalar path)")
+    assert G.held({"dq0": dq0b, "dk": dkbuf2[..., 5:5 + HD]}, ref64, ref32, f"{operand[0]} direct {shape} (scalar path)", UNITS[dt],
+                  **HELD)
     del RECORDS[-len(NAMES):]
     assert (dkbuf2[..., :5] == 7).all() and (dkbuf2[..., 5 + HD:] == 7).all()
 
@@ -246,13 +195,13 @@ def test_dropout_replay(form, shape, operand):
     c = case(form, shape, operand[0])
     ref64, ref32 = refs(form, shape, operand[0], drop)
     got = run_bwd(c, dropout=drop)
-    assert held(got, ref64, ref32, c["dk_dtype"], f"{operand[0]} {form} {shape} dropout={drop[0]}")
+    assert G.held(got, ref64, ref32, f"{operand[0]} {form} {shape} dropout={drop[0]}", UNITS[c["dk_dtype"]], **HELD)
     again = run_bwd(c, dropout=drop)
     other = run_bwd(c, dropout=(drop[0], drop[1] + 1, drop[2]))
     for n in NAMES:
         assert torch.equal(got[n], again[n]) and not torch.equal(got[n], other[n]), n
     plain64, _ = refs(form, shape, operand[0])      # and the dropout matters: the reference without it is far away
-    assert errors(got["dk"], plain64["dk"])[0] > 0.1
+    assert G.errors(got["dk"], plain64["dk"], "bl")[0] > 0.1
 
 
 # ---- 4. determinism and refusals -------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
 import rowops_oracle as O  # noqa: E402
+from grad_oracle import h16  # noqa: E402,F401  (the fixture: both 16-bit builds)
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import ops, _lib as L  # noqa: E402
 
@@ -25,13 +26,6 @@ F32, F64 = torch.float32, torch.float64
 P = ops.ptr
 EINVAL, EALIGN = -1, -2
 INFO = {}  # measurements that are recorded, not asserted (the InstanceNorm sweep, the model's mean/sigma)
-
-
-@pytest.fixture(params=[torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
-def h16(request):
-    R.set_compute_dtype(request.param)
-    yield request.param
-    R.set_compute_dtype(torch.bfloat16)
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -3,8 +3,9 @@ CPU oracle (oracle/rf_oracle.py: soft_tied_attention) in the three compute modes
 call (attend(tape=) + _backward), unchanged forward numbers, dropout replay in both mask orders, fp16 small losses, determinism
 and the refusals.
 
-The helpers and ceilings are those of tests/test_axial_backward_gpu.py, restated here: relative L2 error of a whole gradient
-under CEIL (1e-4 fp32, 1e-2 fp16, 5e-2 bf16).  The function has no kinks, so no kink floor is added.
+The gradients are held by the ceiling-or-kink-floor rule of tests/grad_oracle.py; the function has no kinks, so no kink floor
+is added.  Both to_k biases add a constant to every logit of a softmax row: exact zeros here, rounding noise in the oracle.  With
+one of the two outputs out of the loss some parameters are not reached: no gradient in the oracle, exact zeros here.
 
 Routes (model.SoftTiedAttentionOverResidues.attend): every fused route needs the 16-bit modes and d_head = 32.  d_msa 32 with
 two heads (d_head 16) therefore stays on the general route (rf_gemm + rf_tied_softmax) at every length, in every mode; d_msa 64
@@ -21,13 +22,13 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 
 DEV = "cuda"
-MODES = [torch.float32, torch.bfloat16, torch.float16]
-CEIL = {torch.float32: 1e-4, torch.float16: 1e-2, torch.bfloat16: 5e-2}
+MODES, CEIL = G.MODES, G.CEIL
 LOSSES = ("both", "out", "att")
 # (B, N, L, D, H).  D = 32, H = 2: L = 1, no multiple of 8 (20, 100), the ragged route's shortest chain (40) and a full tile (64),
 # with 3 and 16 MSA rows and one or two samples -- the general route throughout (d_head 16)
@@ -39,43 +40,9 @@ HEAD_MAJOR = (16, 16, 64, 64, 2)     # 16384 positions: the head-major route, th
 FOLD = (16, 16, 64, 384, 12)         # ... and at the model's width, folded into the q projection (ops.gemm_takes_row_scale)
 
 
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-def rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-300)).item()
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def randomize(mod, seed):
-    """non-trivial LayerNorm affines and biases (the defaults 1 / 0 would hide their gradients' mistakes)"""
-    g = gen(seed)
-    with torch.no_grad():
-        for name, p in mod.named_parameters():
-            if p.dim() == 1:
-                p.copy_((torch.randn(p.shape, generator=g) * 0.1 + (1.0 if "fn.0.weight" in name else 0.0)).to(p.device))
-    return mod
-
-
-def state(mod, pre):
-    return {f"{pre}.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}
-
-
-def oracle_grads(fn, P, x):
-    """float64 autograd of the scalar fn(P, x): {"x": d/dx, name: d/dP[name]}"""
-    P = {k: v.detach().clone().requires_grad_() for k, v in P.items()}
-    xd = x.detach().double().cpu().clone().requires_grad_()
-    fn(P, xd).backward()
-    out = {k: v.grad for k, v in P.items() if v.grad is not None}
-    out["x"] = xd.grad
-    return out
+CENTRED = lambda name: "fn.0.weight" in name   # noqa: E731  the 1-D parameters drawn around 1
+ZERO_BIASES = ("m.to_k.bias", "m.poswise_weight.to_k.0.bias")
+_restore_mode = G.restore_mode()
 
 
 def loss_of(out, att, w_o, w_a, kind):
@@ -93,8 +60,8 @@ def setup(shape, p_dropout=0.0):
     """module (fp32 weights, CPU, return_att=True), input and the two outputs' weights; shared by the modes and left unchanged"""
     B, N, L, D, H = shape
     torch.manual_seed(100 + L + D)
-    mod = randomize(R.SoftTiedAttentionOverResidues(D, H, p_dropout=p_dropout, return_att=True), 200 + L)
-    g = gen(300 + L + N)
+    mod = G.randomize(R.SoftTiedAttentionOverResidues(D, H, p_dropout=p_dropout, return_att=True), 200 + L, CENTRED)
+    g = G.gen(300 + L + N)
     return mod, torch.randn(B, N, L, D, generator=g), torch.randn(B, N, L, D, generator=g), torch.randn(B, L, L, H, generator=g)
 
 
@@ -103,10 +70,12 @@ def reference(shape, kind):
     mod, x, w_o, w_a = setup(shape)
     H = shape[4]
 
-    def fn(P, xd):
-        out, att = O.soft_tied_attention(P, "m", xd, H)
-        return loss_of(out, att, w_o.double(), w_a.double(), kind)
-    return oracle_grads(fn, state(mod, "m"), x)
+    return oracle(lambda P, xd: O.soft_tied_attention(P, "m", xd, H), mod, x, w_o, w_a, kind)
+
+
+def oracle(fn, mod, x, w_o, w_a, kind):
+    """float64 autograd of loss_of(*fn(P, x), ..): {"x", "m." + name: gradient}"""
+    return G.oracle_grads(fn, G.state(mod), {"x": x}, lambda o: loss_of(*o, w_o.double(), w_a.double(), kind))[0]
 
 
 def head_major_ran():
@@ -117,47 +86,30 @@ def head_major_ran():
 
 def module_grads(mod, x, w_o, w_a, kind, scale=1.0, route=None):
     """loss.backward() through the public forward on the device: {"x", "m." + name: gradient}"""
-    for p in mod.parameters():
-        p.grad = None
-    xg = x.to(DEV).requires_grad_()
-    out, att = mod(xg)
-    if route:   # (the other routes launch no kernel that leaves a code: nothing to assert there)
-        assert head_major_ran(), _lib.lib.rf_attn_last_route()
-    assert out.requires_grad and att.requires_grad
-    (loss_of(out, att, w_o.to(DEV), w_a.to(DEV), kind) * scale).backward()
-    return dict({"m." + n: p.grad for n, p in mod.named_parameters()}, x=xg.grad)
+    def loss(o):
+        if route:   # (the other routes launch no kernel that leaves a code: nothing to assert there)
+            assert head_major_ran(), _lib.lib.rf_attn_last_route()
+        assert o[0].requires_grad and o[1].requires_grad
+        return loss_of(*o, w_o.to(DEV), w_a.to(DEV), kind)
+    return G.grads_of(mod, {"x": x}, loss, scale)[0]
 
 
 def compare(got, ref, dtype, tag):
-    assert set(ref) <= set(got)
-    for key in set(got) - set(ref):     # a parameter the loss does not depend on: no gradient in the oracle, exact zeros here
-        assert (got[key] == 0).all(), key
-    bad = {}
-    for key in ref:
-        if key in ("m.to_k.bias", "m.poswise_weight.to_k.0.bias"):
-            # a constant added to every logit of a softmax row: an exact zero here, rounding noise in the oracle
-            weight = ref[key.replace("bias", "weight")]
-            assert (got[key] == 0).all(), key
-            assert ref[key].norm() < 1e-10 * weight.norm() or weight.norm() == 0, (key, ref[key].norm(), weight.norm())
-            continue
-        err = rel(got[key], ref[key])
-        print(f"{dtype} {tag} {key}: rel-L2 {err:.3e} (ceiling {CEIL[dtype]:.0e})")
-        if not err < CEIL[dtype]:
-            bad[key] = err
-    assert not bad, (tag, bad)
+    """the to_k biases: exact zeros, the oracle's own value below 1e-10 of the weight's gradient (or that weight unreached too)"""
+    zero = {}
+    for key in set(ZERO_BIASES) & set(ref):
+        weight = ref[key.replace("bias", "weight")].norm()
+        zero[key] = 1e-10 * weight if weight > 0 else float("inf")
+    G.compare(got, ref, dtype, tag, zero=zero, unreached_zero=True)
 
 
 def check_against_oracle(shape, dtype, kinds=LOSSES, route=None):
     R.set_compute_dtype(dtype)
     mod, x, w_o, w_a = setup(shape)
-    mod = mod.to(DEV).enable_backward()
-    try:
+    with G.recording(mod):
         for kind in kinds:
             got = module_grads(mod, x, w_o, w_a, kind, route=route if ops.is_h16(dtype) else False)
             compare(got, reference(shape, kind), dtype, f"{shape} loss={kind}")
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
 
 
 # ------------------------------------------------------------------------------------------------ against the oracle
@@ -326,14 +278,11 @@ def test_dropout_masks_are_replayed_in_the_order_the_forward_drew_them(dtype, sh
         out_drops = tuple((keep_map((B, N, L, D), r), r[0]) for r in tape["drops"])
 
         def fn(keep):
-            def f(P, xd):
-                o, a = restated(P, xd, H, keep, rec[0], out_drops)
-                return loss_of(o, a, w_o.double(), w_a.double(), "both")
-            return f
-        ref = oracle_grads(fn(keep_w), state(mod, "m"), x)
+            return lambda P, xd: restated(P, xd, H, keep, rec[0], out_drops)
+        ref = oracle(fn(keep_w), mod, x, w_o, w_a, "both")
         compare(got, ref, dtype, f"{shape} train, {order}")
-        wrong = oracle_grads(fn(other), state(mod, "m"), x)
-        assert rel(got["x"], wrong["x"]) > 10 * CEIL[dtype]
+        wrong = oracle(fn(other), mod, x, w_o, w_a, "both")
+        assert G.rel(got["x"], wrong["x"]) > 10 * CEIL[dtype]
     finally:
         mod.eval()
         mod.to("cpu")
@@ -346,9 +295,7 @@ def test_dropout_replay_finite_differences():
     R.set_compute_dtype(torch.float32)
     shape = (1, 3, 20, 32, 2)
     mod, x, w_o, w_a = setup(shape, 0.25)
-    mod = mod.to(DEV)
-    try:
-        mod.train().enable_backward()
+    with G.recording(mod, train=True):
         x, w_o, w_a = (t.to(DEV) for t in (x, w_o, w_a))
 
         def loss(xx):
@@ -364,7 +311,7 @@ def test_dropout_replay_finite_differences():
             p.grad = None
         xg = x.clone().requires_grad_()
         loss(xg).backward()
-        g = gen(31)
+        g = G.gen(31)
         eps = 3e-2   # (the function is smooth: the step only has to stay well above the fp32 loss noise, ~1e-5)
         v = torch.zeros(x.numel())
         v[torch.randperm(x.numel(), generator=g)[:8]] = torch.randn(8, generator=g)   # a few input elements
@@ -386,9 +333,6 @@ def test_dropout_replay_finite_differences():
                 wt.copy_(w0)
             an_w = (wt.grad * dw).sum().item()
             assert abs((lp - lm) / (2 * eps) - an_w) <= 2e-2 * abs(an_w) + 1e-3, ((lp - lm) / (2 * eps), an_w)
-    finally:
-        mod.eval().enable_backward(False)
-        mod.to("cpu")
 
 
 # ------------------------------------------------------------------------------------------------ fp16 small losses
@@ -396,20 +340,16 @@ def test_fp16_small_loss_does_not_underflow():
     R.set_compute_dtype(torch.float16)
     shape = (1, 16, 100, 64, 2)
     mod, x, w_o, w_a = setup(shape)
-    mod = mod.to(DEV).enable_backward()
-    try:
+    with G.recording(mod):
         res = [module_grads(mod, x, w_o, w_a, "both", scale=s) for s in (1.0, 1e-8)]
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
     for key, a in res[0].items():
         b = res[1][key]
         assert torch.isfinite(b).all(), key
-        if key in ("m.to_k.bias", "m.poswise_weight.to_k.0.bias"):
+        if key in ZERO_BIASES:
             assert (b == 0).all()
             continue
         assert b.abs().max() > 0, key
-        assert rel(b * 1e8, a) < CEIL[torch.float16], key
+        assert G.rel(b * 1e8, a) < CEIL[torch.float16], key
 
 
 # ------------------------------------------------------------------------------------------------ determinism
@@ -417,15 +357,11 @@ def test_fp16_small_loss_does_not_underflow():
 def test_backward_is_deterministic(shape):
     R.set_compute_dtype(torch.bfloat16)
     mod, x, w_o, w_a = setup(shape)
-    mod = mod.to(DEV).enable_backward()
-    try:
+    with G.recording(mod):
         res = []
         for _ in range(2):
             got = module_grads(mod, x, w_o, w_a, "both")
             res.append([got[k].clone() for k in sorted(got)])
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
     assert all(torch.equal(a, b) for a, b in zip(*res))
 
 
@@ -435,7 +371,7 @@ def test_channel_counts_checked_while_recording(D, H):
     R.set_compute_dtype(torch.float32)
     torch.manual_seed(7)
     mod = R.SoftTiedAttentionOverResidues(D, H, p_dropout=0.0).to(DEV)
-    x = torch.randn(1, 2, 8, D, generator=gen(7)).to(DEV)
+    x = torch.randn(1, 2, 8, D, generator=G.gen(7)).to(DEV)
     with torch.no_grad():
         plain = mod(x)   # fine for the forward
     mod.enable_backward()

@@ -19,12 +19,12 @@ if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
 import attn_oracle as A  # noqa: E402
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from oracle import rf_oracle as O  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 from rosettafold_pytorch_amd.runtime import RT  # noqa: E402
-from test_rowops_bound_gpu import h16  # noqa: E402,F401  (the fixture: both 16-bit builds)
-from test_tied_backward_gpu import compare as compare_grads, loss_of, oracle_grads, randomize  # noqa: E402
+from grad_oracle import h16  # noqa: E402,F401  (the fixture: both 16-bit builds)
 
 lib = _lib.lib
 DEV = "cuda"
@@ -328,41 +328,39 @@ BWD = (1, 64, 257, DM, NH)
 def bwd_setup(p_dropout=0.0):
     B, N, L, D, H = BWD
     torch.manual_seed(100 + L + D)
-    mod = randomize(R.SoftTiedAttentionOverResidues(D, H, p_dropout=p_dropout, return_att=True), 200 + L)
-    g = torch.Generator().manual_seed(300 + L + N)
+    mod = G.randomize(R.SoftTiedAttentionOverResidues(D, H, p_dropout=p_dropout, return_att=True), 200 + L,
+                      lambda name: "fn.0.weight" in name)
+    g = G.gen(300 + L + N)
     return mod, torch.randn(B, N, L, D, generator=g), torch.randn(B, N, L, D, generator=g), torch.randn(B, L, L, H, generator=g)
 
 
+def loss_of(o, w_o, w_a):
+    """sum(out * w_o) + sum(att * w_a)"""
+    return (o[0] * w_o).sum() + (o[1] * w_a).sum()
+
+
 def module_grads(mod, x, w_o, w_a):
-    for p in mod.parameters():
-        p.grad = None
-    xg = x.to(DEV).requires_grad_()
     before = ops.COUNTERS["tied_logits_long"]
-    out, att = mod(xg)
-    assert ops.COUNTERS["tied_logits_long"] - before == 1 and lib.rf_attn_last_route() == 222   # recorded on the long route
-    assert out.requires_grad and att.requires_grad
-    loss_of(out, att, w_o.to(DEV), w_a.to(DEV), "both").backward()
-    return dict({"m." + n: p.grad.clone() for n, p in mod.named_parameters()}, x=xg.grad.clone())
+
+    def loss(o):
+        assert ops.COUNTERS["tied_logits_long"] - before == 1 and lib.rf_attn_last_route() == 222   # recorded on the long route
+        assert o[0].requires_grad and o[1].requires_grad
+        return loss_of(o, w_o.to(DEV), w_a.to(DEV))
+    return {k: t.clone() for k, t in G.grads_of(mod, {"x": x}, loss)[0].items()}
 
 
 def test_recorded_backward_against_float64_autograd():
-    """enable_backward(), (N, L) = (64, 257), bf16: x and every parameter gradient under the ceilings of
-    tests/test_tied_backward_gpu.py (relative L2 of a whole gradient, 5e-2 in bfloat16)"""
+    """enable_backward(), (N, L) = (64, 257), bf16: x and every parameter gradient under the ceiling of tests/grad_oracle.py
+    (relative L2 of a whole gradient, 5e-2 in bfloat16; no kinks); both to_k biases exactly zero, as in
+    tests/test_tied_backward_gpu.py"""
     R.set_compute_dtype(torch.bfloat16)
     mod, x, w_o, w_a = bwd_setup()
-    H = BWD[4]
-
-    def fn(P_, xd):
-        out, att = O.soft_tied_attention(P_, "m", xd, H)
-        return loss_of(out, att, w_o.double(), w_a.double(), "both")
-    ref = oracle_grads(fn, {f"m.{k}": v.detach().double().cpu() for k, v in mod.state_dict().items()}, x)
-    mod = mod.to(DEV).enable_backward()
-    try:
+    ref, _ = G.oracle_grads(lambda P_, xd: O.soft_tied_attention(P_, "m", xd, BWD[4]), G.state(mod), {"x": x},
+                            lambda o: loss_of(o, w_o.double(), w_a.double()))
+    with G.recording(mod):
         got = module_grads(mod, x, w_o, w_a)
-    finally:
-        mod.enable_backward(False)
-        mod.to("cpu")
-    compare_grads(got, ref, torch.bfloat16, f"{BWD} long ragged")
+    zero = {k: 1e-10 * ref[k.replace("bias", "weight")].norm() for k in ("m.to_k.bias", "m.poswise_weight.to_k.0.bias")}
+    G.compare(got, ref, torch.bfloat16, f"{BWD} long ragged", zero=zero, unreached_zero=True)
 
 
 def test_recorded_backward_in_train_mode_repeats_bitwise():

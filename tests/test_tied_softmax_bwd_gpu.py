@@ -1,17 +1,13 @@
 """rf_tied_softmax_bwd and rf_scale_rows_bwd (csrc/backward.hip): the two kernels the backward of
 SoftTiedAttentionOverResidues adds, in both builds.
 
-Each is held against float64 autograd of a restatement of the forward on the same operands, by the rule of
-tests/test_poswise_bwd_gpu.py and tests/test_dist_attention_bwd_gpu.py: the ceiling of an output is MARGIN = 4 times a yardstick
-measured at run time, the larger of (a) the error of torch's own float32 autograd of the same restatement against the float64
-result and (b) the rounding unit of the output's storage type (2^-24 for fp32; the 16-bit type's unit for the 16-bit copies and
-a 16-bit dx).  Relative L2 error of the whole tensor and of the worst row -- one (b, h, i) softmax row of the map, one row of
-rf_scale_rows_bwd's dx; dw holds one number per row, so its worst row is its worst element.
+Each is held against float64 autograd of a restatement of the forward on the same operands, by the yardstick rule of
+tests/grad_oracle.py.  The units are 2^-24 for fp32 outputs, the 16-bit type's unit for the 16-bit copies and a 16-bit dx.  A row
+is one (b, h, i) softmax row of the map, one row of rf_scale_rows_bwd's dx; dw holds one number per row, so its worst row is its
+worst element.
 
 RF_TIED_BACKWARD_ERRORS=FILE: the measured errors are also merged into that JSON file (key "kernel_errors")."""
 import functools
-import json
-import os
 
 import pytest
 import torch
@@ -20,6 +16,7 @@ pytestmark = pytest.mark.gpu
 if not torch.cuda.is_available():
     pytest.skip("needs a GPU", allow_module_level=True)
 
+import grad_oracle as G  # noqa: E402
 import rosettafold_pytorch_amd as R  # noqa: E402
 from rosettafold_pytorch_amd import _lib, ops  # noqa: E402
 
@@ -28,68 +25,19 @@ DEV = "cuda"
 # that is no multiple of 8 (16-bit copies at ld = 104), and a row that crosses 256 threads
 SHAPES = [(2, 2, 1), (1, 3, 5), (1, 2, 63), (1, 5, 65), (1, 12, 100), (1, 2, 257)]
 BUILDS = [("bf16-build", torch.bfloat16), ("f16-build", torch.float16)]
-UNIT = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
-MARGIN = 4.0
+UNIT = G.UNIT
 SENTINEL = 7.0
 RECORDS = []
-
-
-@pytest.fixture(autouse=True)
-def _restore_mode():
-    yield
-    R.set_compute_dtype(torch.bfloat16)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _write_records():
-    yield
-    path = os.environ.get("RF_TIED_BACKWARD_ERRORS")
-    if path and RECORDS:
-        doc = {}
-        if os.path.exists(path):
-            with open(path) as fh:
-                doc = json.load(fh)
-        doc["kernel_errors"] = {"margin": MARGIN, "yardstick": "max(torch float32 autograd vs float64, unit of the storage type)",
-                                "cases": RECORDS}
-        with open(path, "w") as fh:
-            json.dump(doc, fh, indent=1)
+HELD = dict(rows=1, records=RECORDS, key="out")
+_restore_mode = G.restore_mode()
+_write_records = G.records_fixture("RF_TIED_BACKWARD_ERRORS", RECORDS,
+                                   "max(torch float32 autograd vs float64, unit of the storage type)")
 
 
 @pytest.fixture(params=BUILDS, ids=[b[0] for b in BUILDS])
 def build(request):
     R.set_compute_dtype(request.param[1])
     return request.param[1]
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def errors(got, want, row_dims):
-    """(relative L2 error of the whole tensor, worst relative L2 error of one row: the trailing row_dims dimensions).  A row that
-    is exactly zero in `want` must be exactly zero in `got` (infinite error otherwise)."""
-    g, w = got.detach().double().cpu(), want.double()
-    assert g.shape == w.shape and torch.isfinite(g).all()
-    lead = g.shape[:g.dim() - row_dims]
-    gr, wr = g.reshape(*lead, -1), w.reshape(*lead, -1)
-    num, den = (gr - wr).norm(dim=-1), wr.norm(dim=-1)
-    rows = torch.where(den > 0, num / den.clamp_min(1e-300), torch.where(num > 0, float("inf"), 0.0).double())
-    return ((g - w).norm() / w.norm().clamp_min(1e-300)).item(), rows.max().item()
-
-
-def held(got, ref64, ref32, units, row_dims, tag):
-    """every output under MARGIN x its yardstick, whole tensor and worst row; prints and records the figures"""
-    ok = True
-    for n, unit in units.items():
-        m_all, m_row = errors(got[n], ref64[n], row_dims[n])
-        y_all, y_row = errors(ref32[n], ref64[n], row_dims[n])
-        c_all, c_row = MARGIN * max(y_all, unit), MARGIN * max(y_row, unit)
-        print(f"{tag} {n}: rel-L2 {m_all:.3e} (float32 autograd {y_all:.3e}, unit {unit:.1e}, ceiling {c_all:.3e}), "
-              f"worst row {m_row:.3e} (float32 autograd {y_row:.3e}, ceiling {c_row:.3e})")
-        RECORDS.append(dict(case=tag, out=n, rel_l2=m_all, worst_row=m_row, f32_autograd_rel_l2=y_all, f32_autograd_worst_row=y_row,
-                            unit=unit, ceiling_rel_l2=c_all, ceiling_worst_row=c_row))
-        ok = ok and m_all <= c_all and m_row <= c_row
-    return ok
 
 
 # ================================================================================================ rf_tied_softmax_bwd
@@ -115,7 +63,7 @@ def softmax_case(shape, sym, shift=None):
     """One set of operands per (shape, with / without g_sym, shift), shared and left unchanged.  Logits are normal with a standard
     deviation of 3; shift "row": +80 on one whole row; "half": -80 on half of one row's entries."""
     B, H, L = shape
-    g_ = gen(4000 + 13 * L + H)
+    g_ = G.gen(4000 + 13 * L + H)
     logits = torch.randn(B, H, L, L, generator=g_) * 3
     if shift == "row":
         logits[0, H - 1, L // 2] += 80.0
@@ -165,12 +113,12 @@ def test_softmax_bwd_against_float64_autograd(shape, sym, build):
     refs64 = {"ds": ref64["ds"], "ds16": ref64["ds"], "p16": ref64["p"]}
     refs32 = {"ds": ref32["ds"], "ds16": ref32["ds"], "p16": ref32["p"]}
     units = {"ds": UNIT[torch.float32], "ds16": UNIT[build], "p16": UNIT[build]}
-    assert held(got, refs64, refs32, units, dict.fromkeys(units, 1), f"{build} tied_softmax_bwd {shape} sym={sym}")
+    assert G.held(got, refs64, refs32, f"{build} tied_softmax_bwd {shape} sym={sym}", units, **HELD)
     if shape[2] == 1:
         assert (got["ds"] == 0).all() and (got["ds16"].float() == 0).all() and (got["p16"].float() == 1).all()
     else:   # the check has teeth: the gradient of the transposed map must fail it
         wrong = dict(c, dp=c["dp"].transpose(-1, -2).contiguous())
-        assert not held(run_softmax_bwd(wrong), refs64, refs32, {"ds": units["ds"]}, {"ds": 1}, "(transposed dp: must fail)")
+        assert not G.held(run_softmax_bwd(wrong), {"ds": ref64["ds"]}, {"ds": ref32["ds"]}, "(transposed dp: must fail)", units, **HELD)
         del RECORDS[-1]
     alone = run_softmax_bwd(c, copies=False)     # without the 16-bit copies: the same fp32 bits
     assert torch.equal(alone["ds"], got["ds"])
@@ -186,13 +134,13 @@ def test_softmax_bwd_shifted_rows_stay_finite(shift, build):
     got = run_softmax_bwd(c)
     assert all(torch.isfinite(t.float()).all() for t in got.values())
     units = {"ds": UNIT[torch.float32]}
-    assert held(got, {"ds": ref64["ds"]}, {"ds": ref32["ds"]}, units, {"ds": 1}, f"{build} tied_softmax_bwd {shape} shift={shift}")
+    assert G.held(got, {"ds": ref64["ds"]}, {"ds": ref32["ds"]}, f"{build} tied_softmax_bwd {shape} shift={shift}", units, **HELD)
     # an entry whose float64 probability is below 1e-30 contributes nothing: |ds| there is below the yardstick's absolute size
     tiny = ref64["p"] < 1e-30
     if shift == "half":
         assert tiny.any()
-    y_all, _ = errors(ref32["ds"], ref64["ds"], 1)
-    floor = MARGIN * max(y_all, UNIT[torch.float32]) * ref64["ds"].abs().max().item()
+    y_all, _ = G.errors(ref32["ds"], ref64["ds"], 1)
+    floor = G.MARGIN * max(y_all, UNIT[torch.float32]) * ref64["ds"].abs().max().item()
     assert (got["ds"].cpu()[tiny].abs() <= floor).all()
 
 
@@ -235,7 +183,7 @@ def scale_autograd(c, dtype):
 
 @functools.lru_cache(maxsize=None)
 def scale_case(tokens, H, D, dt):
-    g_ = gen(5000 + tokens + D)
+    g_ = G.gen(5000 + tokens + D)
     x, gy = (torch.randn(tokens, H, D, generator=g_).to(dt).to(DEV) for _ in range(2))
     return dict(x=x, gy=gy, w=torch.randn(tokens, H, generator=g_).to(DEV), alpha=0.375)   # (a float32 number, not 1)
 
@@ -252,13 +200,13 @@ def test_scale_rows_bwd_against_float64_autograd(case, operand, build):
     got = {"dx": dx.view(tokens, H, D), "dw": dw.view(tokens, H, 1)}
     ref64, ref32 = ({"dx": r["dx"], "dw": r["dw"].unsqueeze(-1)} for r in (ref64, ref32))
     units = {"dx": UNIT[dt], "dw": UNIT[torch.float32]}
-    assert held(got, ref64, ref32, units, {"dx": 1, "dw": 1}, f"{build} scale_rows_bwd {case} {operand}")
+    assert G.held(got, ref64, ref32, f"{build} scale_rows_bwd {case} {operand}", units, **HELD)
     again = ops.scale_rows_bwd(c["x"], H * D, D, c["gy"], H * D, D, c["w"].view(-1), c["alpha"], tokens, H, D)
     assert torch.equal(again[0], dx) and torch.equal(again[1], dw)
     flipped = ops.scale_rows_bwd(c["x"], H * D, D, c["gy"].flip(-1).contiguous(), H * D, D, c["w"].view(-1), c["alpha"], tokens, H, D)
     if tokens > 1:   # the check has teeth
-        assert not held({"dx": flipped[0].view(tokens, H, D), "dw": flipped[1].view(tokens, H, 1)}, ref64, ref32, units,
-                        {"dx": 1, "dw": 1}, "(flipped gradient: must fail)")
+        assert not G.held({"dx": flipped[0].view(tokens, H, D), "dw": flipped[1].view(tokens, H, 1)}, ref64, ref32,
+                          "(flipped gradient: must fail)", units, **HELD)
         del RECORDS[-2:]
 
 
