@@ -827,6 +827,70 @@ int64_t rf_pair_axis_sums_ws_bytes(int B, int L, int D);
 int rf_pair_axis_sums(const float* g, const int64_t* aa_idx, float* rows, float* cols, float* dsep, float* dbias, int B, int L,
                       int D, void* workspace, int64_t ws_bytes, void* stream);
 
+/* ---- backward pass of the SE(3) node layers and of the graph attention (csrc/se3.hip; structure.py GNormBias, G1x1SE3,
+ * GAttentiveSelfInt, GMABSE3; ea/modules.py:328-473, 683-774) ------------------------------------------------------------------
+ * rf_version >= 22.  All tensors are fp32 in both builds (the structure track is fp32 in every compute mode).  Nothing of the
+ * forward is saved but its inputs.  The fp32 operands are widened to fp64, every sum (dot products, softmax normalisers, the sums
+ * over edges, channels and nodes) is an fp64 sum, and each result is rounded once.  No atomics: the same bits run to run.  EVERY
+ * addressed output element is written by the call.  The two contractions that are left (G1x1SE3's weight gradient and the Linear
+ * inside GAttentiveSelfInt) run on rf_gemm (RF_F32) and rf_conv_wgrad (RF_F32), which take any channel count in fp32.
+ *
+ * Backward of rf_se3_attention, with the forward's addressing: the same per-edge k0, k1, v0, v1, per-node q0, q1, dense eid map,
+ * heads, mk*, mv*, V, L and the same limit L <= 1024.  g0 / g1: the gradient of out0 / out1, rows g0_ld / g1_ld floats apart
+ * (0 = packed: mv0 / 3*mv1), so that it can be the leading channels of the GCat buffer's gradient.  Per (dst node, head), over the
+ * node's incoming edges e in the forward's order, on this head's channels of both degrees:
+ *   p_e  = softmax_e(<k_e, q_node> / sqrt(mk0 + 3 mk1))        recomputed in fp64, maximum subtracted
+ *   dv_e = p_e g_node          dp_e = <v_e, g_node>          S = sum_e p_e dp_e          dl_e = p_e (dp_e - S)
+ *   dk_e = dl_e q_node / sqrt(nfeat)                          dq_node = sum_e dl_e k_e / sqrt(nfeat)
+ * dk0, dk1, dv0, dv1 are per-edge like k and v, dq0, dq1 per-node like q (packed).  An edge has one dst: one wave owns each
+ * (edge, head) slice of dk / dv and each (node, head) slice of dq.  A node of in-degree 0 gets dq exactly 0; a node of in-degree
+ * 1 gets dk exactly 0 on that edge, dq exactly 0 and dv equal to g bit for bit.  Edge rows the eid map does not name (at or above
+ * the edge count) are not written.  A degree with mk = 0 (mv = 0) takes NULL pointers.
+ * RF_EINVAL before any launch: a NULL tensor of a present degree, a size <= 0, L > 1024, V % L != 0, a channel count that
+ * `heads` does not divide, a g_ld below its row. */
+int rf_se3_attention_bwd(const float* k0, const float* k1, const float* q0, const float* q1, const float* v0, const float* v1,
+                         const int32_t* eid, const float* g0, const float* g1, int64_t g0_ld, int64_t g1_ld, float* dk0, float* dk1,
+                         float* dq0, float* dq1, float* dv0, float* dv1, int heads, int mk0, int mk1, int mv0, int mv1, int V, int L,
+                         void* stream);
+/* Backward of rf_se3_norm_bias.  v, g (the gradient of y), dv: [V, m, 2 deg + 1]; bias, dbias: [m].  With n = max(|v|, 1e-12),
+ * t = relu(n + b_c), y = t v / n: where n + b_c > 0 (the forward's own fp32 test, so that both take the same side of the kink)
+ *   dv = (t / n) g + (1 / n - t / n^2) (<v, g> / n) v        (the second term absent where |v| < 1e-12: n is a constant there)
+ *   dbias[c] = sum over the nodes of <v, g> / n
+ * and elsewhere dv and the node's term of dbias are exactly 0.  A thread owns one (node, channel); the terms of dbias go to the
+ * workspace (fp64, rf_se3_norm_bias_bwd_ws_bytes bytes, 8-byte aligned; 0 for an empty problem) and one block per channel adds
+ * them in a fixed order.  RF_EINVAL before any launch: a NULL tensor or workspace, a size <= 0, a workspace too small. */
+int64_t rf_se3_norm_bias_bwd_ws_bytes(int64_t V, int m, int deg);
+int rf_se3_norm_bias_bwd(const float* v, const float* bias, const float* g, float* dv, float* dbias, int64_t V, int m, int deg,
+                         void* workspace, int64_t ws_bytes, void* stream);
+/* Backward of rf_se3_gram.  v, dv: [V, m, 2 deg + 1]; ds: [V, m*m], the gradient of s:
+ *   dv_a (+)= sum_b (ds[a,b] + ds[b,a]) [|<v_a, v_b>| >= 1e-12] v_b
+ * The bracket is the clamp's derivative, decided by the forward's own fp32 product.  accumulate != 0: added (in fp64, one rounding)
+ * to what dv holds -- GAttentiveSelfInt reads v twice, and dv already carries rf_se3_attn_apply_bwd's dx.  A thread owns one
+ * (node, a).  deg is 0 or 1.  RF_EINVAL before any launch: a NULL tensor, a size <= 0, deg outside [0, 1]. */
+int rf_se3_gram_bwd(const float* v, const float* ds, float* dv, int accumulate, int64_t V, int m, int deg, void* stream);
+/* Backward of rf_se3_attn_apply.  att, datt: [V, m_out*m_in]; x, dx: [V, m_in, 2 deg + 1]; g: [V, m_out, 2 deg + 1], the gradient
+ * of y.  Per node, with p = softmax_m(att[n,o,:]) recomputed in fp64:
+ *   datt[n,o,m] = p_m (<g[n,o,:], x[n,m,:]> - sum_l p_l <g[n,o,:], x[n,l,:]>)          dx[n,m,:] = sum_o p[o,m] g[n,o,:]
+ * A block owns one node and keeps its probabilities in m_out * m_in * 8 bytes of LDS: the sum over o never leaves the block.
+ * RF_EINVAL before any launch: a NULL tensor, a size <= 0, deg outside [0, 1], more than 64 KB of LDS (m_out * m_in > 8192). */
+int rf_se3_attn_apply_bwd(const float* att, const float* x, const float* g, float* datt, float* dx, int64_t V, int m_out, int m_in,
+                          int deg, void* stream);
+/* Backward of rf_layernorm followed by act = RF_ACT_LEAKY (slope 0.01) or RF_ACT_NONE, at ANY D >= 1 (rf_layernorm_bwd stops at
+ * 1024; GAttentiveSelfInt normalises m_in^2 values: 361, 2304).  x (the forward's input), g (the gradient of the activation's
+ * output), dx: fp32 [rows, D], contiguous; gamma, beta, dgamma, dbeta: fp32 [D].  Mean and rstd are recomputed two-pass in fp64:
+ *   ge = g * (act == RF_ACT_LEAKY && gamma xhat + beta <= 0 ? 0.01 : 1)       (the gate from these fp64 statistics, not from the
+ *                                                                               forward's fp32 output: an output within fp32
+ *                                                                               rounding distance of 0 may take the other side)
+ *   dx = rstd * (ge gamma - mean(ge gamma) - xhat * mean(ge gamma xhat))       dgamma[c] = sum_rows ge xhat,  dbeta[c] = sum_rows ge
+ * A block per row with a strided loop writes dx and the row's statistics; a thread per column sums chunks of 64 rows into fp64
+ * partials, which a last launch adds in chunk order.  dgamma or dbeta may be NULL (both: dx only).  Workspace (8-byte aligned):
+ * rf_layernorm_act_bwd_ws_bytes bytes (0 for an empty problem).
+ * RF_EINVAL before any launch: a NULL tensor or workspace, a size <= 0, another activation, rows > 64 * 65535, a workspace too
+ * small. */
+int64_t rf_layernorm_act_bwd_ws_bytes(int64_t rows, int D);
+int rf_layernorm_act_bwd(const float* x, const float* g, const float* gamma, const float* beta, float eps, int act, float* dx,
+                         float* dgamma, float* dbeta, int64_t rows, int D, void* workspace, int64_t ws_bytes, void* stream);
+
 /* Library self-description */
 /* Timing experiments only: when buf is non-null every bf16 rf_gemm workgroup records 8 x uint64 phase stamps into it. */
 int rf_debug_gemm_stamps(void* buf);

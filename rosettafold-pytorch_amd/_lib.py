@@ -134,6 +134,14 @@ PROTOTYPES = {
     "rf_embedding_bwd": [vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, u64, u64, vp, i64, vp],
     "rf_pair_axis_sums_ws_bytes": [i32, i32, i32],  # returns int64
     "rf_pair_axis_sums": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp],
+    "rf_se3_attention_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                             i32, vp],
+    "rf_se3_norm_bias_bwd_ws_bytes": [i64, i32, i32],  # returns int64
+    "rf_se3_norm_bias_bwd": [vp, vp, vp, vp, vp, i64, i32, i32, vp, i64, vp],
+    "rf_se3_gram_bwd": [vp, vp, vp, i32, i64, i32, i32, vp],
+    "rf_se3_attn_apply_bwd": [vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+    "rf_layernorm_act_bwd_ws_bytes": [i64, i32],  # returns int64
+    "rf_layernorm_act_bwd": [vp, vp, vp, vp, f32, i32, vp, vp, vp, i64, i32, vp, i64, vp],
     "rf_debug_gemm_stamps": [vp],
     "rf_debug_gemm_fast_stamps": [vp],
     "rf_gemm_last_family": [],
@@ -161,6 +169,8 @@ def _load(path):
     handle.rf_layernorm_bwd_fused_ws_bytes.restype = C.c_int64
     handle.rf_embedding_bwd_ws_bytes.restype = C.c_int64
     handle.rf_pair_axis_sums_ws_bytes.restype = C.c_int64
+    handle.rf_se3_norm_bias_bwd_ws_bytes.restype = C.c_int64
+    handle.rf_layernorm_act_bwd_ws_bytes.restype = C.c_int64
     handle.rf_build_info.restype = C.c_char_p
     handle.rf_build_info.argtypes = []
     return handle

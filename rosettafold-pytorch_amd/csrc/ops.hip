@@ -1583,7 +1583,7 @@ extern "C" int rf_add_pos_enc(const float* x, const int64_t* aa_idx, const float
   return rf_launch_status();
 }
 
-extern "C" int rf_version(void) { return 21; }
+extern "C" int rf_version(void) { return 22; }
 #ifdef RF_H16_IS_F16
 extern "C" const char* rf_build_info(void) { return "librfmi_f16 gfx950 (MI355X) round-3: 16-bit operand type = IEEE fp16"; }
 #else

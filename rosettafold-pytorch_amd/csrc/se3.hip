@@ -717,3 +717,407 @@ extern "C" int rf_center_ca(const float* xyz, float* y, int64_t nres, void* stre
   hipLaunchKernelGGL(center_ca_kernel, dim3(cdiv(nres * 9, 256)), dim3(256), 0, (hipStream_t)stream, xyz, y, nres * 9);
   return rf_launch_status();
 }
+
+// ================================================================================================
+// Backward of the node layers and of the graph attention (include/rfmi.h: rf_se3_attention_bwd, rf_se3_norm_bias_bwd,
+// rf_se3_gram_bwd, rf_se3_attn_apply_bwd, rf_layernorm_act_bwd).  Nothing of the forward is saved but its inputs; the fp32
+// operands are widened to fp64, every sum is an fp64 sum and every result is rounded once.  An output element belongs to one
+// thread or one wave; the two sums over nodes (dbias, dgamma / dbeta) go through partials in the caller's workspace, added in a
+// fixed order.  No atomics: the same bits run to run.
+// ================================================================================================
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// sum over the 256 threads of a block, the same value in every thread; red: 4 doubles of LDS (reusable after the call)
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ---- graph attention: one wave per (dst node, head), the forward's walk of column dst of the eid map ---------------------------
+__global__ __launch_bounds__(256) void se3_attention_bwd_kernel(const float* k0, const float* k1, const float* q0,
+                                                                const float* q1, const float* v0, const float* v1,
+                                                                const int32_t* eid, const float* g0, const float* g1,
+                                                                int64_t g0_ld, int64_t g1_ld, float* dk0, float* dk1, float* dq0,
+                                                                float* dq1, float* dv0, float* dv1, int heads, int mk0, int mk1,
+                                                                int mv0, int mv1, int V, int L, double inv_sqrt_nfeat) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (wid >= (int64_t)V * heads) return;
+  const int node = wid / heads, hd = wid % heads;
+  const int b = node / L, j = node % L;
+  const int ck0 = mk0 / heads, ck1 = 3 * (mk1 / heads), cv0 = mv0 / heads, cv1 = 3 * (mv1 / heads);
+  // this head's slices: degree 0 [.., m0] at hd * c0, degree 1 [.., m1, 3] at hd * c1 (c1 counts floats)
+  const float* qa = q0 + (int64_t)node * mk0 + hd * ck0;
+  const float* qb = q1 + (int64_t)node * mk1 * 3 + hd * ck1;
+  const float* ga = g0 + (int64_t)node * g0_ld + hd * cv0;
+  const float* gb = g1 + (int64_t)node * g1_ld + hd * cv1;
+  double pr[RF_ATT_MAXPL];
+  int ids[RF_ATT_MAXPL];
+  double mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < RF_ATT_MAXPL; ++t) {
+    const int i = lane + 64 * t;
+    int id = -1;
+    double a = -INFINITY;
+    if (i < L) id = eid[((int64_t)b * L + i) * L + j];
+    if (id >= 0) {
+      const float* ka = k0 + (int64_t)id * mk0 + hd * ck0;
+      const float* kb = k1 + (int64_t)id * mk1 * 3 + hd * ck1;
+      a = 0.0;
+      for (int c = 0; c < ck0; ++c) a = fma((double)ka[c], (double)qa[c], a);
+      for (int c = 0; c < ck1; ++c) a = fma((double)kb[c], (double)qb[c], a);
+      a *= inv_sqrt_nfeat;
+    }
+    pr[t] = a;
+    ids[t] = id;
+    mx = fmax(mx, a);
+  }
+  mx = wave_max_f64(mx);
+  double s = 0.0;
+#pragma unroll
+  for (int t = 0; t < RF_ATT_MAXPL; ++t) {
+    pr[t] = ids[t] >= 0 ? exp(pr[t] - mx) : 0.0;
+    s += pr[t];
+  }
+  s = wave_sum_f64(s);
+  if (!(s > 0.0)) {  // in-degree 0: the output is the constant 0 (wave-uniform branch)
+    for (int c = lane; c < ck0; c += 64) dq0[(int64_t)node * mk0 + hd * ck0 + c] = 0.f;
+    for (int c = lane; c < ck1; c += 64) dq1[(int64_t)node * mk1 * 3 + hd * ck1 + c] = 0.f;
+    return;
+  }
+  // dp_e = <v_e, g_node>,  S = sum_e p_e dp_e;  afterwards pr holds dl_e = p_e (dp_e - S), and dv_e = p_e g is written
+  double dp[RF_ATT_MAXPL];
+  double S = 0.0;
+#pragma unroll
+  for (int t = 0; t < RF_ATT_MAXPL; ++t) {
+    dp[t] = 0.0;
+    if (ids[t] >= 0) {
+      pr[t] /= s;   // one edge: exp(0) / 1 = 1 exactly
+      const float* va = v0 + (int64_t)ids[t] * mv0 + hd * cv0;
+      const float* vb = v1 + (int64_t)ids[t] * mv1 * 3 + hd * cv1;
+      float* da = dv0 + (int64_t)ids[t] * mv0 + hd * cv0;
+      float* db = dv1 + (int64_t)ids[t] * mv1 * 3 + hd * cv1;
+      double d = 0.0;
+      for (int c = 0; c < cv0; ++c) {
+        d = fma((double)va[c], (double)ga[c], d);
+        da[c] = (float)(pr[t] * (double)ga[c]);
+      }
+      for (int c = 0; c < cv1; ++c) {
+        d = fma((double)vb[c], (double)gb[c], d);
+        db[c] = (float)(pr[t] * (double)gb[c]);
+      }
+      dp[t] = d;
+      S += pr[t] * d;   // (no FMA contraction across the statement matters here: one edge gives 1 * d = d exactly either way)
+    }
+  }
+  S = wave_sum_f64(S);
+#pragma unroll
+  for (int t = 0; t < RF_ATT_MAXPL; ++t) {
+    if (ids[t] >= 0) {
+      const double dl = pr[t] * (dp[t] - S) * inv_sqrt_nfeat;   // one edge: dp - S = 0 exactly
+      pr[t] = dl;
+      float* da = dk0 + (int64_t)ids[t] * mk0 + hd * ck0;
+      float* db = dk1 + (int64_t)ids[t] * mk1 * 3 + hd * ck1;
+      for (int c = 0; c < ck0; ++c) da[c] = (float)(dl * (double)qa[c]);
+      for (int c = 0; c < ck1; ++c) db[c] = (float)(dl * (double)qb[c]);
+    }
+  }
+  for (int c = 0; c < ck0 + ck1; ++c) {
+    double a = 0.0;
+#pragma unroll
+    for (int t = 0; t < RF_ATT_MAXPL; ++t)
+      if (ids[t] >= 0)
+        a = fma(pr[t], (double)(c < ck0 ? k0[(int64_t)ids[t] * mk0 + hd * ck0 + c]
+                                        : k1[(int64_t)ids[t] * mk1 * 3 + hd * ck1 + (c - ck0)]), a);
+    a = wave_sum_f64(a);
+    if (lane == 0) {
+      if (c < ck0) dq0[(int64_t)node * mk0 + hd * ck0 + c] = (float)a;
+      else dq1[(int64_t)node * mk1 * 3 + hd * ck1 + (c - ck0)] = (float)a;
+    }
+  }
+}
+
+extern "C" int rf_se3_attention_bwd(const float* k0, const float* k1, const float* q0, const float* q1, const float* v0,
+                                    const float* v1, const int32_t* eid, const float* g0, const float* g1, int64_t g0_ld,
+                                    int64_t g1_ld, float* dk0, float* dk1, float* dq0, float* dq1, float* dv0, float* dv1,
+                                    int heads, int mk0, int mk1, int mv0, int mv1, int V, int L, void* stream) {
+  if (heads <= 0 || mk0 < 0 || mk1 < 0 || mv0 < 0 || mv1 < 0 || mk0 + mk1 <= 0 || mv0 + mv1 <= 0 || V <= 0 || L <= 0) return RF_EINVAL;
+  if (L > 64 * RF_ATT_MAXPL || V % L) return RF_EINVAL;
+  if (mk0 % heads || mk1 % heads || mv0 % heads || mv1 % heads) return RF_EINVAL;
+  if (!eid || (mk0 && (!k0 || !q0 || !dk0 || !dq0)) || (mk1 && (!k1 || !q1 || !dk1 || !dq1)) || (mv0 && (!v0 || !g0 || !dv0)) ||
+      (mv1 && (!v1 || !g1 || !dv1)))
+    return RF_EINVAL;
+  if (g0_ld <= 0) g0_ld = mv0;
+  if (g1_ld <= 0) g1_ld = 3 * mv1;
+  if (g0_ld < mv0 || g1_ld < 3 * mv1) return RF_EINVAL;
+  const double nfeat = (double)(mk0 + 3 * mk1);
+  hipLaunchKernelGGL(se3_attention_bwd_kernel, dim3(cdiv((int64_t)V * heads, 4)), dim3(256), 0, (hipStream_t)stream, k0, k1, q0,
+                     q1, v0, v1, eid, g0, g1, g0_ld, g1_ld, dk0, dk1, dq0, dq1, dv0, dv1, heads, mk0, mk1, mv0, mv1, V, L,
+                     1.0 / sqrt(nfeat));
+  return rf_launch_status();
+}
+
+// ---- GNormBias: a thread per (node, channel); its <v, g> / n goes to the workspace, a block per channel adds them in node order --
+__global__ __launch_bounds__(256) void norm_bias_bwd_kernel(const float* v, const float* bias, const float* g, float* dv,
+                                                            double* part, int64_t VM, int m, int nc) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= VM) return;
+  const int c = e % m;
+  float n2 = 0.f;   // the gate is the forward's own fp32 expression, so that both take the same side of relu's kink
+  for (int a = 0; a < nc; ++a) n2 = fmaf(v[e * nc + a], v[e * nc + a], n2);
+  const bool open = fmaxf(fmaxf(sqrtf(n2), 1e-12f) + bias[c], 0.f) > 0.f;
+  if (!open) {
+    for (int a = 0; a < nc; ++a) dv[e * nc + a] = 0.f;
+    part[e] = 0.0;
+    return;
+  }
+  double q = 0.0, vg = 0.0;
+  for (int a = 0; a < nc; ++a) {
+    q = fma((double)v[e * nc + a], (double)v[e * nc + a], q);
+    vg = fma((double)v[e * nc + a], (double)g[e * nc + a], vg);
+  }
+  const double n = fmax(sqrt(q), 1e-12);
+  const double t = n + (double)bias[c];
+  const double r = vg / n;                       // <v, g> / n = d loss / d t
+  // |v| under the clamp: n is the constant 1e-12 and only the direct term is left
+  const double w = sqrt(q) >= 1e-12 ? (1.0 / n - t / (n * n)) * r : 0.0;
+  for (int a = 0; a < nc; ++a) dv[e * nc + a] = (float)((t / n) * (double)g[e * nc + a] + w * (double)v[e * nc + a]);
+  part[e] = r;
+}
+
+// out[c] = sum over rows r of part[r * m + c], one block per column: thread t adds rows t, t + 256, ... in order, the 256 sums
+// are added as a fixed tree
+__global__ __launch_bounds__(256) void column_sum_f64_kernel(const double* part, float* out, int64_t rows, int m) {
+  __shared__ double red[256];
+  const int c = blockIdx.x;
+  double s = 0.0;
+  for (int64_t r = threadIdx.x; r < rows; r += 256) s += part[r * m + c];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[c] = (float)red[0];
+}
+
+extern "C" int64_t rf_se3_norm_bias_bwd_ws_bytes(int64_t V, int m, int deg) {
+  if (V <= 0 || m <= 0 || deg < 0) return 0;
+  return V * m * (int64_t)sizeof(double);
+}
+
+extern "C" int rf_se3_norm_bias_bwd(const float* v, const float* bias, const float* g, float* dv, float* dbias, int64_t V, int m,
+                                    int deg, void* workspace, int64_t ws_bytes, void* stream) {
+  if (!v || !bias || !g || !dv || !dbias || V <= 0 || m <= 0 || deg < 0) return RF_EINVAL;
+  if (!workspace || ((uintptr_t)workspace % 8) || ws_bytes < rf_se3_norm_bias_bwd_ws_bytes(V, m, deg)) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(norm_bias_bwd_kernel, dim3(cdiv(V * m, 256)), dim3(256), 0, s, v, bias, g, dv, (double*)workspace, V * m, m,
+                     2 * deg + 1);
+  hipLaunchKernelGGL(column_sum_f64_kernel, dim3(m), dim3(256), 0, s, (const double*)workspace, dbias, V, m);
+  return rf_launch_status();
+}
+
+// ---- GAttentiveSelfInt front: a thread per (node, a) owns dv[n, a, :] ---------------------------------------------------------
+__global__ __launch_bounds__(256) void gram_bwd_kernel(const float* v, const float* ds, float* dv, int64_t VM, int m, int nc,
+                                                       int accumulate) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (node, a)
+  if (e >= VM) return;
+  const int a = e % m;
+  const int64_t n = e / m;
+  const float* vn = v + n * m * nc;
+  const float* dn = ds + n * m * m;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int b = 0; b < m; ++b) {
+    float d = 0.f;   // the forward's fp32 product decides which side of the clamp the entry is on
+    for (int c = 0; c < nc; ++c) d = fmaf(vn[a * nc + c], vn[b * nc + c], d);
+    if (fabsf(d) >= 1e-12f) {
+      const double w = (double)dn[a * m + b] + (double)dn[b * m + a];
+      for (int c = 0; c < nc; ++c) acc[c] = fma(w, (double)vn[b * nc + c], acc[c]);
+    }
+  }
+  for (int c = 0; c < nc; ++c) dv[e * nc + c] = (float)(accumulate ? acc[c] + (double)dv[e * nc + c] : acc[c]);
+}
+
+extern "C" int rf_se3_gram_bwd(const float* v, const float* ds, float* dv, int accumulate, int64_t V, int m, int deg,
+                               void* stream) {
+  if (!v || !ds || !dv || V <= 0 || m <= 0 || deg < 0 || deg > 1) return RF_EINVAL;
+  hipLaunchKernelGGL(gram_bwd_kernel, dim3(cdiv(V * m, 256)), dim3(256), 0, (hipStream_t)stream, v, ds, dv, V * m, m, 2 * deg + 1,
+                     accumulate);
+  return rf_launch_status();
+}
+
+// ---- GAttentiveSelfInt back: a block per node; a wave per output row o recomputes its softmax and writes datt[n, o, :], the
+// probabilities stay in LDS for dx[n, m, :] = sum_o p[o, m] g[n, o, :] ------------------------------------------------------------
+__global__ __launch_bounds__(256) void attn_apply_bwd_kernel(const float* att, const float* x, const float* g, float* datt,
+                                                             float* dx, int m_out, int m_in, int nc) {
+  extern __shared__ double sp[];   // [m_out][m_in]
+  const int64_t n = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* xn = x + n * m_in * nc;
+  const float* gn = g + n * m_out * nc;
+  for (int o = wave; o < m_out; o += 4) {
+    const float* a = att + (n * m_out + o) * m_in;
+    double mx = -INFINITY;
+    for (int m = lane; m < m_in; m += 64) mx = fmax(mx, (double)a[m]);
+    mx = wave_max_f64(mx);
+    double s = 0.0;
+    for (int m = lane; m < m_in; m += 64) {
+      const double p = exp((double)a[m] - mx);
+      sp[o * m_in + m] = p;
+      s += p;
+    }
+    s = wave_sum_f64(s);
+    double S = 0.0;
+    for (int m = lane; m < m_in; m += 64) {
+      const double p = sp[o * m_in + m] / s;
+      sp[o * m_in + m] = p;
+      double u = 0.0;
+      for (int c = 0; c < nc; ++c) u = fma((double)gn[o * nc + c], (double)xn[m * nc + c], u);
+      S = fma(p, u, S);
+    }
+    S = wave_sum_f64(S);
+    for (int m = lane; m < m_in; m += 64) {
+      double u = 0.0;
+      for (int c = 0; c < nc; ++c) u = fma((double)gn[o * nc + c], (double)xn[m * nc + c], u);
+      datt[(n * m_out + o) * m_in + m] = (float)(sp[o * m_in + m] * (u - S));
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < m_in * nc; e += 256) {
+    const int m = e / nc, c = e % nc;
+    double acc = 0.0;
+    for (int o = 0; o < m_out; ++o) acc = fma(sp[o * m_in + m], (double)gn[o * nc + c], acc);
+    dx[n * m_in * nc + e] = (float)acc;
+  }
+}
+
+extern "C" int rf_se3_attn_apply_bwd(const float* att, const float* x, const float* g, float* datt, float* dx, int64_t V, int m_out,
+                                     int m_in, int deg, void* stream) {
+  if (!att || !x || !g || !datt || !dx || V <= 0 || V > 0x7fffffffLL || m_out <= 0 || m_in <= 0 || deg < 0 || deg > 1)
+    return RF_EINVAL;
+  const int64_t lds = (int64_t)m_out * m_in * (int64_t)sizeof(double);
+  if (lds > 64 * 1024) return RF_EINVAL;
+  hipLaunchKernelGGL(attn_apply_bwd_kernel, dim3((unsigned)V), dim3(256), (size_t)lds, (hipStream_t)stream, att, x, g, datt, dx,
+                     m_out, m_in, 2 * deg + 1);
+  return rf_launch_status();
+}
+
+// ---- LayerNorm (+ LeakyReLU) backward at any D: a block per row writes dx and the row's (mean, rstd); a second kernel takes the
+// column sums of ge and ge xhat over chunks of LNA_ROWS rows, a third adds the chunks in order ------------------------------------
+#define LNA_ROWS 64
+__device__ __forceinline__ double lna_ge(float g, double xh, float gamma, float beta, int act) {
+  // RF_ACT_LEAKY (slope 0.01, csrc/ops.hip): the gate is gamma xhat + beta <= 0 with the fp64 statistics of this kernel, NOT the
+  // forward's fp32 value (rf_layernorm keeps a row in one wave's registers and sums in another order, which a block-strided
+  // kernel cannot replay): an output within fp32 rounding distance of 0 may take the other side of the kink here
+  return act == RF_ACT_LEAKY && !(xh * (double)gamma + (double)beta > 0.0) ? 0.01 * (double)g : (double)g;
+}
+
+__global__ __launch_bounds__(256) void layernorm_act_bwd_row_kernel(const float* x, const float* g, const float* gamma,
+                                                                    const float* beta, float eps, int act, float* dx,
+                                                                    double* stats, int D) {
+  // no FMA contraction in here: ge gamma must be the same rounded product where it is summed and where the sum is taken off it,
+  // so that a row of one element gives dx = 0 exactly (the fma() calls below are explicit and stay)
+#pragma clang fp contract(off)
+  __shared__ double red[4];
+  const int64_t r = blockIdx.x;
+  const float* xr = x + r * D;
+  const float* gr = g + r * D;
+  double s = 0.0;
+  for (int c = threadIdx.x; c < D; c += 256) s += (double)xr[c];
+  const double mean = block_sum_f64(s, red) / (double)D;
+  double q = 0.0;
+  for (int c = threadIdx.x; c < D; c += 256) {
+    const double d = (double)xr[c] - mean;
+    q = fma(d, d, q);
+  }
+  const double rstd = 1.0 / sqrt(block_sum_f64(q, red) / (double)D + (double)eps);
+  double m1 = 0.0, m2 = 0.0;
+  for (int c = threadIdx.x; c < D; c += 256) {
+    const double xh = ((double)xr[c] - mean) * rstd;
+    const double gg = lna_ge(gr[c], xh, gamma[c], beta[c], act) * (double)gamma[c];
+    m1 += gg;
+    m2 = fma(gg, xh, m2);
+  }
+  m1 = block_sum_f64(m1, red) / (double)D;
+  m2 = block_sum_f64(m2, red) / (double)D;
+  for (int c = threadIdx.x; c < D; c += 256) {
+    const double xh = ((double)xr[c] - mean) * rstd;
+    const double gg = lna_ge(gr[c], xh, gamma[c], beta[c], act) * (double)gamma[c];
+    dx[r * D + c] = (float)(rstd * (gg - m1 - xh * m2));
+  }
+  if (threadIdx.x == 0) {
+    stats[2 * r] = mean;
+    stats[2 * r + 1] = rstd;
+  }
+}
+
+// part[chunk][0][c] = sum of ge, part[chunk][1][c] = sum of ge xhat over the chunk's rows, in row order; a thread per column
+__global__ __launch_bounds__(256) void layernorm_act_bwd_cols_kernel(const float* x, const float* g, const float* gamma,
+                                                                     const float* beta, int act, const double* stats,
+                                                                     double* part, int64_t rows, int D) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= D) return;
+  const int64_t r0 = (int64_t)blockIdx.y * LNA_ROWS;
+  const int64_t r1 = r0 + LNA_ROWS < rows ? r0 + LNA_ROWS : rows;
+  const float ga = gamma[c], be = beta[c];
+  double sg = 0.0, sx = 0.0;
+  for (int64_t r = r0; r < r1; ++r) {
+    const double xh = ((double)x[r * D + c] - stats[2 * r]) * stats[2 * r + 1];
+    const double ge = lna_ge(g[r * D + c], xh, ga, be, act);
+    sg += ge;
+    sx = fma(ge, xh, sx);
+  }
+  part[((int64_t)blockIdx.y * 2) * D + c] = sg;
+  part[((int64_t)blockIdx.y * 2 + 1) * D + c] = sx;
+}
+
+__global__ __launch_bounds__(256) void layernorm_act_bwd_finalize_kernel(const double* part, float* dgamma, float* dbeta, int nchunk,
+                                                                         int D) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= 2 * D) return;
+  const int which = c / D, col = c % D;
+  double t = 0.0;
+  for (int k = 0; k < nchunk; ++k) t += part[((int64_t)k * 2 + which) * D + col];
+  if (which == 0) {
+    if (dbeta) dbeta[col] = (float)t;
+  } else if (dgamma) {
+    dgamma[col] = (float)t;
+  }
+}
+
+extern "C" int64_t rf_layernorm_act_bwd_ws_bytes(int64_t rows, int D) {
+  if (rows <= 0 || D <= 0) return 0;
+  return (rows * 2 + (int64_t)cdiv(rows, LNA_ROWS) * 2 * D) * (int64_t)sizeof(double);
+}
+
+extern "C" int rf_layernorm_act_bwd(const float* x, const float* g, const float* gamma, const float* beta, float eps, int act,
+                                    float* dx, float* dgamma, float* dbeta, int64_t rows, int D, void* workspace, int64_t ws_bytes,
+                                    void* stream) {
+  if (!x || !g || !gamma || !beta || !dx || rows <= 0 || rows > 0x7fffffffLL || D <= 0) return RF_EINVAL;
+  if (act != RF_ACT_NONE && act != RF_ACT_LEAKY) return RF_EINVAL;
+  const unsigned nchunk = cdiv(rows, LNA_ROWS);
+  if (nchunk > 65535u) return RF_EINVAL;
+  if (!workspace || ((uintptr_t)workspace % 8) || ws_bytes < rf_layernorm_act_bwd_ws_bytes(rows, D)) return RF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  double* stats = (double*)workspace;
+  double* part = stats + rows * 2;
+  hipLaunchKernelGGL(layernorm_act_bwd_row_kernel, dim3((unsigned)rows), dim3(256), 0, s, x, g, gamma, beta, eps, act, dx, stats, D);
+  if (dgamma || dbeta) {
+    hipLaunchKernelGGL(layernorm_act_bwd_cols_kernel, dim3(cdiv(D, 256), nchunk), dim3(256), 0, s, x, g, gamma, beta, act,
+                       (const double*)stats, part, rows, D);
+    hipLaunchKernelGGL(layernorm_act_bwd_finalize_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, s, (const double*)part, dgamma,
+                       dbeta, (int)nchunk, D);
+  }
+  return rf_launch_status();
+}

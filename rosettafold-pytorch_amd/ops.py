@@ -1264,6 +1264,122 @@ def se3_attn_apply(att, x, m_out, deg):
     return y
 
 
+# ---- backward of the SE(3) node layers and of the graph attention (csrc/se3.hip; fp32 in every compute mode)
+def _f32c(name, t, shape):
+    """t is a contiguous fp32 device tensor of `shape` (ValueError otherwise)"""
+    if not torch.is_tensor(t) or t.dtype != F32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{name}: a contiguous fp32 tensor {list(shape)} is needed, got {got}")
+
+
+def se3_attention_bwd(k0, k1, q0, q1, v0, v1, eid, g0, g1, heads, mk0, mk1, mv0, mv1, V, L_):
+    """Backward of se3_attention (rf_se3_attention_bwd): k_d / v_d per edge [cap, m, 2d+1], q_d per node [V, m, 2d+1], eid the
+    dense int32 map [B, L, L]; g_d fp32 [V, C_d, 2d+1] with C_d >= mv_d, the gradient of out_d -- the whole GCat buffer's gradient
+    may be handed in, its leading mv_d channels are read.  Returns (dk0, dk1, dq0, dq1, dv0, dv1), shaped like k, q and v; edge rows
+    at or above the edge count are not written (they are allocated, never read by a consumer)."""
+    _need_cuda(k0, k1, q0, q1, v0, v1, eid, g0, g1)
+    if L_ > 1024:
+        raise ValueError(f"se3_attention_bwd: chain lengths up to 1024, got {L_}")
+    if L_ <= 0 or V <= 0 or V % L_ or heads <= 0 or any(m % heads for m in (mk0, mk1, mv0, mv1)):
+        raise ValueError(f"se3_attention_bwd: V = {V}, L = {L_}, heads = {heads}, channels {(mk0, mk1, mv0, mv1)}")
+    cap = k0.shape[0]
+    for name, t, m, d in (("k0", k0, mk0, 0), ("k1", k1, mk1, 1), ("v0", v0, mv0, 0), ("v1", v1, mv1, 1)):
+        _f32c("se3_attention_bwd " + name, t, (cap, m, 2 * d + 1))
+    _f32c("se3_attention_bwd q0", q0, (V, mk0, 1))
+    _f32c("se3_attention_bwd q1", q1, (V, mk1, 3))
+    if eid.dtype != torch.int32 or tuple(eid.shape) != (V // L_, L_, L_) or not eid.is_contiguous():
+        raise ValueError(f"se3_attention_bwd: eid must be a contiguous int32 [{V // L_}, {L_}, {L_}] tensor")
+    for name, t, m, d in (("g0", g0, mv0, 0), ("g1", g1, mv1, 1)):
+        if t.dim() != 3 or t.shape[1] < m:
+            raise ValueError(f"se3_attention_bwd {name}: [V, >= {m}, {2 * d + 1}] is needed, got {tuple(t.shape)}")
+        _f32c("se3_attention_bwd " + name, t, (V, t.shape[1], 2 * d + 1))
+    dk0, dk1, dq0, dq1, dv0, dv1 = (torch.empty_like(t) for t in (k0, k1, q0, q1, v0, v1))
+    check(lib.rf_se3_attention_bwd(ptr(k0), ptr(k1), ptr(q0), ptr(q1), ptr(v0), ptr(v1), ptr(eid), ptr(g0), ptr(g1), g0.shape[1],
+                                   3 * g1.shape[1], ptr(dk0), ptr(dk1), ptr(dq0), ptr(dq1), ptr(dv0), ptr(dv1), heads, mk0, mk1,
+                                   mv0, mv1, V, L_, stream()), "rf_se3_attention_bwd")
+    return dk0, dk1, dq0, dq1, dv0, dv1
+
+
+def se3_norm_bias_bwd(v, bias, g, deg):
+    """Backward of se3_norm_bias (rf_se3_norm_bias_bwd): v, g fp32 [V, m, 2 deg + 1], bias fp32 [m].  Returns (dv, dbias)."""
+    _need_cuda(v, bias, g)
+    if not torch.is_tensor(v) or v.dim() != 3 or v.shape[2] != 2 * deg + 1 or v.numel() == 0:
+        raise ValueError(f"se3_norm_bias_bwd: v must be a non-empty [V, m, {2 * deg + 1}] tensor")
+    V, m, _ = v.shape
+    _f32c("se3_norm_bias_bwd v", v, v.shape)
+    _f32c("se3_norm_bias_bwd g", g, v.shape)
+    _f32c("se3_norm_bias_bwd bias", bias, (m,))
+    ws_bytes = int(lib.rf_se3_norm_bias_bwd_ws_bytes(V, m, deg))
+    ws = torch.empty(ws_bytes // 8, device=v.device, dtype=torch.float64)
+    dv = torch.empty_like(v)
+    dbias = torch.empty(m, device=v.device, dtype=F32)
+    check(lib.rf_se3_norm_bias_bwd(ptr(v), ptr(bias), ptr(g), ptr(dv), ptr(dbias), V, m, deg, ptr(ws), ws_bytes, stream()),
+          "rf_se3_norm_bias_bwd")
+    return dv, dbias
+
+
+def se3_gram_bwd(v, ds, deg, dv=None):
+    """Backward of se3_gram (rf_se3_gram_bwd): v fp32 [V, m, 2 deg + 1], ds fp32 [V, m*m].  dv: a gradient of v to add to, in place
+    (GAttentiveSelfInt's apply path); None: a fresh tensor.  Returns dv."""
+    _need_cuda(v, ds, dv)
+    if not torch.is_tensor(v) or v.dim() != 3 or deg not in (0, 1) or v.shape[2] != 2 * deg + 1 or v.numel() == 0:
+        raise ValueError("se3_gram_bwd: v must be a non-empty [V, m, 2 deg + 1] tensor of degree 0 or 1")
+    V, m, _ = v.shape
+    _f32c("se3_gram_bwd v", v, v.shape)
+    _f32c("se3_gram_bwd ds", ds, (V, m * m))
+    acc = dv is not None
+    if acc:
+        _f32c("se3_gram_bwd dv", dv, v.shape)
+    else:
+        dv = torch.empty_like(v)
+    check(lib.rf_se3_gram_bwd(ptr(v), ptr(ds), ptr(dv), int(acc), V, m, deg, stream()), "rf_se3_gram_bwd")
+    return dv
+
+
+def se3_attn_apply_bwd(att, x, g, m_out, deg):
+    """Backward of se3_attn_apply (rf_se3_attn_apply_bwd): att fp32 [V, m_out*m_in], x fp32 [V, m_in, 2 deg + 1], g fp32
+    [V, m_out, 2 deg + 1].  Returns (datt like att, dx like x)."""
+    _need_cuda(att, x, g)
+    if not torch.is_tensor(x) or x.dim() != 3 or deg not in (0, 1) or x.shape[2] != 2 * deg + 1 or x.numel() == 0 or m_out <= 0:
+        raise ValueError("se3_attn_apply_bwd: x must be a non-empty [V, m_in, 2 deg + 1] tensor of degree 0 or 1")
+    V, m_in, nc = x.shape
+    if m_out * m_in > 8192:
+        raise ValueError(f"se3_attn_apply_bwd: m_out * m_in = {m_out * m_in} is beyond the 8192 probabilities a block keeps")
+    _f32c("se3_attn_apply_bwd x", x, x.shape)
+    _f32c("se3_attn_apply_bwd att", att, (V, m_out * m_in))
+    _f32c("se3_attn_apply_bwd g", g, (V, m_out, nc))
+    datt, dx = torch.empty_like(att), torch.empty_like(x)
+    check(lib.rf_se3_attn_apply_bwd(ptr(att), ptr(x), ptr(g), ptr(datt), ptr(dx), V, m_out, m_in, deg, stream()),
+          "rf_se3_attn_apply_bwd")
+    return datt, dx
+
+
+def layernorm_act_bwd(x, g, gamma, beta, *, eps=1e-5, act=L.ACT_NONE):
+    """Backward of layernorm(..., act=act) over the last dim at any width (rf_layernorm_act_bwd): x fp32 (the forward's input), g
+    fp32 gradient of the activation's output, act = L.ACT_LEAKY or L.ACT_NONE.  Returns (dx, dgamma [D], dbeta [D]), fp32."""
+    _need_cuda(x, g, gamma, beta)
+    if act not in (L.ACT_NONE, L.ACT_LEAKY):
+        raise ValueError("layernorm_act_bwd: act must be ACT_NONE or ACT_LEAKY")
+    if not torch.is_tensor(x) or x.dim() < 1 or x.numel() == 0:
+        raise ValueError("layernorm_act_bwd: x must be a non-empty tensor")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    _f32c("layernorm_act_bwd x", x, x.shape)
+    _f32c("layernorm_act_bwd g", g, x.shape)
+    _f32c("layernorm_act_bwd gamma", gamma, (D,))
+    _f32c("layernorm_act_bwd beta", beta, (D,))
+    if rows > 64 * 65535:
+        raise ValueError(f"layernorm_act_bwd: at most {64 * 65535} rows, got {rows}")
+    ws_bytes = int(lib.rf_layernorm_act_bwd_ws_bytes(rows, D))
+    ws = torch.empty(ws_bytes // 8, device=x.device, dtype=torch.float64)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(D, device=x.device, dtype=F32)
+    dbeta = torch.empty(D, device=x.device, dtype=F32)
+    check(lib.rf_layernorm_act_bwd(ptr(x), ptr(g), ptr(gamma), ptr(beta), float(eps), int(act), ptr(dx), ptr(dgamma), ptr(dbeta),
+                                   rows, D, ptr(ws), ws_bytes, stream()), "rf_layernorm_act_bwd")
+    return dx, dgamma, dbeta
+
+
 def coord_apply(xyz, disp):
     out = torch.empty_like(xyz)
     check(lib.rf_coord_apply(ptr(xyz), ptr(disp), ptr(out), xyz.shape[0] * xyz.shape[1], stream()), "rf_coord_apply")

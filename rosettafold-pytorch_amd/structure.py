@@ -64,8 +64,40 @@ class GConvSE3Partial(nn.Module):
                 self.kernel_unary[f"({di},{do})"] = PairwiseConv(di, mi, do, mo, edge_dim=edge_dim)
 
 
-class G1x1SE3(nn.Module):
-    """ea/modules.py:328-361."""
+class _FiberModule(RecordingModule):
+    """A node layer of the SE(3)-Transformer on the reference's fiber dicts h = {degree: fp32 [V, m, 2 degree + 1]}, degrees 0 and
+    1, with the opt-in backward of backward.py: `run(h, tape=None)` is the kernel sequence, `_backward(tape, g)` with
+    g = {output degree: contiguous fp32 gradient} returns ({input degree: gradient}, {param: grad}).  forward(h) returns the dict
+    run returns; with enable_backward() and grad mode on it records, one tensor input per degree (an absent degree is None) and
+    one output per output degree.  The structure track is fp32 in every compute mode: nothing here reads the compute dtype, the
+    gradients carry no fp16 scale (_rf_scales_own_grads) and the same bits come out under every set_compute_dtype.  Tapes hold
+    inputs only.  GSE3Res, SE3Transformer, CoordUpdateWithMsaAndPair and RoseTTAFold.forward call run() without a tape: they
+    never record here."""
+    _rf_n_inputs = 2   # the degree-0 and the degree-1 features
+    _rf_scales_own_grads = True
+
+    def _out_degrees(self, h):
+        return sorted(h)
+
+    def _record(self, x0, x1, tape):
+        h = {d: x.float().contiguous() for d, x in ((0, x0), (1, x1)) if x is not None}
+        out = self.run(h, tape=tape)
+        return out if tape is None else tuple(out[d] for d in self._out_degrees(h))
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        g = {d: _scaled_copy(gi, 1.0) for d, gi in zip(self._out_degrees(tape["h"]), gs)}
+        dh, grads = self._backward(tape, g)
+        return (dh.get(0), dh.get(1)), grads
+
+    def forward(self, h):
+        if _recording(self):
+            return dict(zip(self._out_degrees(h), _RecordedFn.apply(self, h.get(0), h.get(1), *self.parameters())))
+        return self._record(h.get(0), h.get(1), None)
+
+
+class G1x1SE3(_FiberModule):
+    """ea/modules.py:328-361.  enable_backward(): the gradients of the transforms and of the input degrees of f_out (an input
+    degree f_out does not name is not read and gets none)."""
 
     def __init__(self, f_in, f_out):
         super().__init__()
@@ -75,7 +107,10 @@ class G1x1SE3(nn.Module):
             mi = f_in[do]
             self.transform[str(do)] = nn.Parameter(torch.randn(mo, mi) / np.sqrt(mi))
 
-    def run(self, h):
+    def _out_degrees(self, h):
+        return sorted(self.f_out)
+
+    def run(self, h, tape=None):
         out = {}
         for d in self.f_out:
             x = h[d]
@@ -86,22 +121,52 @@ class G1x1SE3(nn.Module):
             ops.gemm(x, W, y, V * nc, mo, mi, kc=1, a_row=(nc, mi * nc, 1), a_ko=nc, b_row=(0, 0, mi), b_ko=1,
                      c_row=(nc, mo * nc, 1), c_col=(1, nc), exact=True)
             out[d] = y
+        if tape is not None:
+            tape["h"] = {d: h[d] for d in self.f_out}
         return out
 
+    def _backward(self, tape, g):
+        """Both contractions on the exact fp32 rf_gemm, whose strides express them at any channel count:
+            dx[v,i,c] = sum_o W[o,i] g[v,o,c]         the forward's call on g and W^T
+            dW[o,i]   = sum_{v,c} g[v,o,c] x[v,i,c]    K = (v, c) in chunks of 2 d + 1, a node apart"""
+        dh, grads = {}, {}
+        for d, x in tape["h"].items():
+            V, mi, nc = x.shape
+            W = self.transform[str(d)]
+            mo = W.shape[0]
+            wt = ops.copy(W.detach().t(), torch.empty(mi, mo, device=x.device, dtype=F32))
+            dx = torch.empty_like(x)
+            ops.gemm(g[d], wt, dx, V * nc, mi, mo, kc=1, a_row=(nc, mo * nc, 1), a_ko=nc, b_row=(0, 0, mo), b_ko=1,
+                     c_row=(nc, mi * nc, 1), c_col=(1, nc), exact=True)
+            dw = torch.empty(mo, mi, device=x.device, dtype=F32)
+            ops.gemm(g[d], x, dw, mo, mi, V * nc, kc=nc, a_row=(0, 0, nc), a_ko=mo * nc, b_row=(0, 0, nc), b_ko=mi * nc, exact=True)
+            dh[d], grads[W] = dx, dw
+        return dh, grads
 
-class GNormBias(nn.Module):
-    """ea/modules.py:364-406."""
+
+class GNormBias(_FiberModule):
+    """ea/modules.py:364-406.  enable_backward(): the gradients of the biases and of the input (rf_se3_norm_bias_bwd)."""
 
     def __init__(self, fiber):
         super().__init__()
         self.bias = nn.ParameterDict({str(d): nn.Parameter(torch.randn(m).view(1, m)) for d, m in fiber.items()})
 
-    def run(self, h):
+    def run(self, h, tape=None):
+        if tape is not None:
+            tape["h"] = dict(h)
         return {d: ops.se3_norm_bias(v, self.bias[str(d)].detach().reshape(-1), d) for d, v in h.items()}
 
+    def _backward(self, tape, g):
+        dh, grads = {}, {}
+        for d, v in tape["h"].items():
+            b = self.bias[str(d)]
+            dh[d], db = ops.se3_norm_bias_bwd(v, b.detach().reshape(-1), g[d], d)
+            grads[b] = db.view(b.shape)
+        return dh, grads
 
-class GAttentiveSelfInt(nn.Module):
-    """ea/modules.py:409-473."""
+
+class GAttentiveSelfInt(_FiberModule):
+    """ea/modules.py:409-473.  enable_backward(): the gradients of each degree's LayerNorm and Linear and of the input."""
 
     def __init__(self, f_in, f_out):
         super().__init__()
@@ -113,24 +178,93 @@ class GAttentiveSelfInt(nn.Module):
             nn.init.kaiming_uniform_(lin.weight)
             self.transform[str(d)] = nn.Sequential(LayerNorm(mi * mi), nn.LeakyReLU(), lin)
 
-    def run(self, h):
-        out = {}
-        for d, v in h.items():
+    def _front(self, d, v):
+        """the Gram matrix, its LayerNorm + LeakyReLU and the attention logits of degree d"""
+        net = self.transform[str(d)]
+        s = ops.se3_gram(v, d)
+        t = ops.layernorm(s, _f(net[0].weight), _f(net[0].bias), eps=net[0].eps, out_dtype=F32, act=L.ACT_LEAKY)
+        a = ops.linear(t, net[2].weight.detach(), _f(net[2].bias), out_dtype=F32, exact=True)
+        return s, t, a
+
+    def run(self, h, tape=None):
+        if tape is not None:
+            tape["h"] = dict(h)
+        return {d: ops.se3_attn_apply(self._front(d, v)[2], v, self.f_out[d], d) for d, v in h.items()}
+
+    def _backward(self, tape, g):
+        """Per degree, with s, t, a rebuilt from v by the forward's own launches:
+            d a, d v  = rf_se3_attn_apply_bwd(a, v, g)                    the apply path's share of d v
+            dW, db    = d a^T t, sum d a                                  rf_conv_wgrad in fp32 (exact, any channel count)
+            d t       = d a W                                             rf_gemm, exact fp32
+            d s, dgamma, dbeta = rf_layernorm_act_bwd(s, d t)             LayerNorm + LeakyReLU over m_in^2 values
+            d v      += rf_se3_gram_bwd(v, d s)                           into the same tensor: v is read twice"""
+        dh, grads = {}, {}
+        for d, v in tape["h"].items():
             net = self.transform[str(d)]
-            mi, mo = self.f_in[d], self.f_out[d]
-            s = ops.se3_gram(v, d)
-            t = ops.layernorm(s, _f(net[0].weight), _f(net[0].bias), eps=net[0].eps, out_dtype=F32, act=L.ACT_LEAKY)
-            a = ops.linear(t, net[2].weight.detach(), _f(net[2].bias), out_dtype=F32, exact=True)
-            out[d] = ops.se3_attn_apply(a, v, mo, d)
-        return out
+            lnm, lin = net[0], net[2]
+            s, t, a = self._front(d, v)
+            da, dv = ops.se3_attn_apply_bwd(a, v, g[d], self.f_out[d], d)
+            grads[lin.weight], grads[lin.bias] = ops.conv_wgrad(da, t, 1, bias=True)
+            wt = ops.copy(lin.weight.detach().t(), torch.empty(lin.in_features, lin.out_features, device=v.device, dtype=F32))
+            dt = ops.linear(da, wt, None, out_dtype=F32, exact=True)
+            ds, grads[lnm.weight], grads[lnm.bias] = ops.layernorm_act_bwd(s, dt, _f(lnm.weight), _f(lnm.bias), eps=lnm.eps,
+                                                                          act=L.ACT_LEAKY)
+            dh[d] = ops.se3_gram_bwd(v, ds, d, dv=dv)
+        return dh, grads
 
 
-class GMABSE3(nn.Module):
-    """ea/modules.py:683-774 (no parameters)."""
+class GMABSE3(RecordingModule):
+    """ea/modules.py:683-774 (no parameters) with the skip concatenation behind it (GCat, ea/modules.py:903-928).
+    run(v, k, q, g, skip=None): v, k per-edge and q per-node fiber dicts of degrees 0 and 1, g the graph dict of build_graph (its
+    eid, V and L are read), skip a fiber dict of node features or None.  Returns {degree: [V, mv (+ skip channels), 2 degree + 1]}:
+    the attention in the leading channels, the skip features behind them.  enable_backward(): with grad mode on,
+    forward(v, k, q, g, skip=None) records and the gradient reaches v, k, q and skip (rf_se3_attention_bwd on the leading channels
+    of the output's gradient; the trailing channels are the skip's gradient, bit for bit); the graph takes none.  Rows of the
+    per-edge gradients at or above the edge count are not written.  fp32 in every compute mode, like the node layers."""
+    _rf_n_inputs = 9   # v0, v1, k0, k1, q0, q1, skip0, skip1 (either may be None), the graph (no gradient)
+    _rf_scales_own_grads = True
 
     def __init__(self, f_value, f_key, n_heads):
         super().__init__()
         self.f_value, self.f_key, self.n_heads = dict(f_value), dict(f_key), n_heads
+
+    def run(self, v, k, q, g, skip=None, tape=None):
+        skip = skip or {}
+        fk, fv = self.f_key, self.f_value
+        if tape is not None:
+            tape.update(v=dict(v), k=dict(k), q=dict(q), g=g, skip={d: x.shape for d, x in skip.items()})
+        z0, z1 = ops.se3_attention(k[0], k[1], q[0], q[1], v[0], v[1], g["eid"], self.n_heads, fk[0], fk[1], fv[0], fv[1],
+                                   g["V"], g["L"], skip0=skip.get(0), skip1=skip.get(1))
+        return {0: z0, 1: z1}
+
+    def _backward(self, tape, gz):
+        """gz: {degree: contiguous fp32 gradient of the concatenated output}.  Returns ({"v", "k", "q", "skip": fiber dicts}, {})."""
+        v, k, q, g = tape["v"], tape["k"], tape["q"], tape["g"]
+        fk, fv = self.f_key, self.f_value
+        dk0, dk1, dq0, dq1, dv0, dv1 = ops.se3_attention_bwd(k[0], k[1], q[0], q[1], v[0], v[1], g["eid"], gz[0], gz[1],
+                                                             self.n_heads, fk[0], fk[1], fv[0], fv[1], g["V"], g["L"])
+        dskip = {d: ops.copy(gz[d][:, fv[d]:], torch.empty(shape, device=gz[d].device, dtype=F32))
+                 for d, shape in tape["skip"].items()}
+        return {"v": {0: dv0, 1: dv1}, "k": {0: dk0, 1: dk1}, "q": {0: dq0, 1: dq1}, "skip": dskip}, {}
+
+    def _record(self, v0, v1, k0, k1, q0, q1, s0, s1, g, tape):
+        c = lambda x: x.float().contiguous()  # noqa: E731
+        out = self.run({0: c(v0), 1: c(v1)}, {0: c(k0), 1: c(k1)}, {0: c(q0), 1: c(q1)}, g,
+                       {d: c(x) for d, x in ((0, s0), (1, s1)) if x is not None}, tape=tape)
+        return out if tape is None else (out[0], out[1])
+
+    def _backward_from_autograd(self, tape, gs, s, want):
+        d, _ = self._backward(tape, {0: _scaled_copy(gs[0], 1.0), 1: _scaled_copy(gs[1], 1.0)})
+        return (d["v"][0], d["v"][1], d["k"][0], d["k"][1], d["q"][0], d["q"][1], d["skip"].get(0), d["skip"].get(1), None), {}
+
+    def forward(self, v, k, q, g, skip=None):
+        if g["L"] > 1024:
+            raise ValueError(f"GMABSE3: the graph attention covers chains of up to 1024 residues, got {g['L']}")
+        skip = skip or {}
+        args = (v[0], v[1], k[0], k[1], q[0], q[1], skip.get(0), skip.get(1), g)
+        if _recording(self):
+            return dict(zip((0, 1), _RecordedFn.apply(self, *args)))
+        return self._record(*args, None)
 
 
 def _pack_radial_net(rp):
@@ -247,12 +381,10 @@ class GSE3Res(nn.Module):
                 R[di] = r
             msg[(which, do)] = ops.se3_message(R.get(0), R.get(1), g["basis"], h0, h1f, g["src"], g["count"], mo, do, mi0, mi1, cap)
         q = self.GMAB["q"].run(h)
-        fk, fv = self.f_mid_in, self.f_mid_out
         # skip connection 'cat' (GCat, ea/modules.py:903-928): the attention writes the leading channels of the
         # concatenated buffers, the node's input features are copied in behind them
-        z0, z1 = ops.se3_attention(msg[("k", 0)], msg[("k", 1)], q[0], q[1], msg[("v", 0)], msg[("v", 1)], g["eid"],
-                                   self.n_heads, fk[0], fk[1], fv[0], fv[1], g["V"], g["L"], skip0=h.get(0), skip1=h.get(1))
-        return self.project.run({0: z0, 1: z1})
+        z = self.GMAB["attn"].run({0: msg[("v", 0)], 1: msg[("v", 1)]}, {0: msg[("k", 0)], 1: msg[("k", 1)]}, q, g, skip=h)
+        return self.project.run(z)
 
 
 class SE3Transformer(nn.Module):
